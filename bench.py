@@ -11,7 +11,7 @@ O(N*P) input is generated and kept in HBM), fused rollout + cost + block softmax
 exactly K such steps (`srbd_step` / `srbd_step_sharded`), bracketed by a barrier and a device
 synchronisation; `value` = rollouts of all ranks x K / max-over-ranks wall time.  `p50_step_ms` /
 `p99_step_ms` are per-step host-to-host latencies (>= 1000 steps).  The timed steps launch their
-kernels in the call (as the sharded steps of N > 1 do, so per-N values compare).  One GPU also reports
+kernels in the call (as the sharded steps of N > 1 do, so per-N values compare).  With --full one GPU also reports
 `armed_step`: the same loop with srbd_set_armed (each srbd_step queues its successor's copy / rollout /
 merge behind itself, the copy kernel waiting on a host-mapped word, so the next call stores its inputs
 instead of launching; outputs bit-identical); --armed makes that the timed mode.  `device_chain` is the same
@@ -25,6 +25,22 @@ are exchanged by the merge kernel over xGMI (IPC-mapped mailboxes; RCCL all-gath
   --scaling weak   (default for c1-c4): num_samples rows per GPU, N_total = num_samples x N;
   --scaling strong (default for c5)   : N_total = num_samples split over the N GPUs
                                         (C5: 524 288 = 65 536 per GPU at N=8).
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does what the headline needs and no more: it creates the
+context, warms up, takes the metric's p50 sample when K < --latency-steps (1 000 steps, some 25 ms; after them a
+short timed region runs in the steady state that a long one reaches by itself), times the K steps and prints the line.
+--full adds every other measurement to the same line: `armed_step` / `unarmed_step`, `python_step`,
+`device_chain`, `kernels_us` and `roofline` (runs of their own), `cpu_baseline`, the supplementary shapes
+(`north_star_65536`, `c3`, `c5_1gpu`, the other noise stream, `c5_strong` / `c5_weak` at N > 1) and the interface /
+TAMOLS / C4 latencies.  The options that size those measurements (--device-steps, --other-steps, --targets,
+--extras, --cpu-seconds, --no-cpu-baseline) act under --full only.
+
+--dump-outputs DIR writes what the last timed step returned to its caller as DIR/<name>.npy (float32; best_index
+float64): `best` (and `sigma` for CEM) as the timed loop handed them back, and `grf`, `predicted_state`, `best_cost`,
+`best_index` and the per-rollout `costs` (one GPU) of that step.  The C loop keeps only the parameters of its last
+step, so the step is run again after the timed region from the same warm start, inputs, key and counter (K - 1
+steps, then the K-th through the binding); `replay_bitwise` in the line says that this second pass returned the
+parameters of the timed one bit for bit.  Inputs, keys and counters depend on the arguments alone.
 """
 from __future__ import annotations
 
@@ -68,6 +84,12 @@ def parse_args(argv=None):
     ap.add_argument("--num-samples", type=int, default=0, help="override the workload's num_samples")
     ap.add_argument("--extras", type=int, default=200,
                     help="steps of the supplementary interface / TAMOLS latency probes (0: skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline (other mode, device chain, per-kernel times and "
+                         "roofline, CPU baseline, supplementary shapes, interface / TAMOLS / C4 latencies); without "
+                         "it only the warm-up, the p50 sample and the timed steps run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy")
     return ap.parse_args(argv)
 
 
@@ -405,6 +427,34 @@ def c4_pipeline_latency(steps: int):
                     "the step's input, the rollout launch queued behind it, one host wait) when the context allows"}
 
 
+def last_step_arrays(best, sigma, res, costs=None) -> dict:
+    """What the caller of one step receives, as named arrays (--dump-outputs)."""
+    import numpy as np
+
+    out = {"best": np.asarray(best, np.float32),
+           "grf": np.array(res.grf, np.float32), "predicted_state": np.array(res.predicted_state, np.float32),
+           "best_cost": np.array([res.best_cost], np.float32), "best_index": np.array([res.best_index], np.float64)}
+    if sigma is not None:
+        out["sigma"] = np.asarray(sigma, np.float32)
+    if costs is not None:
+        out["costs"] = np.asarray(costs, np.float32)
+    return out
+
+
+def write_outputs(path: str, arrays: dict, replay_bitwise: bool) -> dict:
+    """DIR/<name>.npy per array; the summary that goes into the line."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    if not replay_bitwise:
+        print("bench: the replayed last step did not return the timed step's parameters bit for bit",
+              file=sys.stderr, flush=True)
+    return {"dir": path, "arrays": {n: list(a.shape) for n, a in sorted(arrays.items())},
+            "bytes": int(sum(a.nbytes for a in arrays.values())), "replay_bitwise": bool(replay_bitwise)}
+
+
 # ---------------------------------------------------------------------------------------------- runs
 def run_steps(step_fn, ins, best, first_counter, count, lat=None):
     """`count` host-to-host steps, counters consecutive (the fused next-step draws are used)."""
@@ -456,6 +506,7 @@ def bench_single(_lib, w, args):
     _, best, state["sigma"] = ctx.bench_host_steps(states, refs, contacts, best, state["sigma"], keys.at(k), k,
                                                    max(1, args.warmup))
     k += max(1, args.warmup)
+    best0, sigma0, k0 = best, state["sigma"], k  # bench_host_steps works on copies
     t0 = time.perf_counter()
     t_us, best, state["sigma"] = ctx.bench_host_steps(states, refs, contacts, best, state["sigma"], keys.at(k), k,
                                                       args.steps)
@@ -463,6 +514,19 @@ def bench_single(_lib, w, args):
     k += args.steps
     if not lat:
         lat = list(t_us * 1e-6)
+    dump = None
+    if args.dump_outputs:  # the last timed step again, for the outputs the C loop does not keep
+        b, sg = best0, sigma0
+        if args.steps > 1:
+            _, b, sg = ctx.bench_host_steps(states, refs, contacts, b, sg, keys.at(k0), k0, args.steps - 1)
+        s, r, c = ins[(args.steps - 1) % len(ins)]  # the C loop's i-th call takes input set i % n
+        b, sg, res, costs = ctx.step(s, r, c, b, sigma=sg, seed=keys.at(k - 1), counter=k - 1, want_costs=True)
+        same = np.array_equal(b, best) and (sg is None or np.array_equal(sg, state["sigma"]))
+        dump = write_outputs(args.dump_outputs, last_step_arrays(best, state["sigma"], res, costs), same)
+    if not args.full:
+        ctx.close()
+        return dict(n_total=w.num_samples, n_local=w.num_samples, wall=wall, lat=lat, transport=None, armed=armed,
+                    dump=dump, timed_us=[round(float(x), 2) for x in t_us] if args.steps <= 64 else None)
     # the other mode over a sample of the same loop
     other = None
     if args.other_steps > 0:
@@ -490,12 +554,13 @@ def bench_single(_lib, w, args):
     kern = ctx.time_kernels(200)
     ctx.close()
     return dict(n_total=w.num_samples, n_local=w.num_samples, wall=wall, lat=lat, kern=kern, dev=dev,
-                transport=None, py_lat=py, armed=armed, other=other, arm_stats=(served, cancelled),
+                transport=None, py_lat=py, armed=armed, other=other, arm_stats=(served, cancelled), dump=dump,
                 timed_us=[round(float(x), 2) for x in t_us] if args.steps <= 64 else None)
 
 
-def bench_multi(_lib, w, args, rank, world, local_rank, scaling, steps=None, device_steps=None):
-    """One sharded workload on this rank's GPU (the process group is up); steps / device_steps override args."""
+def bench_multi(_lib, w, args, rank, world, local_rank, scaling, steps=None, device_steps=None, dump_dir=None):
+    """One sharded workload on this rank's GPU (the process group is up); steps / device_steps override args.
+    dump_dir: every rank runs the last timed step again (--dump-outputs), rank 0 writes its outputs."""
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -514,7 +579,7 @@ def bench_multi(_lib, w, args, rank, world, local_rank, scaling, steps=None, dev
     state = {"sigma": sigma}
 
     def step(s, r, c, b, k):
-        b, sg, _ = mpc.step(s, r, c, b, sigma=state["sigma"], seed=keys.at(k), counter=k)
+        b, sg, state["res"] = mpc.step(s, r, c, b, sigma=state["sigma"], seed=keys.at(k), counter=k)
         if sg is not None:
             state["sigma"] = sg
         return b
@@ -533,6 +598,7 @@ def bench_multi(_lib, w, args, rank, world, local_rank, scaling, steps=None, dev
     dist.barrier()
     torch.cuda.synchronize()
     timed = []
+    best0, sigma0, k0 = best, state["sigma"], k
     t0 = time.perf_counter()
     if c_timed:  # rollout -> xGMI record exchange -> merge, srbd_step_sharded from C
         t_us, best, state["sigma"] = mpc.ctx.bench_host_steps(*arrs, best, state["sigma"], keys.at(k), k, steps)
@@ -547,6 +613,29 @@ def bench_multi(_lib, w, args, rank, world, local_rank, scaling, steps=None, dev
     wall = float(t.item())
     if not lat:
         lat = timed
+    dump = None
+    if dump_dir:  # the last timed step again on every rank (see bench_single)
+        best_t, sigma_t = best, state["sigma"]
+        b, state["sigma"] = best0, sigma0
+        if c_timed:
+            if steps > 1:
+                _, b, state["sigma"] = mpc.ctx.bench_host_steps(*arrs, b, state["sigma"], keys.at(k0), k0, steps - 1)
+            s, r, c = ins[(steps - 1) % len(ins)]
+            b = step(s, r, c, b, k0 + steps - 1)
+        else:
+            b = run_steps(step, ins, b, k0, steps)
+        same = np.array_equal(b, best_t) and (sigma_t is None or np.array_equal(state["sigma"], sigma_t))
+        if rank == 0:
+            dump = write_outputs(dump_dir, last_step_arrays(best_t, sigma_t, state["res"]), same)
+        state["sigma"] = sigma_t
+        dist.barrier()
+    if not args.full:
+        n_local, transport = mpc.ctx.n_local, mpc.transport
+        transports = [None] * world
+        dist.all_gather_object(transports, transport)
+        mpc.close()
+        return dict(n_total=n_total, n_local=n_local, wall=wall, lat=lat, transport=transport, transports=transports,
+                    steps=steps, world=world, dump=dump)
     dev = None
     if device_steps > 0:
         mpc.device_steps(max(1, args.warmup))
@@ -568,7 +657,7 @@ def bench_multi(_lib, w, args, rank, world, local_rank, scaling, steps=None, dev
     dist.all_gather_object(transports, transport)
     mpc.close()
     return dict(n_total=n_total, n_local=n_local, wall=wall, lat=lat, kern=kern, dev=dev, transport=transport,
-                transports=transports, steps=steps, world=world)
+                transports=transports, steps=steps, world=world, dump=dump)
 
 
 def rows_per_rank(n_total: int, world: int):
@@ -631,8 +720,8 @@ def main(argv=None):
 
         torch.cuda.set_device(local_rank)
         dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
-        out = bench_multi(_lib, w, args, rank, world, local_rank, scaling)
-        if world > 1 and args.targets > 0 and args.config == "c2":
+        out = bench_multi(_lib, w, args, rank, world, local_rank, scaling, dump_dir=args.dump_outputs)
+        if args.full and world > 1 and args.targets > 0 and args.config == "c2":
             # BASELINE configs[4] beside the headline: C5's 524 288 rows split over the N GPUs (strong; the
             # one-GPU line's c5_1gpu is its denominator) and 524 288 rows per GPU (weak)
             c5 = CONFIGS["c5"]
@@ -677,6 +766,24 @@ def main(argv=None):
                 (f"host-to-host srbd_step_sharded ({out['transport']} record exchange), "
                  + ("timed in C (srbd_bench_host_steps)" if out["transport"] in ("xgmi", "rccl")
                     else "through the Python binding") + ", max over ranks"),
+        **({"timed_step_us": out["timed_us"]} if out.get("timed_us") else {}),
+        **({"dump_outputs": out["dump"]} if out.get("dump") else {}),
+        "full": bool(args.full),
+    }
+    if args.full:
+        line.update(full_fields(_lib, w, args, out, single, extra))
+    sys.stdout.flush()
+    buf = (json.dumps(line) + "\n").encode()
+    while buf:
+        buf = buf[os.write(out_fd, buf):]
+
+
+def full_fields(_lib, w, args, out, single, extra):
+    """--full: the fields beside the headline, from the run's own extra measurements (bench_single / bench_multi)
+    and from runs of their own (CPU baseline, supplementary shapes, interface / TAMOLS / C4 latencies)."""
+    import numpy as np
+
+    line = {
         "device_chain": out["dev"],
         **({("unarmed_step" if out["armed"] else "armed_step"): out["other"],
             "armed_served_cancelled": list(out["arm_stats"])} if single else {}),
@@ -684,7 +791,6 @@ def main(argv=None):
                          "steps": len(out["py_lat"]), "path": "Context.step (ctypes) -> srbd_step"}
                         if out.get("py_lat") else None),
         "kernels_us": {k: round(v, 3) for k, v in out["kern"].items()},
-        **({"timed_step_us": out["timed_us"]} if out.get("timed_us") else {}),
         "roofline": roofline(w, out["n_local"], out["kern"], pmc_traffic(w.name)),
         **extra,
     }
@@ -709,10 +815,7 @@ def main(argv=None):
         line["interface_step_armed"] = interface_latency(w, args.extras, armed=True)
         line["tamols_c4"] = tamols_latency(args.extras)
         line["c4"] = c4_pipeline_latency(args.extras)
-    sys.stdout.flush()
-    buf = (json.dumps(line) + "\n").encode()
-    while buf:
-        buf = buf[os.write(out_fd, buf):]
+    return line
 
 
 if __name__ == "__main__":

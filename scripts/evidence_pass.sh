@@ -20,7 +20,7 @@ step() {  # step NAME TIMEOUT cmd...  (stdout -> NAME.out, stderr -> NAME.err)
 ARGS="--steps 300 --warmup 10 --no-cpu-baseline --extras 0 --other-steps 0 --targets 0 --latency-steps 300 --device-steps 300"
 SQ="SQ_WAVES SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_BUSY_CYCLES"
 for c in $CFGS; do
-    step stats_${c}_$T 180 rocprofv3 --kernel-trace --stats -d $O/prof_${c}_$T -o run --output-format csv -- python3 $R/bench.py --config $c $ARGS
+    step stats_${c}_$T 180 rocprofv3 --kernel-trace --stats -d $O/prof_${c}_$T -o run --output-format csv -- python3 $R/bench.py --full --config $c $ARGS
     L="launch_probe.py $c step 300"
     step pmcf_${c}_$T 120 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $O/pmcf_${c}_$T -o run --output-format csv -- python3 $R/scripts/$L
     step pmcw_${c}_$T 120 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $O/pmcw_${c}_$T -o run --output-format csv -- python3 $R/scripts/$L

@@ -12,7 +12,7 @@ rc=$?; echo "pytest exit=$rc" >> $O/tests_$T.log; tail -4 $O/tests_$T.log
 if fault $O/tests_$T.log; then echo "GPU fault in tests"; exit 3; fi
 [ $rc -eq 0 ] || exit 4
 if [ "$B" = bench ]; then
-    timeout -k 10 400 python bench.py > $O/bench_$T.json 2> $O/bench_$T.err; rc=$?
+    timeout -k 10 400 python bench.py --full > $O/bench_$T.json 2> $O/bench_$T.err; rc=$?
     if fault $O/bench_$T.err; then echo "GPU fault in bench"; exit 3; fi
     [ $rc -eq 0 ] || { echo "bench rc=$rc"; tail -5 $O/bench_$T.err; exit 5; }
     python - $O/bench_$T.json <<'PY'

@@ -13,7 +13,7 @@ for w in c2 ns; do
   timeout -k 10 120 python scripts/step_tail.py $w > $O/tail_${w}_$T.json 2> $O/tail_${w}_$T.err || { echo "step_tail $w failed"; exit 4; }
   cat $O/tail_${w}_$T.json
 done
-timeout -k 10 300 python bench.py --steps 2000 --no-cpu-baseline --other-steps 1000 > $O/bench_$T.json 2> $O/bench_$T.err || { echo bench failed; tail -5 $O/bench_$T.err; exit 5; }
+timeout -k 10 300 python bench.py --full --steps 2000 --no-cpu-baseline --other-steps 1000 > $O/bench_$T.json 2> $O/bench_$T.err || { echo bench failed; tail -5 $O/bench_$T.err; exit 5; }
 python - $O/bench_$T.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -7,7 +7,7 @@ TESTS=${@:-tests/test_gpu_parity.py tests/test_gpu_fullsize.py tests/test_gpu_tr
 timeout -k 10 400 python -u -m pytest $TESTS -x -q -o addopts="" --timeout 120 --timeout-method thread > $O/tests_$T.log 2>&1 || { echo "tests failed"; tail -30 $O/tests_$T.log; exit 3; }
 tail -2 $O/tests_$T.log
 for cfg in c2 ns; do
-  timeout -k 10 200 python bench.py --config $cfg --steps 2000 --targets 0 --extras 0 --no-cpu-baseline --other-steps 0 --device-steps 1000 > $O/bench_${T}_$cfg.json 2> $O/bench_${T}_$cfg.err || { echo "bench $cfg failed"; tail -5 $O/bench_${T}_$cfg.err; exit 4; }
+  timeout -k 10 200 python bench.py --full --config $cfg --steps 2000 --targets 0 --extras 0 --no-cpu-baseline --other-steps 0 --device-steps 1000 > $O/bench_${T}_$cfg.json 2> $O/bench_${T}_$cfg.err || { echo "bench $cfg failed"; tail -5 $O/bench_${T}_$cfg.err; exit 4; }
   python - "$O/bench_${T}_$cfg.json" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

@@ -15,6 +15,6 @@ timeout -k 10 300 python scripts/c4_split_probe.py > $O/c4_split_$T.json 2> $O/c
 timeout -k 10 180 rocprofv3 --kernel-trace --stats -d $O/prof_c4chain_$T -o run --output-format csv -- python3 $R/scripts/c4_split_probe.py 300 > /dev/null 2> $O/prof_c4chain_$T.err || { echo c4 chain prof failed; exit 5; }
 SQ="SQ_WAVES SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_BUSY_CYCLES"
 RNGS=jax timeout -s KILL 120 rocprofv3 --pmc $SQ --kernel-trace -d $O/sq_jaxns_$T -o run --output-format csv -- python3 $R/scripts/jax_rng_time.py ns > $O/jaxns_$T.json 2> $O/jaxns_$T.err || { echo jax sq failed; exit 5; }
-timeout -k 10 300 python bench.py --sharded --config c5 --num-samples 65536 --steps 1000 --no-cpu-baseline > $O/sharded_w1_c5rank_$T.json 2> $O/sharded_w1_c5rank_$T.err || { echo sharded failed; tail -5 $O/sharded_w1_c5rank_$T.err; exit 6; }
-timeout -k 10 600 python bench.py > $O/bench_$T.json 2> $O/bench_$T.err || { echo bench failed; tail -5 $O/bench_$T.err; exit 7; }
+timeout -k 10 300 python bench.py --full --sharded --config c5 --num-samples 65536 --steps 1000 --no-cpu-baseline > $O/sharded_w1_c5rank_$T.json 2> $O/sharded_w1_c5rank_$T.err || { echo sharded failed; tail -5 $O/sharded_w1_c5rank_$T.err; exit 6; }
+timeout -k 10 600 python bench.py --full > $O/bench_$T.json 2> $O/bench_$T.err || { echo bench failed; tail -5 $O/bench_$T.err; exit 7; }
 echo ALLDONE

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}; cd "$R" || exit 1
 O=$R/gpurun_out; T=${1:-sh}; mkdir -p $O
 for w in "c5 65536" "ns 65536"; do
     set -- $w
-    timeout -k 10 300 python bench.py --sharded --config $1 --num-samples $2 --steps 2000 --device-steps 1000 \
+    timeout -k 10 300 python bench.py --full --sharded --config $1 --num-samples $2 --steps 2000 --device-steps 1000 \
         > $O/sharded_${1}_${2}_$T.json 2> $O/sharded_${1}_${2}_$T.err || { echo "sharded $1 failed"; tail -5 $O/sharded_${1}_${2}_$T.err; exit 1; }
     python - $O/sharded_${1}_${2}_$T.json <<'PY'
 import json, sys

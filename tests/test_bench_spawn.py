@@ -79,3 +79,27 @@ def test_main_spawns_before_loading_anything(monkeypatch):
     assert e.value.code == 5 and calls == [(4, ["--gpus", "4", "--steps", "3"])]
     assert bench.parse_args(["--gpus", "8"]).config == "c2"  # the driver's default: the headline C2, weak scaling
     assert isinstance(bench.parse_args([]), argparse.Namespace)
+
+
+def test_plain_run_is_the_default_and_outputs_are_written(tmp_path):
+    """--full is off unless asked for; --dump-outputs names the directory; the arrays of a step's result go out as
+    float32 / float64 .npy files, one per name, and the line's summary lists them."""
+    import types
+
+    import numpy as np
+
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    a = bench.parse_args(["--full", "--dump-outputs", str(tmp_path / "o")])
+    assert a.full is True and a.dump_outputs == str(tmp_path / "o")
+    res = types.SimpleNamespace(grf=[1.0] * 12, predicted_state=[0.5] * 24, best_cost=2.5, best_index=(1 << 24) + 1)
+    arrs = bench.last_step_arrays(np.arange(6, dtype=np.float64), None, res, np.ones(10))
+    info = bench.write_outputs(a.dump_outputs, arrs, True)
+    assert info["arrays"] == {"best": [6], "best_cost": [1], "best_index": [1], "costs": [10], "grf": [12],
+                              "predicted_state": [24]}
+    assert info["replay_bitwise"] is True and info["bytes"] == 4 * (6 + 1 + 10 + 12 + 24) + 8
+    got = {n: np.load(tmp_path / "o" / (n + ".npy")) for n in info["arrays"]}
+    assert got["best_index"].dtype == np.float64 and int(got["best_index"][0]) == (1 << 24) + 1  # exact past 2^24
+    assert all(v.dtype == np.float32 for n, v in got.items() if n != "best_index")
+    np.testing.assert_array_equal(got["best"], np.arange(6, dtype=np.float32))
+    assert "sigma" in bench.last_step_arrays(np.zeros(3), np.ones(3), res)
