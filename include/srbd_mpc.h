@@ -466,6 +466,50 @@ int srbd_interface_step(srbd_ctx* ctx, srbd_interface_io* io, const float* conta
                         int32_t contact_stride, float* best_params, int32_t params_per_leg, float* sigma,
                         srbd_result* out);
 
+/* ------------------------------------------------------------------ batched environments
+ * One context holding E environments of one configuration, and one host call that steps all of them: the
+ * reference's replica mode (simulation/batched_simulations.py:40-58, SURVEY 3.4 and 8(e) "Replica mode") inside one
+ * process, for evaluation sweeps, dataset generation (simulation/generate_dataset.py) and training loops.  A step
+ * costs four launches whatever E is (input copy, draws or the transpose of injected noise, rollouts, merges) and
+ * one host wait on one published word.
+ *   Shared: the srbd_config -- robot, N (num_samples is per environment), H, method, parametrization, S, dts, Q,
+ *   bounds.  Per environment: everything per step -- state, reference, contact sequence, warm start, noise key.
+ *   Equivalence: environment e returns exactly what srbd_step returns on a context srbd_create(cfg) (world_size 1)
+ *   for the same inputs, (seeds[e], counters[e]) and noise stream -- every output bit for bit (one fixed reduction
+ *   tree, keyed by the environment's own rows 0..N-1).  Device draws of environment e are srbd_draw_noise(seeds[e],
+ *   counters[e])'s; row 0 is zero.  Environments are independent: a NaN state or an all-swing contact sequence in
+ *   one changes nothing in another.
+ *   Range: 1 <= num_envs <= 4096, 1 <= N <= 16 384 (256 leaves of the reduction tree: what one merge block folds;
+ *   beyond that one environment fills the GPU and separate contexts lose nothing).
+ *   Supported: MPPI and random sampling; the three parametrizations at any H and S srbd_create takes; the Philox
+ *   and both JAX streams; injected noise.
+ *   SRBD_E_INVALID (with a message saying which and why): a larger N or num_envs, CEM-MPPI (its draws depend on
+ *   the sigma each step produces, and its merge is one context's column-split hand-off), rank / world_size other
+ *   than 0 / 1.  use_graph is ignored.  There are no batch forms of gait-adaptive sampling, the opt-in cost terms,
+ *   armed steps or the device-resident chains.  A failed allocation: SRBD_E_NOMEM; no device: SRBD_E_NODEVICE.
+ *   A call that returns an error has changed nothing in best_params.  A step whose launches end without publishing
+ *   returns SRBD_E_HIP, leaves the arrival count zero and the next step exact. */
+typedef struct srbd_batch srbd_batch;
+int srbd_batch_create(const srbd_config* cfg, int32_t num_envs, srbd_batch** out);
+void srbd_batch_destroy(srbd_batch* b);
+/* Last error of b, or of the calling thread's last failed srbd_batch_create when b == NULL. */
+const char* srbd_batch_last_error(const srbd_batch* b);
+int srbd_batch_num_envs(const srbd_batch* b);
+/* SRBD_RNG_* (srbd_set_rng); default SRBD_RNG_PHILOX. */
+int srbd_batch_set_rng(srbd_batch* b, int32_t kind);
+/*   states, refs  : E x 24
+ *   contacts      : E x 4 x contact_stride; the first H columns are used
+ *   best_params   : E x P, in: warm starts, out: updated
+ *   noise         : NULL -> device draws; else E x N x P row-major, row 0 of each environment zero
+ *   seeds, counters : E each
+ *   out           : E results
+ *   out_costs     : E x N saturated costs, or NULL */
+int srbd_batch_step(srbd_batch* b, const float* states, const float* refs, const float* contacts,
+                    int32_t contact_stride, float* best_params, const float* noise, const uint64_t* seeds,
+                    const uint64_t* counters, srbd_result* out, float* out_costs);
+/* E x N saturated costs of the last step. */
+int srbd_batch_copy_costs(srbd_batch* b, float* out_costs);
+
 /* Diagnostic: enable != 0 stamps the phases of the following TAMOLS calls; out_us[5] (may be NULL)
  * receives the last call's mean per-block durations of (patch, queries, scores, slice argmin + count)
  * and the span from the first block's start to the last leg's end, in us.  enable == 0 turns it off. */

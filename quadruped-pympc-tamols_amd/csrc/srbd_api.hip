@@ -2627,3 +2627,213 @@ extern "C" int srbd_probe_merge_phases(srbd_ctx* c, uint64_t* host64) {
     return SRBD_OK;
 }
 #endif
+
+// ------------------------------------------------------------------ batched environments (srbd_batch_*)
+// E independent problems of one configuration behind one host call: per step one input copy, one draw (or
+// transpose) launch, one rollout launch and one merge launch over all environments (srbd_batch.hip), and one host
+// wait on one published word.  The single context's fields the batch shares -- configuration, ModelConst, stream,
+// publish word, sequence number, error text -- live in `c`, so fill_input and wait_published serve both.
+struct srbd_batch {
+    srbd_ctx c;
+    int E = 0;
+    StepInput* h_in = nullptr;       // E, mapped pinned staging
+    StepInput* d_in_host = nullptr;  // its device alias
+    StepInput* d_in = nullptr;       // E
+    StepOutput* h_out = nullptr;     // E, mapped pinned: the merge blocks write them
+    StepOutput* d_out_host = nullptr;
+    float* d_noise = nullptr;        // E x P x ldn
+    float* d_costs = nullptr;        // E x ldn
+    float* d_rec = nullptr;          // E x nleaf leaf records
+    uint32_t* d_eflag = nullptr;     // E (merge_body's own publish word per block)
+    uint32_t* d_count = nullptr;     // the merge blocks' arrival count, zero between steps
+    float* d_noise_rm = nullptr;     // injected noise as given (row-major), E x N x P
+    bool stepped = false;
+};
+
+extern "C" void srbd_batch_destroy(srbd_batch* b) {
+    if (!b) return;
+    (void)hipSetDevice(b->c.cfg.device_id);
+    if (b->c.stream) (void)hipStreamSynchronize(b->c.stream);
+    (void)hipFree(b->d_in);
+    (void)hipFree(b->d_noise);
+    (void)hipFree(b->d_costs);
+    (void)hipFree(b->d_rec);
+    (void)hipFree(b->d_eflag);
+    (void)hipFree(b->d_count);
+    (void)hipFree(b->d_noise_rm);
+    if (b->h_in) (void)hipHostFree(b->h_in);
+    if (b->h_out) (void)hipHostFree(b->h_out);
+    if (b->c.h_flag) (void)hipHostFree(b->c.h_flag);
+    if (b->c.stream) (void)hipStreamDestroy(b->c.stream);
+    delete b;
+}
+
+extern "C" const char* srbd_batch_last_error(const srbd_batch* b) {
+    return b ? b->c.err.c_str() : g_last_error.c_str();
+}
+
+extern "C" int srbd_batch_num_envs(const srbd_batch* b) { return b ? b->E : SRBD_E_INVALID; }
+
+extern "C" int srbd_batch_create(const srbd_config* cfg, int32_t num_envs, srbd_batch** out) {
+    if (!cfg || !out) return fail(nullptr, SRBD_E_INVALID, "null argument");
+    *out = nullptr;
+    if (num_envs < 1 || num_envs > BATCH_MAX_ENVS)
+        return fail(nullptr, SRBD_E_INVALID, "num_envs must be in [1, " + std::to_string(BATCH_MAX_ENVS) + "]");
+    if (cfg->num_samples > BATCH_MAX_SAMPLES)
+        return fail(nullptr, SRBD_E_INVALID,
+                    "num_samples per environment must be <= " + std::to_string(BATCH_MAX_SAMPLES) +
+                        " (256 leaves, what one merge block folds): beyond that one environment fills the GPU, use "
+                        "separate contexts");
+    if (cfg->method == SRBD_CEM_MPPI)
+        return fail(nullptr, SRBD_E_INVALID,
+                    "CEM-MPPI has no batch form: its draws depend on each step's sigma and its merge is the "
+                    "column-split hand-off of one context");
+    if ((cfg->world_size > 1) || cfg->rank != 0)
+        return fail(nullptr, SRBD_E_INVALID, "a batch is unsharded: rank / world_size must be 0 / 1");
+    ModelConst mc;
+    std::string why;
+    int rc = build_model(cfg, &mc, &why);
+    if (rc) return fail(nullptr, rc, why);
+    if ((long long)mc.P * mc.ldn * 4 >= (1LL << 31))  // the rollout's per-environment buffer descriptor
+        return fail(nullptr, SRBD_E_INVALID, "noise matrix of one environment exceeds 2^31 bytes");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return fail(nullptr, SRBD_E_NODEVICE, "no HIP device visible (this library has no CPU fallback)");
+    if (cfg->device_id < 0 || cfg->device_id >= ndev) return fail(nullptr, SRBD_E_NODEVICE, "bad device_id");
+    srbd_batch* b = new srbd_batch();
+    b->c.cfg = *cfg;
+    b->c.cfg.world_size = 1;
+    b->c.mc = mc;
+    b->c.nleaf = mc.nleaf;
+    b->c.wrec_stride = rec_floats_wave(mc.P, mc.K);
+    b->E = num_envs;
+    const size_t E = (size_t)num_envs;
+    auto cleanup_fail = [&](const char* what, hipError_t e) {
+        std::string m = std::string(what) + ": " + hipGetErrorString(e);
+        srbd_batch_destroy(b);
+        return fail(nullptr, e == hipErrorOutOfMemory ? SRBD_E_NOMEM : SRBD_E_HIP, m);
+    };
+    hipError_t e;
+    if ((e = hipSetDevice(cfg->device_id)) != hipSuccess) return cleanup_fail("hipSetDevice", e);
+    if ((e = hipStreamCreateWithFlags(&b->c.stream, hipStreamNonBlocking)) != hipSuccess)
+        return cleanup_fail("hipStreamCreate", e);
+    batch_prepare();
+    if ((e = hipHostMalloc((void**)&b->h_in, sizeof(StepInput) * E, hipHostMallocMapped)) != hipSuccess)
+        return cleanup_fail("hipHostMalloc", e);
+    if ((e = hipHostGetDevicePointer((void**)&b->d_in_host, b->h_in, 0)) != hipSuccess)
+        return cleanup_fail("hipHostGetDevicePointer", e);
+    if ((e = hipHostMalloc((void**)&b->h_out, sizeof(StepOutput) * E, hipHostMallocMapped | hipHostMallocCoherent)) !=
+        hipSuccess)
+        return cleanup_fail("hipHostMalloc", e);
+    if ((e = hipHostGetDevicePointer((void**)&b->d_out_host, b->h_out, 0)) != hipSuccess)
+        return cleanup_fail("hipHostGetDevicePointer", e);
+    if ((e = hipHostMalloc((void**)&b->c.h_flag, sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent)) !=
+        hipSuccess)
+        return cleanup_fail("hipHostMalloc", e);
+    if ((e = hipHostGetDevicePointer((void**)&b->c.d_flag, b->c.h_flag, 0)) != hipSuccess)
+        return cleanup_fail("hipHostGetDevicePointer", e);
+    __atomic_store_n(b->c.h_flag, 0u, __ATOMIC_RELEASE);
+    memset(b->h_in, 0, sizeof(StepInput) * E);
+    memset(b->h_out, 0, sizeof(StepOutput) * E);
+    // sizes in 64 bits: E x P x ldn floats passes 2^32 bytes long before the limits
+    const size_t noise_bytes = sizeof(float) * E * (size_t)mc.P * (size_t)mc.ldn;
+    const size_t rec_bytes = sizeof(float) * E * (size_t)mc.nleaf * (size_t)b->c.wrec_stride;
+    if ((e = hipMalloc((void**)&b->d_in, sizeof(StepInput) * E)) != hipSuccess) return cleanup_fail("hipMalloc", e);
+    if ((e = hipMalloc((void**)&b->d_noise, noise_bytes)) != hipSuccess) return cleanup_fail("hipMalloc", e);
+    if ((e = hipMalloc((void**)&b->d_costs, sizeof(float) * E * (size_t)mc.ldn)) != hipSuccess)
+        return cleanup_fail("hipMalloc", e);
+    if ((e = hipMalloc((void**)&b->d_rec, rec_bytes)) != hipSuccess) return cleanup_fail("hipMalloc", e);
+    if ((e = hipMalloc((void**)&b->d_eflag, sizeof(uint32_t) * E)) != hipSuccess) return cleanup_fail("hipMalloc", e);
+    if ((e = hipMalloc((void**)&b->d_count, sizeof(uint32_t))) != hipSuccess) return cleanup_fail("hipMalloc", e);
+    // the noise padding rows (n_local .. ldn) stay zero, as in a single context
+    if ((e = hipMemsetAsync(b->d_noise, 0, noise_bytes, b->c.stream)) != hipSuccess ||
+        (e = hipMemsetAsync(b->d_in, 0, sizeof(StepInput) * E, b->c.stream)) != hipSuccess ||
+        (e = hipMemsetAsync(b->d_costs, 0, sizeof(float) * E * (size_t)mc.ldn, b->c.stream)) != hipSuccess ||
+        (e = hipMemsetAsync(b->d_eflag, 0, sizeof(uint32_t) * E, b->c.stream)) != hipSuccess ||
+        (e = hipMemsetAsync(b->d_count, 0, sizeof(uint32_t), b->c.stream)) != hipSuccess)
+        return cleanup_fail("hipMemset", e);
+    if ((e = hipStreamSynchronize(b->c.stream)) != hipSuccess) return cleanup_fail("hipStreamSynchronize", e);
+    *out = b;
+    return SRBD_OK;
+}
+
+extern "C" int srbd_batch_set_rng(srbd_batch* b, int32_t kind) {
+    if (!b) return SRBD_E_INVALID;
+    if (kind != SRBD_RNG_PHILOX && kind != SRBD_RNG_JAX && kind != SRBD_RNG_JAX_LEGACY)
+        return fail(&b->c, SRBD_E_INVALID, "unknown RNG kind");
+    b->c.mc.rng = kind;  // (N - 1) P < 2^32 holds for every batch shape; no draws are made ahead
+    return SRBD_OK;
+}
+
+extern "C" int srbd_batch_copy_costs(srbd_batch* b, float* out_costs) {
+    if (!b || !out_costs) return SRBD_E_INVALID;
+    if (!b->stepped) return fail(&b->c, SRBD_E_STATE, "no step yet");
+    srbd_ctx* c = &b->c;
+    const ModelConst& mc = c->mc;
+    HIP_TRY(c, hipSetDevice(c->cfg.device_id));
+    HIP_TRY(c, hipMemcpy2DAsync(out_costs, sizeof(float) * mc.n_local, b->d_costs, sizeof(float) * mc.ldn,
+                                sizeof(float) * mc.n_local, b->E, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SRBD_OK;
+}
+
+extern "C" int srbd_batch_step(srbd_batch* b, const float* states, const float* refs, const float* contacts,
+                               int32_t contact_stride, float* best_params, const float* noise, const uint64_t* seeds,
+                               const uint64_t* counters, srbd_result* out, float* out_costs) {
+    if (!b) return SRBD_E_INVALID;
+    srbd_ctx* c = &b->c;
+    const ModelConst& mc = c->mc;
+    if (!states || !refs || !contacts || !best_params || !seeds || !counters || !out || contact_stride < mc.H)
+        return fail(c, SRBD_E_INVALID, "invalid step arguments");
+    HIP_TRY(c, hipSetDevice(c->cfg.device_id));
+    const int E = b->E, P = mc.P;
+    for (int e = 0; e < E; ++e) {
+        StepInput* in = b->h_in + e;
+        const int rc = fill_input(&c->cfg, mc, in, states + 24 * (size_t)e, refs + 24 * (size_t)e,
+                                  contacts + (size_t)e * 4 * contact_stride, contact_stride,
+                                  best_params + (size_t)e * P, nullptr, seeds[e], counters[e]);
+        if (rc) return fail(c, rc, "invalid step arguments");
+        in->noise_scaled = noise ? 1 : 0;
+    }
+    launch_batch_copy(b->d_in_host, b->d_in, E, offsetof(StepInput, best) + sizeof(float) * (size_t)P, c->stream);
+    if (noise) {
+        const size_t bytes = sizeof(float) * (size_t)E * mc.n_local * P;
+        if (!b->d_noise_rm) {
+            const hipError_t e = hipMalloc((void**)&b->d_noise_rm, bytes);
+            if (e != hipSuccess) {
+                b->d_noise_rm = nullptr;
+                (void)hipStreamSynchronize(c->stream);
+                return fail(c, e == hipErrorOutOfMemory ? SRBD_E_NOMEM : SRBD_E_HIP,
+                            std::string("hipMalloc: ") + hipGetErrorString(e));
+            }
+        }
+        HIP_TRY(c, hipMemcpyAsync(b->d_noise_rm, noise, bytes, hipMemcpyHostToDevice, c->stream));
+        launch_batch_transpose(mc, b->d_noise_rm, b->d_noise, E, c->stream);
+    } else {
+        launch_batch_rng(mc, b->d_in, b->d_noise, E, c->stream);
+    }
+    launch_batch_rollout(mc, b->d_in, b->d_noise, b->d_costs, b->d_rec, c->wrec_stride, E, c->stream);
+    const uint32_t seq = ++c->seq;
+    launch_batch_merge(mc, b->d_in, b->d_rec, c->wrec_stride, b->d_noise, b->d_out_host, b->d_eflag, b->d_count,
+                       c->d_flag, seq, E, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    int rc = wait_published(c, seq);
+    if (rc) {  // the stream has drained (or failed): a launch that stopped part-way may have left arrivals counted
+        (void)hipStreamSynchronize(c->stream);
+        (void)hipMemset(b->d_count, 0, sizeof(uint32_t));
+        return rc;
+    }
+    b->stepped = true;
+    if (out_costs && (rc = srbd_batch_copy_costs(b, out_costs))) return rc;
+    for (int e = 0; e < E; ++e) {
+        const StepOutput& o = b->h_out[e];
+        memcpy(best_params + (size_t)e * P, o.best, sizeof(float) * P);
+        memcpy(out[e].grf, o.grf, sizeof(out[e].grf));
+        memcpy(out[e].predicted_state, o.pred, sizeof(out[e].predicted_state));
+        out[e].best_cost = o.best_cost;
+        out[e].best_index = o.best_index;
+        out[e].best_freq = o.best_freq;
+        out[e].status = o.status;
+    }
+    return SRBD_OK;
+}

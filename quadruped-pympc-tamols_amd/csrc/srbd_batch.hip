@@ -1,0 +1,326 @@
+// srbd_batch.hip -- batched environments: E independent MPC problems of one configuration stepped by one set of
+// launches (srbd_batch_step, include/srbd_mpc.h).  Environment e lies on blockIdx.y of every launch and owns in[e], the
+// noise matrix at e P ldn, its costs row and its nleaf leaf records; within an environment every float operation is
+// the single context's, in its order (the shared device code of srbd_core.h, srbd_device.h, srbd_quad.h and
+// srbd_merge.h), and the reduction tree is keyed by the environment's own rows, so environment e's outputs are
+// srbd_step's bit for bit.
+//   batch_copy_kernel       the E step inputs, host-mapped staging -> device
+//   batch_rng_kernel        rng_items per environment, keyed by in[e]'s seed and counter
+//   batch_transpose_kernel  injected noise (row-major) -> SoA per environment
+//   batch_rollout_kernel    rollout_quad_kernel's plain form (MPPI / random sampling, no cost terms): one 64-sample
+//                           leaf per 256-thread block, leaf records only (no in-launch fold, merge or draws: with
+//                           E x nleaf blocks in flight the tail those forms shorten is amortised)
+//   batch_merge_kernel      one block per environment: merge_body over its leaf records -> out[e]; the last block to
+//                           finish publishes the step's sequence word
+#include <algorithm>
+
+#include "srbd_device.h"
+#include "srbd_merge.h"
+#include "srbd_quad.h"
+
+namespace srbd {
+
+__global__ void __launch_bounds__(256) batch_copy_kernel(const uint4* __restrict__ src, uint4* __restrict__ dst,
+                                                         int nwords, int stride_words) {
+    const size_t o = (size_t)blockIdx.x * stride_words;
+    for (int i = threadIdx.x; i < nwords; i += 256) dst[o + i] = src[o + i];
+}
+
+__global__ void __launch_bounds__(256) batch_rng_kernel(const ModelConst mc, const StepInput* __restrict__ in,
+                                                        float* __restrict__ noise) {
+    const int e = blockIdx.y;
+    const RngJob job{noise + (size_t)e * mc.P * mc.ldn, 0, 0, 1, 0, nullptr};  // keyed by in[e] (dev_ctr)
+    rng_items(mc, in + e, job, blockIdx.x * 256 + threadIdx.x, gridDim.x * 256);
+}
+
+// transpose_kernel (srbd_kernels.hip) per environment: row-major (n x P) -> SoA [P][ldn]
+__global__ void __launch_bounds__(256) batch_transpose_kernel(const float* __restrict__ src, int n, int P, int ldn,
+                                                              float* __restrict__ dst) {
+    __shared__ float tile[32][33];
+    src += (size_t)blockIdx.z * n * P;
+    dst += (size_t)blockIdx.z * P * ldn;
+    const int bx = blockIdx.x * 32, by = blockIdx.y * 32;  // bx: rows (samples), by: params
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
+    for (int i = ty; i < 32; i += 8) {
+        const int row = bx + i, col = by + tx;
+        tile[i][tx] = (row < n && col < P) ? src[(size_t)row * P + col] : 0.0f;
+    }
+    __syncthreads();
+    for (int i = ty; i < 32; i += 8) {
+        const int col = by + i, row = bx + tx;
+        if (col < P && row < n) dst[(size_t)col * ldn + row] = tile[tx][i];
+    }
+}
+
+// rollout_quad_kernel<KIND, HT, ST, CEMT = false, EXT = false> (srbd_kernels.hip) with the environment on
+// blockIdx.y: the leg-parallel force phase, the component-parallel rigid-body step, the tracking cost and the leaf
+// record, statement for statement, so the costs and records are that kernel's bits.  Left out: the step input by
+// value, the in-launch draws, folds and merges, CEM's sigma scaling and the opt-in cost terms (refused at create).
+template <int KIND, int HT, int ST>
+__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) batch_rollout_kernel(
+    const ModelConst mc, const StepInput* __restrict__ in_arr, const float* __restrict__ noise_arr,
+    float* __restrict__ costs_arr, float* __restrict__ recs_arr, int rec_stride) {
+    const int env = blockIdx.y;
+    const StepInput* __restrict__ in = in_arr + env;
+    const float* __restrict__ noise = noise_arr + (size_t)env * mc.P * mc.ldn;
+    float* __restrict__ costs = costs_arr + (size_t)env * mc.ldn;
+    float* __restrict__ recs = recs_arr + (size_t)env * mc.nleaf * rec_stride;
+    const int nroll = gridDim.x;
+
+    constexpr bool CT = HT > 0 && (KIND == SRBD_ZERO_ORDER || ST > 0);
+    const int SPB = 64;  // one leaf per block
+    const int H = CT ? HT : mc.H;
+    const int S = CT ? ST : mc.S;
+    const int PL = CT ? (KIND == SRBD_ZERO_ORDER ? 3 * HT : (KIND == SRBD_LINEAR_SPLINE ? 3 * (ST + 1) : 12 * ST))
+                      : mc.PL;
+    // ZST (zero-order, compile-time horizon H <= 12): the noise a lane reads stays raw in its registers and goes to
+    // LDS after the horizon, where the leaf sums read it (38.5 KB per block: four blocks per CU)
+    constexpr bool ZST = CT && KIND == SRBD_ZERO_ORDER && HT <= 12;
+    constexpr int PCT = ZST ? 12 * HT : 1;
+    constexpr int ZSTR = PCT + 1;
+    __shared__ __attribute__((aligned(16))) float zst[ZST ? 64 * ZSTR : 1];
+    __shared__ float bls[ZST ? PCT : 1];
+    const int tid = threadIdx.x;
+    const int q4 = tid & 3;
+    const int c = q4 < 3 ? q4 : 2;
+    const int sib = tid >> 2;
+    const int k = blockIdx.x * SPB + sib;
+    const bool valid = k < mc.n_local;
+    const size_t ldn = (size_t)mc.ldn;
+    const float* __restrict__ nz = noise + k;
+    const float* __restrict__ best = in->best;
+
+    // lane constants
+    const QuadLane L = quad_lane(mc, c);
+    const float Qp = sel3(c, mc.Q[0], mc.Q[1], mc.Q[2]), Qv = sel3(c, mc.Q[3], mc.Q[4], mc.Q[5]);
+    const float Qr = sel3(c, mc.Q[6], mc.Q[7], mc.Q[8]), Qw = sel3(c, mc.Q[9], mc.Q[10], mc.Q[11]);
+    const float* st = in->state;
+    const float* rf = in->ref;
+    const float rp = sel3(c, rf[0], rf[1], rf[2]), rv = sel3(c, rf[3], rf[4], rf[5]);
+    const float rr = sel3(c, rf[6], rf[7], rf[8]), rw = sel3(c, rf[9], rf[10], rf[11]);
+    float p = sel3(c, st[0], st[1], st[2]), v = sel3(c, st[3], st[4], st[5]);
+    float r = sel3(c, st[6], st[7], st[8]), w = sel3(c, st[9], st[10], st[11]);
+    float cost = 0.0f;
+    const int lq = q4;  // this lane's leg in the force phase
+    uint32_t lmask[4];
+#pragma unroll
+    for (int l = 0; l < 4; ++l) lmask[l] = lq == l ? ~0u : 0u;
+    float footL[3];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) footL[q] = st[12 + 3 * lq + q];
+    constexpr int NCL = ZST ? HT : 1;
+    float clreg[NCL];
+    if constexpr (ZST) {
+#pragma unroll
+        for (int n = 0; n < HT; ++n) clreg[n] = in->contact[lq][n];
+    }
+
+    // specialised shapes: every parameter this lane reads over the horizon is loaded before the first step
+    constexpr int NPRE = !CT ? 1 : (KIND == SRBD_ZERO_ORDER ? HT : (KIND == SRBD_LINEAR_SPLINE ? ST + 1 : 4 * ST));
+    float pre[3][NPRE];  // pre[q][i] = component q's slot i of this lane's leg
+    // noise through a buffer descriptor over this environment's matrix alone (P ldn 4 < 2^31, checked at create):
+    // a lane's offset can never reach another environment's rows
+    const int cblk = lq * PL;
+    const auto nrs = __builtin_amdgcn_make_buffer_rsrc((void*)noise, (short)0, mc.P * mc.ldn * 4, 0x00020000);
+    const int voff = (cblk * mc.ldn + k) * 4;
+    const float* __restrict__ bl = best + cblk;
+    if constexpr (ZST) {
+        for (int j = tid; j < PCT; j += 256) bls[j] = best[j];
+    }
+    auto load_slot = [&](const int i) __attribute__((always_inline)) {
+#pragma unroll
+        for (int l = 0; l < 3; ++l) {
+            const int jr = KIND == SRBD_ZERO_ORDER ? l * HT + i
+                           : (KIND == SRBD_LINEAR_SPLINE ? l * (ST + 1) + i : 10 * (i >> 2) + 4 * l + (i & 3));
+            const float nzv = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(nrs, voff, jr * mc.ldn * 4, 0));
+            if constexpr (ZST)
+                pre[l][i] = nzv;  // raw: best is added at use, the value staged for the epilogue
+            else
+                pre[l][i] = bl[jr] + nzv;
+        }
+    };
+    if constexpr (CT) {
+#pragma unroll
+        for (int i = 0; i < NPRE; ++i) load_slot(i);
+    }
+    if constexpr (ZST) {  // the LDS copy of best is complete (the noise loads stay in flight)
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+    }
+
+    float dep = p;  // step_ptr dependency: set part-way through each step
+    auto step = [&](const int n) __attribute__((always_inline)) {
+        const auto is = step_ptr(in, dep);
+        float cl[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if constexpr (!ZST)
+#pragma unroll
+            for (int l = 0; l < 4; ++l) cl[l] = is->contact[l][n];
+        const float fref = is->fzref[n];
+        const float dt = mc.dts[n];
+        const float sq = mc.sq[n], somq = mc.somq[n], sa = mc.sa[n], sb = mc.sb[n], scc = mc.sc[n], sd = mc.sd[n];
+        const int idx = CT && KIND != SRBD_ZERO_ORDER ? chunk_index(n, HT, ST) : mc.sidx[n];
+        const float clq = ZST ? clreg[ZST ? n : 0]
+                              : __uint_as_float((__float_as_uint(cl[0]) & lmask[0]) | (__float_as_uint(cl[1]) & lmask[1]) |
+                                                (__float_as_uint(cl[2]) & lmask[2]) | (__float_as_uint(cl[3]) & lmask[3]));
+        const int lbase = lq * PL;
+        // component q of this leg's decoded force (slot i, parameter j of the leg when not prefetched)
+        auto PQ = [&](int q, int i, int j) {
+            if constexpr (ZST) {
+                return bls[lbase + j] + pre[q][i];
+            } else if constexpr (CT) {
+                return pre[q][i];
+            } else {
+                const float z = nz[(size_t)(lbase + j) * ldn];
+                return best[lbase + j] + z;
+            }
+        };
+        float rq[3];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            if (KIND == SRBD_ZERO_ORDER) {
+                rq[q] = PQ(q, n, n + q * H);
+            } else if (KIND == SRBD_LINEAR_SPLINE) {
+                const int o = idx + q * (S + 1);
+                rq[q] = somq * PQ(q, idx, o) + sq * PQ(q, idx + 1, o + 1);
+            } else {
+                const int o = 10 * idx + 4 * q;
+                const float p0 = PQ(q, 4 * idx, o), p1 = PQ(q, 4 * idx + 1, o + 1), p2 = PQ(q, 4 * idx + 2, o + 2),
+                            p3 = PQ(q, 4 * idx + 3, o + 3);
+                const float phi = 0.5f * ((p2 - p1) + (p1 - p0));
+                const float phin = 0.5f * ((p3 - p2) + (p2 - p1));
+                rq[q] = sa * p1 + sb * phi + scc * p2 + sd * phin;
+            }
+        }
+        // shape_leg / clip_leg (srbd_core.h), this lane's leg
+        const float fz = clamp_cs((fref + rq[2]) * clq, mc.grf_min, mc.grf_max);
+        const float lo = mc.neg_mu * fz, hi = mc.mu * fz;
+        const float fx = clamp_cs(third(rq[0] * clq), lo, hi), fy = clamp_cs(third(rq[1] * clq), lo, hi);
+        // integrate(): skew_dot(p_foot - p, f) * c (the position's components from their lanes)
+        const float vx = footL[0] - qp<QP_B0>(p), vy = footL[1] - qp<QP_B1>(p), vz = footL[2] - qp<QP_B2>(p);
+        float sm[6] = {fx * clq, fy * clq, fz * clq, ((-vz) * fy + vy * fz) * clq, (vz * fx + (-vx) * fz) * clq,
+                       ((-vy) * fx + vx * fy) * clq};
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {  // quad butterfly: (l0 + l1) + (l2 + l3) on every lane (adds commute)
+            sm[i] = sm[i] + qp<QP_XOR1>(sm[i]);
+            sm[i] = sm[i] + qp<QP_XOR2>(sm[i]);
+        }
+        const float temp = sel3(c, sm[0], sm[1], sm[2]);
+        dep = sm[5];  // the next step's scalar loads issue from here on (step_ptr)
+        quad_rb_apply3(mc, L, quad_rb_prep(L, r, w), temp, sm[3], sm[4], sm[5], dt, p, v, r, w);
+        // tracking cost (NMPC:451), accumulated per component lane
+        const float ep = p - rp, ev = v - rv, er_ = r - rr, ew = w - rw;
+        const float tp = (ep * Qp) * ep, tv = (ev * Qv) * ev, tr = (er_ * Qr) * er_, tw = (ew * Qw) * ew;
+        cost = cost + (((tp + tv) + tr) + tw);
+    };
+    if constexpr (CT) {
+        unroll_seq([&](auto nc) { step(decltype(nc)::value); }, std::make_integer_sequence<int, (CT ? HT : 1)>{});
+    } else {
+        for (int n = 0; n < H; ++n) step(n);
+    }
+    cost = (qp<QP_B0>(cost) + qp<QP_B1>(cost)) + qp<QP_B2>(cost);
+    cost = cost + in->cost_feet;  // 0, or NaN when a foot term is non-finite (Q_feet = 0)
+    if (isnan(cost) || isinf(cost)) cost = 1000000.0f;
+    if (valid && q4 == 0) costs[k] = cost;
+    if constexpr (ZST) {  // the block's noise, sample-major (leg lq's block of columns lq PL .. lq PL + PL - 1)
+#pragma unroll
+        for (int q = 0; q < 3; ++q)
+#pragma unroll
+            for (int i = 0; i < NPRE; ++i) zst[sib * ZSTR + lq * PL + q * HT + i] = pre[q][i];
+    }
+    const GroupArgs grp{nullptr, nullptr, 1, nullptr};  // gsize 1: leaf records only
+    block_epilogue<false, ZST>(mc, in, SPB, q4 == 0 ? sib : -1, valid, cost, noise, recs, rec_stride, 0.0f, grp, nroll,
+                               ZST ? zst : nullptr, ZSTR);
+}
+
+// One block per environment (blockIdx.y; blockIdx.x == 0, as merge_body's unsplit form expects): the environment's
+// leaf records folded to the root and out[e] written, exactly as merge_kernel does for one problem.  merge_body ends
+// with every wave's output stores complete, a system release by thread 0 (fence_sys) and its own publish word
+// (eflag[e], device memory, unread).  Then thread 0 counts its block; the last arriver resets the counter for the
+// next launch and stores `seq` into the host's word -- after every block's outputs, so one word publishes them all.
+template <int NT, bool STAGE>
+__global__ void __launch_bounds__(NT) batch_merge_kernel(const ModelConst mc, StepInput* __restrict__ in,
+                                                         const float* __restrict__ recs, int rec_stride,
+                                                         const float* __restrict__ noise,
+                                                         StepOutput* __restrict__ out, uint32_t* __restrict__ eflag,
+                                                         uint32_t* __restrict__ count, uint32_t* __restrict__ flag,
+                                                         uint32_t seq) {
+    const int e = blockIdx.y;
+    __shared__ MergeShared<NT> sh;
+    extern __shared__ __attribute__((aligned(16))) float dsm[];
+    merge_body<NT, STAGE>(mc, in + e, recs + (size_t)e * mc.nleaf * rec_stride, mc.nleaf, rec_stride, 0,
+                          noise + (size_t)e * mc.P * mc.ldn, nullptr, out + e, 0, 0, nullptr, eflag + e, seq, 0, 1, sh,
+                          dsm);
+    if (threadIdx.x == 0) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const uint32_t old = __hip_atomic_fetch_add(count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (old == gridDim.y - 1) {
+            __hip_atomic_store(count, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(flag, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+}
+
+// ------------------------------------------------------------------ launchers
+void batch_prepare() {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&batch_merge_kernel<MERGE_STAGE_THREADS, true>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)MERGE_LDS_DYN_MAX);
+}
+
+void launch_batch_copy(const StepInput* in_host, StepInput* in, int E, size_t bytes, hipStream_t s) {
+    hipLaunchKernelGGL(batch_copy_kernel, dim3(E), dim3(256), 0, s, (const uint4*)in_host, (uint4*)in,
+                       (int)(bytes / 16), (int)(sizeof(StepInput) / 16));
+}
+
+void launch_batch_rng(const ModelConst& mc, const StepInput* in, float* noise, int E, hipStream_t s) {
+    // the draws do not depend on the grid (rng_items strides over the items): about 32 768 blocks in all
+    const int gx = std::max(1, std::min(rng_grid(mc), 32768 / E));
+    hipLaunchKernelGGL(batch_rng_kernel, dim3(gx, E), dim3(256), 0, s, mc, in, noise);
+}
+
+void launch_batch_transpose(const ModelConst& mc, const float* src, float* noise, int E, hipStream_t s) {
+    const dim3 grid((mc.n_local + 31) / 32, (mc.P + 31) / 32, E);
+    hipLaunchKernelGGL(batch_transpose_kernel, grid, dim3(256), 0, s, src, mc.n_local, mc.P, mc.ldn, noise);
+}
+
+void launch_batch_rollout(const ModelConst& mc, const StepInput* in, const float* noise, float* costs, float* recs,
+                          int rec_stride, int E, hipStream_t s) {
+    const dim3 grid(mc.nleaf, E);
+    const int H = mc.H, S = mc.S;
+#define SRBD_BR(K, HH, SS)                                                                                       \
+    {                                                                                                            \
+        hipLaunchKernelGGL((batch_rollout_kernel<K, HH, SS>), grid, dim3(256), 0, s, mc, in, noise, costs, recs, \
+                           rec_stride);                                                                          \
+        return;                                                                                                  \
+    }
+    switch (mc.kind) {  // launch_rollout's compile-time shapes
+        case SRBD_ZERO_ORDER:
+            if (H == 10) SRBD_BR(SRBD_ZERO_ORDER, 10, 0);
+            if (H == 12) SRBD_BR(SRBD_ZERO_ORDER, 12, 0);
+            if (H == 16) SRBD_BR(SRBD_ZERO_ORDER, 16, 0);
+            SRBD_BR(SRBD_ZERO_ORDER, 0, 0);
+        case SRBD_LINEAR_SPLINE:
+            if (S == 2 && H == 12) SRBD_BR(SRBD_LINEAR_SPLINE, 12, 2);
+            if (S == 2 && H == 16) SRBD_BR(SRBD_LINEAR_SPLINE, 16, 2);
+            SRBD_BR(SRBD_LINEAR_SPLINE, 0, 0);
+        default:
+            if (S == 2 && H == 12) SRBD_BR(SRBD_CUBIC_SPLINE, 12, 2);
+            if (S == 2 && H == 16) SRBD_BR(SRBD_CUBIC_SPLINE, 16, 2);
+            SRBD_BR(SRBD_CUBIC_SPLINE, 0, 0);
+    }
+#undef SRBD_BR
+}
+
+void launch_batch_merge(const ModelConst& mc, StepInput* in, const float* recs, int rec_stride, const float* noise,
+                        StepOutput* out, uint32_t* eflag, uint32_t* count, uint32_t* flag, uint32_t seq, int E,
+                        hipStream_t s) {
+    size_t smem = 0;
+    const dim3 grid(1, E);
+    if (merge_stage_fits(mc.nleaf, rec_stride, mc.P, mc.K, &smem))
+        hipLaunchKernelGGL((batch_merge_kernel<MERGE_STAGE_THREADS, true>), grid, dim3(MERGE_STAGE_THREADS), smem, s, mc,
+                           in, recs, rec_stride, noise, out, eflag, count, flag, seq);
+    else
+        hipLaunchKernelGGL((batch_merge_kernel<MERGE_THREADS, false>), grid, dim3(MERGE_THREADS), smem, s, mc, in, recs,
+                           rec_stride, noise, out, eflag, count, flag, seq);
+}
+
+}  // namespace srbd

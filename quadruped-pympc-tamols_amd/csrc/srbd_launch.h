@@ -160,8 +160,30 @@ void launch_arm_copy(const uint32_t* go, uint32_t seq, uint64_t deadline_ticks, 
 void launch_div_selftest(const float* a, const float* b, int n, float* o, hipStream_t s);
 void launch_log1p_selftest(const float* t, int n, float* o, hipStream_t s);
 
+// Batched environments (srbd_batch.hip): E independent problems of one ModelConst (world 1, MPPI / random sampling)
+// per launch, environment e on blockIdx.y.  Device arrays: in[E]; noise E x P x ldn (SoA per environment); costs
+// E x ldn; recs E x nleaf leaf records; out[E] and `flag` host-mapped.  Every launch count is independent of E.
+constexpr int BATCH_MAX_ENVS = 4096;
+constexpr int BATCH_MAX_SAMPLES = 16384;  // 256 leaves: what one merge block folds unsplit (MERGE_SPLIT_MIN_RECS)
+void batch_prepare();  // once per batch context: the staged merge's dynamic LDS limit
+// in_host[e] -> in[e], the first `bytes` (a multiple of 16) of every StepInput; one block per environment
+void launch_batch_copy(const StepInput* in_host, StepInput* in, int E, size_t bytes, hipStream_t s);
+// environment e's draws keyed by in[e]'s seed and counter (rng_items)
+void launch_batch_rng(const ModelConst& mc, const StepInput* in, float* noise, int E, hipStream_t s);
+// injected noise, E x n_local x P row-major -> SoA per environment
+void launch_batch_transpose(const ModelConst& mc, const float* src, float* noise, int E, hipStream_t s);
+// four-lane rollouts, one 64-sample leaf per block: costs and leaf records (no in-launch fold)
+void launch_batch_rollout(const ModelConst& mc, const StepInput* in, const float* noise, float* costs, float* recs,
+                          int rec_stride, int E, hipStream_t s);
+// one block per environment folds its leaf records to the root (merge_body) and writes out[e]; the blocks count
+// themselves in *count (zero between launches: the last arriver resets it) and the last one stores `seq` in *flag.
+// eflag: E device words (each block's own publish word inside merge_body)
+void launch_batch_merge(const ModelConst& mc, StepInput* in, const float* recs, int rec_stride, const float* noise,
+                        StepOutput* out, uint32_t* eflag, uint32_t* count, uint32_t* flag, uint32_t seq, int E,
+                        hipStream_t s);
+
 // TAMOLS (tamols_kernel.hip)
-constexpr int TAMOLS_NQ = 19;        // nearest-neighbour queries per candidate
+constexpr int TAMOLS_NQ = 19;       // nearest-neighbour queries per candidate
 constexpr int TAMOLS_MAXCAND = 320;  // rows * cols
 
 struct TamolsArgs {

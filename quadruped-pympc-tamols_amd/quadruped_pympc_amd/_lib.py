@@ -186,6 +186,14 @@ SIGNATURES.update({
     "srbd_time_launch": (_I, [_P, _I, _I, _FP, _IP]),
     "srbd_jax_prng_key": (_I, [C.c_uint64, _P]),
     "srbd_jax_split": (_I, [_P, _I, _I, _P]),
+    # batched environments (BatchContext passes cached addresses, as Context does)
+    "srbd_batch_create": (_I, [C.POINTER(SrbdConfig), _I, C.POINTER(_P)]),
+    "srbd_batch_destroy": (None, [_P]),
+    "srbd_batch_last_error": (C.c_char_p, [_P]),
+    "srbd_batch_num_envs": (_I, [_P]),
+    "srbd_batch_set_rng": (_I, [_P, _I]),
+    "srbd_batch_step": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
+    "srbd_batch_copy_costs": (_I, [_P, _P]),
 })
 
 # srbd_time_launch kinds (include/srbd_mpc.h)
@@ -651,4 +659,85 @@ class Context:
         """srbd_draw_noise: the device draws of a step keyed by (seed, counter), (n_local, P) row-major."""
         out = np.zeros((self.n_local, self.P), np.float32)
         self.check(lib.srbd_draw_noise(self.h, int(seed), int(counter), fptr(out)), "srbd_draw_noise")
+        return out
+
+
+class BatchContext:
+    """Owns one ``srbd_batch``: ``num_envs`` independent problems of one configuration stepped by one call
+    (``srbd_batch_step``, include/srbd_mpc.h).  Environment ``e`` of a step returns what ``Context(cfg).step`` returns
+    for the same inputs, bit for bit.  Inputs are copied into persistent staging arrays, as ``Context`` does."""
+
+    def __init__(self, cfg: SrbdConfig, num_envs: int):
+        self.cfg = cfg
+        self.P = num_params(cfg)
+        self.N = cfg.num_samples
+        self.E = int(num_envs)
+        h = _P()
+        rc = lib.srbd_batch_create(C.byref(cfg), self.E, C.byref(h))
+        if rc != OK:
+            msg = lib.srbd_batch_last_error(None)
+            raise RuntimeError(f"srbd_batch_create failed ({rc}): {msg.decode() if msg else ''}")
+        self.h = h
+        E, H = self.E, cfg.horizon
+        self._states = np.zeros((E, 24), np.float32)
+        self._refs = np.zeros((E, 24), np.float32)
+        self._contacts = np.zeros((E, 4, H), np.float32)
+        self._best = np.zeros((E, self.P), np.float32)
+        self._seeds = np.zeros(E, np.uint64)
+        self._counters = np.zeros(E, np.uint64)
+        self._results = (SrbdResult * E)()
+        self._addr = tuple(a.ctypes.data for a in (self._states, self._refs, self._contacts, self._best, self._seeds,
+                                                   self._counters))
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib.srbd_batch_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def check(self, rc, what):
+        if rc != OK:
+            msg = lib.srbd_batch_last_error(self.h)
+            raise RuntimeError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
+
+    def set_rng(self, kind):
+        """srbd_batch_set_rng: 'philox' (default), 'jax' or 'jax_legacy'; in the JAX modes the seeds are packed keys."""
+        code = RNG_CODES[kind] if isinstance(kind, str) else int(kind)
+        self.check(lib.srbd_batch_set_rng(self.h, code), "srbd_batch_set_rng")
+
+    def step(self, states, refs, contacts, best, noise=None, seeds=None, counters=None, want_costs=False):
+        """One step of every environment: states / refs (E, 24), contacts (E, 4, >=H), best (E, P), noise None or
+        (E, N, P), seeds / counters (E,) -> (best (E, P), list of E SrbdResult, costs (E, N) or None)."""
+        E, H = self.E, self.cfg.horizon
+        self._states[...] = np.reshape(states, (E, 24))
+        self._refs[...] = np.reshape(refs, (E, 24))
+        contacts = np.asarray(contacts)
+        if contacts.ndim != 3 or contacts.shape[:2] != (E, 4) or contacts.shape[2] < H:
+            raise ValueError("contact sequences must be (E, 4, >=H)")
+        self._contacts[...] = contacts[:, :, :H]
+        self._best[...] = np.reshape(best, (E, self.P))
+        self._seeds[...] = 42 if seeds is None else np.asarray(seeds, np.uint64).reshape(E)
+        self._counters[...] = 0 if counters is None else np.asarray(counters, np.uint64).reshape(E)
+        a_noise = None
+        if noise is not None:
+            noise = np.ascontiguousarray(noise, dtype=np.float32)
+            if noise.shape != (E, self.N, self.P):
+                raise ValueError(f"noise must be ({E}, {self.N}, {self.P})")
+            a_noise = noise.ctypes.data
+        costs = np.empty((E, self.N), np.float32) if want_costs else None
+        a = self._addr
+        rc = lib.srbd_batch_step(self.h, a[0], a[1], a[2], H, a[3], a_noise, a[4], a[5], C.addressof(self._results),
+                                 None if costs is None else costs.ctypes.data)
+        self.check(rc, "srbd_batch_step")
+        results = [SrbdResult.from_buffer_copy(r) for r in self._results]
+        return self._best.copy(), results, costs
+
+    def copy_costs(self) -> np.ndarray:
+        out = np.empty((self.E, self.N), np.float32)
+        self.check(lib.srbd_batch_copy_costs(self.h, out.ctypes.data), "srbd_batch_copy_costs")
         return out

@@ -1,0 +1,144 @@
+"""``Sampling_MPC`` over ``num_envs`` environments stepped by one call (``srbd_batch_step``, include/srbd_mpc.h).
+
+The reference runs many simulations as replica processes (simulation/batched_simulations.py:40-58), one controller
+each.  ``Batched_Sampling_MPC`` is the one-process form: one configuration (the same config mirror ``Sampling_MPC``
+reads), and per environment a state, reference, contact sequence, warm start and noise key.  Environment ``e`` of a
+``compute_control`` call returns what a ``Sampling_MPC`` with the same key returns, bit for bit.
+
+MPPI and random sampling; ``sampling_method == 'cem_mppi'`` has no batch form (its draws depend on the sigma each
+step produces) and raises ``NotImplementedError``.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from ... import _lib
+from ...runtime import active_config
+from .centroidal_nmpc_hip import Sampling_MPC
+
+f32 = np.float32
+
+
+class LazyBatchCosts:
+    """Saturated per-sample costs (E, N) of one batch step, fetched from the device on first use."""
+
+    def __init__(self, ctx: "_lib.BatchContext", step_id: int, owner: "Batched_Sampling_MPC"):
+        self._ctx, self._step_id, self._owner, self._data = ctx, step_id, owner, None
+        self.shape = (ctx.E, ctx.N)
+
+    def __array__(self, dtype=None, copy=None):
+        if self._data is None:
+            if self._owner._calls != self._step_id:
+                raise RuntimeError("costs of an older step: materialise them before the next compute call")
+            self._data = self._ctx.copy_costs()
+        return self._data if dtype is None else self._data.astype(dtype)
+
+    def __len__(self):
+        return self.shape[0]
+
+    def __getitem__(self, i):
+        return np.asarray(self)[i]
+
+
+class Batched_Sampling_MPC:
+    """``num_envs`` sampling controllers of one configuration behind one device context."""
+
+    def __init__(self, num_envs: int, config_module=None):
+        cfg = active_config(config_module)
+        if cfg.mpc_params["sampling_method"] == "cem_mppi":
+            raise NotImplementedError("Batched_Sampling_MPC: 'cem_mppi' has no batch form (its draws depend on the "
+                                      "sigma each step produces); use one Sampling_MPC per environment")
+        self.num_envs = int(num_envs)
+        if self.num_envs < 1:
+            raise ValueError("num_envs must be >= 1")
+        # one single-environment controller carries the configuration and the per-environment host helpers
+        # (with_newkey, prepare_state_and_reference); it never creates a device context
+        self._one = Sampling_MPC(config_module)
+        one = self._one
+        self.rng = one.rng
+        self.sampling_method = one.sampling_method
+        self.control_parametrization = one.control_parametrization
+        self.num_sampling_iterations = one.num_sampling_iterations
+        self.num_parallel_computations = one.num_parallel_computations
+        self.horizon = one.horizon
+        self.num_control_parameters = one.num_control_parameters
+        self.num_control_parameters_single_leg = one.num_control_parameters_single_leg
+        self.best_control_parameters = np.zeros((self.num_envs, self.num_control_parameters), dtype=f32)
+        # environment e starts from seed 42 + e: (seed, counter) for Philox, jax.random.PRNGKey(42 + e) otherwise
+        if self.rng == "philox":
+            self.master_keys = np.array([[42 + e, 0] for e in range(self.num_envs)], dtype=np.uint64)
+        else:
+            self.master_keys = np.stack([_lib.jax_prng_key(42 + e) for e in range(self.num_envs)])
+        self._calls = 0
+        self._ctx = None
+        self.jitted_compute_control = self.compute_control
+
+    @property
+    def context(self) -> "_lib.BatchContext":
+        if self._ctx is None:
+            self._ctx = _lib.BatchContext(self._one._srbd_config(), self.num_envs)
+            if self.rng != "philox":
+                self._ctx.set_rng(self.rng)
+        return self._ctx
+
+    def with_newkey(self):
+        """Every environment's key advanced as Sampling_MPC.with_newkey advances its stream's."""
+        one = self._one
+        keys = np.array(self.master_keys)
+        for e in range(self.num_envs):
+            one.master_key = keys[e]
+            keys[e] = one.with_newkey().master_key
+        self.master_keys = keys
+        return self
+
+    def get_key(self):
+        return self.master_keys
+
+    def compute_control(self, states, references, contact_sequences, best_control_parameters, keys, *, noise=None):
+        """The single class's return tuple, stacked on a leading environment axis:
+        (GRFs (E, 12), footholds (E, 12), predicted states (E, 24), best parameters (E, P), best costs (E,),
+        step frequencies (E,), costs (E, N) lazy)."""
+        ctx = self.context
+        E = self.num_envs
+        self._calls += 1
+        if self.rng == "philox":
+            k = np.asarray(keys, dtype=np.uint64).reshape(E, -1)
+            seeds, counters = k[:, 0], (k[:, 1] if k.shape[1] > 1 else np.zeros(E, np.uint64))
+        else:  # the packed JAX keys; the counter only numbers the steps
+            k = np.asarray(keys, dtype=np.uint32).reshape(E, 2)
+            seeds = np.array([_lib.pack_key(k[e]) for e in range(E)], dtype=np.uint64)
+            counters = np.full(E, self._calls, dtype=np.uint64)
+        best, results, _ = ctx.step(states, references, contact_sequences, best_control_parameters, noise=noise,
+                                    seeds=seeds, counters=counters)
+        self.last_results = results
+        grf = np.array([r.grf[:] for r in results], dtype=f32)
+        pred = np.array([r.predicted_state[:] for r in results], dtype=f32)
+        cost = np.array([r.best_cost for r in results], dtype=f32)
+        return (grf, np.zeros((E, 12), dtype=np.int32), pred, best, cost, np.full(E, 1.4),
+                LazyBatchCosts(ctx, self._calls, self))
+
+    def prepare_state_and_reference(self, states_current, reference_states, current_contacts, previous_contacts,
+                                    mpc_frequency=100):
+        """Sampling_MPC.prepare_state_and_reference (srbd_prepare_state) per environment: sequences of E state /
+        reference dicts and contact vectors -> (states (E, 24), references (E, 24)); the warm starts' lift-off
+        legs are zeroed in ``best_control_parameters``."""
+        one = self._one
+        states = np.zeros((self.num_envs, 24))
+        refs = np.zeros((self.num_envs, 24))
+        best = np.array(self.best_control_parameters, dtype=f32)
+        for e in range(self.num_envs):
+            one.best_control_parameters = best[e]
+            states[e], refs[e] = one.prepare_state_and_reference(states_current[e], reference_states[e],
+                                                                 current_contacts[e], previous_contacts[e],
+                                                                 mpc_frequency)
+            best[e] = one.best_control_parameters
+        self.best_control_parameters = best
+        return states, refs
+
+    def reset(self):
+        print("Resetting the controller")
+
+    def close(self):
+        if self._ctx is not None:
+            self._ctx.close()
+            self._ctx = None
