@@ -485,7 +485,8 @@ int srbd_interface_step(srbd_ctx* ctx, srbd_interface_io* io, const float* conta
  *   and both JAX streams; injected noise.
  *   SRBD_E_INVALID (with a message saying which and why): a larger N or num_envs, CEM-MPPI (its draws depend on
  *   the sigma each step produces, and its merge is one context's column-split hand-off), rank / world_size other
- *   than 0 / 1.  use_graph is ignored.  There are no batch forms of gait-adaptive sampling, the opt-in cost terms,
+ *   than 0 / 1.  use_graph is ignored.  Gait-adaptive sampling and the opt-in cost terms have batch forms
+ *   (srbd_batch_set_gait, srbd_batch_set_cost_terms below), but not both at once.  There are no batch forms of CEM,
  *   armed steps or the device-resident chains.  A failed allocation: SRBD_E_NOMEM; no device: SRBD_E_NODEVICE.
  *   A call that returns an error has changed nothing in best_params.  A step whose launches end without publishing
  *   returns SRBD_E_HIP, leaves the arrival count zero and the next step exact. */
@@ -509,6 +510,28 @@ int srbd_batch_step(srbd_batch* b, const float* states, const float* refs, const
                     const uint64_t* counters, srbd_result* out, float* out_costs);
 /* E x N saturated costs of the last step. */
 int srbd_batch_copy_costs(srbd_batch* b, float* out_costs);
+/* Gait-adaptive sampling and the opt-in cost terms in a batch: srbd_set_gait, srbd_clear_gait and srbd_set_cost_terms
+ * with every per-step value per environment and every configuration value shared.  A setting applies to every
+ * following srbd_batch_step until changed.
+ *   timings       : E x 4 leg phases
+ *   freq_sets     : E x n_freq candidate step frequencies (random sampling's set depends on each environment's
+ *                   optimize_swing); n_freq, pgg_dt and duty_factor are shared
+ *   freq_rows     : NULL -> every sample draws its frequency on the device from its environment's set, keyed by
+ *                   (seeds[e], counters[e]) as srbd_step keys it; else E x N injected frequencies
+ *   r_force, w_smooth, w_cone : shared; all zero turns the terms off (the plain kernel again)
+ *   Equivalence: environment e returns exactly what srbd_step returns on a context that received
+ *   srbd_set_gait(timing_e, pgg_dt, duty_factor, freq_set_e, n_freq, freq_rows_e), or srbd_set_cost_terms(r_force,
+ *   w_smooth, w_cone), for the same inputs -- every output bit for bit, srbd_result::best_freq included (the best
+ *   row's frequency; 0 after srbd_batch_clear_gait).
+ *   SRBD_E_INVALID (with a message): null arguments, n_freq outside 1..SRBD_MAX_FREQS, num_splines + 1 > 33 for
+ *   the spline parametrizations, weights negative or not finite, and gait-adaptive sampling together with non-zero
+ *   weights (one context runs that combination on its thread-per-sample kernel; it has no batch form): whichever
+ *   call would make both active fails and changes nothing.  A failed allocation of the frequency array:
+ *   SRBD_E_NOMEM. */
+int srbd_batch_set_gait(srbd_batch* b, const float* timings, float pgg_dt, float duty_factor, const float* freq_sets,
+                        int32_t n_freq, const float* freq_rows);
+int srbd_batch_clear_gait(srbd_batch* b);
+int srbd_batch_set_cost_terms(srbd_batch* b, const float r_force[3], float w_smooth, float w_cone);
 
 /* Diagnostic: enable != 0 stamps the phases of the following TAMOLS calls; out_us[5] (may be NULL)
  * receives the last call's mean per-block durations of (patch, queries, scores, slice argmin + count)

@@ -1130,6 +1130,24 @@ static void drop_graphs(srbd_ctx* c) {
     xg_drop_graphs(c);
 }
 
+// The gait fields of one StepInput (srbd_set_gait, srbd_batch_set_gait); fill_input leaves them as they are.
+static void fill_gait(const ModelConst& mc, StepInput* in, const float* timing, float pgg_dt, float duty_factor,
+                      const float* freq_set, int n_freq, bool explicit_rows) {
+    for (int l = 0; l < 4; ++l) in->ga_timing[l] = timing[l];
+    in->ga_dt = pgg_dt;
+    in->ga_duty = duty_factor;
+    in->ga_nfreq = n_freq;
+    for (int i = 0; i < SRBD_MAX_FREQS; ++i) in->ga_freqs[i] = i < n_freq ? freq_set[i] : 0.0f;
+    // chunk boundaries float32(linspace(0, H, S+1)) as spline_coef forms them; integer steps compare
+    // >= a boundary exactly when they are >= its ceiling
+    for (int i = 0; i < GA_MAXCB; ++i) {
+        const int S = mc.S > 0 ? mc.S : 1;
+        const float cb = (float)((double)mc.H * (double)i / (double)S);
+        in->ga_cb[i] = i <= S ? (int)ceilf(cb) : 1 << 30;
+    }
+    in->ga_explicit = explicit_rows ? 1 : 0;
+}
+
 extern "C" int srbd_set_gait(srbd_ctx* c, const float* timing, float pgg_dt, float duty_factor, const float* freq_set,
                              int32_t n_freq, const float* freq_local) {
     if (!c || !timing || !freq_set || n_freq < 1 || n_freq > SRBD_MAX_FREQS) return SRBD_E_INVALID;
@@ -1140,20 +1158,7 @@ extern "C" int srbd_set_gait(srbd_ctx* c, const float* timing, float pgg_dt, flo
     if (c->mc.kind != SRBD_ZERO_ORDER && c->mc.S + 1 > GA_MAXCB) return fail(c, SRBD_E_INVALID, "num_splines > 32");
     HIP_TRY(c, hipSetDevice(c->cfg.device_id));
     HIP_TRY(c, hipStreamSynchronize(c->stream));  // no step in flight reads the staging or d_ga_freq
-    StepInput* in = c->h_in;
-    for (int l = 0; l < 4; ++l) in->ga_timing[l] = timing[l];
-    in->ga_dt = pgg_dt;
-    in->ga_duty = duty_factor;
-    in->ga_nfreq = n_freq;
-    for (int i = 0; i < SRBD_MAX_FREQS; ++i) in->ga_freqs[i] = i < n_freq ? freq_set[i] : 0.0f;
-    // chunk boundaries float32(linspace(0, H, S+1)) as spline_coef forms them; integer steps compare
-    // >= a boundary exactly when they are >= its ceiling
-    for (int i = 0; i < GA_MAXCB; ++i) {
-        const int S = c->mc.S > 0 ? c->mc.S : 1;
-        const float cb = (float)((double)c->mc.H * (double)i / (double)S);
-        in->ga_cb[i] = i <= S ? (int)ceilf(cb) : 1 << 30;
-    }
-    in->ga_explicit = freq_local ? 1 : 0;
+    fill_gait(c->mc, c->h_in, timing, pgg_dt, duty_factor, freq_set, n_freq, freq_local != nullptr);
     if (freq_local) {
         if (!c->d_ga_freq) {
             HIP_TRY(c, hipMalloc((void**)&c->d_ga_freq, sizeof(float) * (size_t)c->mc.ldn));
@@ -2647,6 +2652,7 @@ struct srbd_batch {
     uint32_t* d_eflag = nullptr;     // E (merge_body's own publish word per block)
     uint32_t* d_count = nullptr;     // the merge blocks' arrival count, zero between steps
     float* d_noise_rm = nullptr;     // injected noise as given (row-major), E x N x P
+    float* d_ga_freq = nullptr;      // injected per-row step frequencies (srbd_batch_set_gait), E x ldn, padding zero
     bool stepped = false;
 };
 
@@ -2661,6 +2667,7 @@ extern "C" void srbd_batch_destroy(srbd_batch* b) {
     (void)hipFree(b->d_eflag);
     (void)hipFree(b->d_count);
     (void)hipFree(b->d_noise_rm);
+    (void)hipFree(b->d_ga_freq);
     if (b->h_in) (void)hipHostFree(b->h_in);
     if (b->h_out) (void)hipHostFree(b->h_out);
     if (b->c.h_flag) (void)hipHostFree(b->c.h_flag);
@@ -2765,6 +2772,82 @@ extern "C" int srbd_batch_set_rng(srbd_batch* b, int32_t kind) {
     return SRBD_OK;
 }
 
+// Gait-adaptive sampling and the opt-in cost terms of a batch: srbd_set_gait / srbd_clear_gait / srbd_set_cost_terms
+// with the per-step values (leg phases, frequency set, injected frequencies) per environment.  The gait fields live
+// in the staging h_in[e], which srbd_batch_step's fill_input leaves alone and batch_copy_kernel carries with the rest
+// of the input; ModelConst (ga, the cost weights) goes to every launch by value, so a setting holds from the next step.
+extern "C" int srbd_batch_set_gait(srbd_batch* b, const float* timings, float pgg_dt, float duty_factor,
+                                   const float* freq_sets, int32_t n_freq, const float* freq_rows) {
+    if (!b) return SRBD_E_INVALID;
+    srbd_ctx* c = &b->c;
+    ModelConst& mc = c->mc;
+    if (!timings || !freq_sets) return fail(c, SRBD_E_INVALID, "null argument");
+    if (n_freq < 1 || n_freq > SRBD_MAX_FREQS)
+        return fail(c, SRBD_E_INVALID, "n_freq must be in [1, " + std::to_string(SRBD_MAX_FREQS) + "]");
+    if (mc.kind != SRBD_ZERO_ORDER && mc.S + 1 > GA_MAXCB) return fail(c, SRBD_E_INVALID, "num_splines > 32");
+    if (mc.cost_on)
+        return fail(c, SRBD_E_INVALID,
+                    "gait-adaptive sampling with the opt-in cost terms has no batch form (one context runs it on its "
+                    "thread-per-sample kernel): clear the cost weights first, or use separate contexts");
+    HIP_TRY(c, hipSetDevice(c->cfg.device_id));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // no step in flight reads the staging or d_ga_freq
+    const size_t E = (size_t)b->E, ldn = (size_t)mc.ldn, N = (size_t)mc.n_local;
+    if (freq_rows) {  // before the staging is touched: a failure leaves the setting as it was
+        if (!b->d_ga_freq) {
+            float* d = nullptr;
+            hipError_t e = hipMalloc((void**)&d, sizeof(float) * E * ldn);
+            if (e == hipSuccess && (e = hipMemset(d, 0, sizeof(float) * E * ldn)) != hipSuccess) (void)hipFree(d);
+            if (e != hipSuccess)
+                return fail(c, e == hipErrorOutOfMemory ? SRBD_E_NOMEM : SRBD_E_HIP,
+                            std::string("hipMalloc: ") + hipGetErrorString(e));
+            b->d_ga_freq = d;
+        }
+        // environment e's N rows to e * ldn; the padding rows stay zero
+        HIP_TRY(c, hipMemcpy2D(b->d_ga_freq, sizeof(float) * ldn, freq_rows, sizeof(float) * N, sizeof(float) * N, E,
+                               hipMemcpyHostToDevice));
+    }
+    for (size_t e = 0; e < E; ++e)
+        fill_gait(mc, b->h_in + e, timings + 4 * e, pgg_dt, duty_factor, freq_sets + (size_t)n_freq * e, n_freq,
+                  freq_rows != nullptr);
+    mc.ga = 1;
+    return SRBD_OK;
+}
+
+extern "C" int srbd_batch_clear_gait(srbd_batch* b) {
+    if (!b) return SRBD_E_INVALID;
+    srbd_ctx* c = &b->c;
+    if (c->mc.ga) {
+        HIP_TRY(c, hipSetDevice(c->cfg.device_id));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        c->mc.ga = 0;
+    }
+    return SRBD_OK;
+}
+
+extern "C" int srbd_batch_set_cost_terms(srbd_batch* b, const float* r_force, float w_smooth, float w_cone) {
+    if (!b) return SRBD_E_INVALID;
+    srbd_ctx* c = &b->c;
+    ModelConst& mc = c->mc;
+    if (!r_force) return fail(c, SRBD_E_INVALID, "null argument");
+    const float w[5] = {r_force[0], r_force[1], r_force[2], w_smooth, w_cone};
+    int on = 0;
+    for (float x : w) {
+        if (!(x >= 0.0f && x < INFINITY)) return fail(c, SRBD_E_INVALID, "cost weights must be finite and >= 0");
+        on |= x != 0.0f;
+    }
+    if (on && mc.ga)
+        return fail(c, SRBD_E_INVALID,
+                    "the opt-in cost terms with gait-adaptive sampling have no batch form (one context runs them on "
+                    "its thread-per-sample kernel): srbd_batch_clear_gait first, or use separate contexts");
+    HIP_TRY(c, hipSetDevice(c->cfg.device_id));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    mc.cost_on = on;
+    memcpy(mc.cost_r, r_force, sizeof(mc.cost_r));
+    mc.cost_smooth = w_smooth;
+    mc.cost_cone = w_cone;
+    return SRBD_OK;
+}
+
 extern "C" int srbd_batch_copy_costs(srbd_batch* b, float* out_costs) {
     if (!b || !out_costs) return SRBD_E_INVALID;
     if (!b->stepped) return fail(&b->c, SRBD_E_STATE, "no step yet");
@@ -2812,7 +2895,11 @@ extern "C" int srbd_batch_step(srbd_batch* b, const float* states, const float* 
     } else {
         launch_batch_rng(mc, b->d_in, b->d_noise, E, c->stream);
     }
-    launch_batch_rollout(mc, b->d_in, b->d_noise, b->d_costs, b->d_rec, c->wrec_stride, E, c->stream);
+    if (mc.ga)
+        launch_batch_rollout_ga(mc, b->d_in, b->d_noise, b->d_costs, b->d_rec, c->wrec_stride, b->d_ga_freq, E,
+                                c->stream);
+    else
+        launch_batch_rollout(mc, b->d_in, b->d_noise, b->d_costs, b->d_rec, c->wrec_stride, E, c->stream);
     const uint32_t seq = ++c->seq;
     launch_batch_merge(mc, b->d_in, b->d_rec, c->wrec_stride, b->d_noise, b->d_out_host, b->d_eflag, b->d_count,
                        c->d_flag, seq, E, c->stream);

@@ -7,9 +7,11 @@
 //   batch_copy_kernel       the E step inputs, host-mapped staging -> device
 //   batch_rng_kernel        rng_items per environment, keyed by in[e]'s seed and counter
 //   batch_transpose_kernel  injected noise (row-major) -> SoA per environment
-//   batch_rollout_kernel    rollout_quad_kernel's plain form (MPPI / random sampling, no cost terms): one 64-sample
-//                           leaf per 256-thread block, leaf records only (no in-launch fold, merge or draws: with
-//                           E x nleaf blocks in flight the tail those forms shorten is amortised)
+//   batch_rollout_kernel    rollout_quad_kernel's plain form (MPPI / random sampling) and, with EXT, its form with
+//                           the opt-in cost terms: one 64-sample leaf per 256-thread block, leaf records only (no
+//                           in-launch fold, merge or draws: with E x nleaf blocks in flight the tail those forms
+//                           shorten is amortised)
+//   batch_rollout_ga_kernel rollout_ga_quad_kernel (gait-adaptive sampling), the same block and record layout
 //   batch_merge_kernel      one block per environment: merge_body over its leaf records -> out[e]; the last block to
 //                           finish publishes the step's sequence word
 #include <algorithm>
@@ -55,8 +57,12 @@ __global__ void __launch_bounds__(256) batch_transpose_kernel(const float* __res
 // rollout_quad_kernel<KIND, HT, ST, CEMT = false, EXT = false> (srbd_kernels.hip) with the environment on
 // blockIdx.y: the leg-parallel force phase, the component-parallel rigid-body step, the tracking cost and the leaf
 // record, statement for statement, so the costs and records are that kernel's bits.  Left out: the step input by
-// value, the in-launch draws, folds and merges, CEM's sigma scaling and the opt-in cost terms (refused at create).
-template <int KIND, int HT, int ST>
+// value, the in-launch draws, folds and merges and CEM's sigma scaling.
+// EXT (srbd_batch_set_cost_terms): that kernel's EXT form -- the component-parallel force phase with this lane's
+// component of extra_cost_step per leg, each step's terms pinned to their step by an empty asm on the accumulator,
+// no LDS noise stage, and for zero-order a rolling window of four prefetched slots instead of the whole horizon
+// (without the pin and the window the unrolled horizon spills: see rollout_quad_kernel).
+template <int KIND, int HT, int ST, bool EXT = false>
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) batch_rollout_kernel(
     const ModelConst mc, const StepInput* __restrict__ in_arr, const float* __restrict__ noise_arr,
     float* __restrict__ costs_arr, float* __restrict__ recs_arr, int rec_stride) {
@@ -75,7 +81,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) b
                       : mc.PL;
     // ZST (zero-order, compile-time horizon H <= 12): the noise a lane reads stays raw in its registers and goes to
     // LDS after the horizon, where the leaf sums read it (38.5 KB per block: four blocks per CU)
-    constexpr bool ZST = CT && KIND == SRBD_ZERO_ORDER && HT <= 12;
+    constexpr bool ZST = CT && KIND == SRBD_ZERO_ORDER && !EXT && HT <= 12;
     constexpr int PCT = ZST ? 12 * HT : 1;
     constexpr int ZSTR = PCT + 1;
     __shared__ __attribute__((aligned(16))) float zst[ZST ? 64 * ZSTR : 1];
@@ -98,9 +104,16 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) b
     const float* rf = in->ref;
     const float rp = sel3(c, rf[0], rf[1], rf[2]), rv = sel3(c, rf[3], rf[4], rf[5]);
     const float rr = sel3(c, rf[6], rf[7], rf[8]), rw = sel3(c, rf[9], rf[10], rf[11]);
+    float feet[4];  // EXT: this lane's component of every foot
+#pragma unroll
+    for (int l = 0; l < 4; ++l) feet[l] = sel3(c, st[12 + 3 * l], st[13 + 3 * l], st[14 + 3 * l]);
     float p = sel3(c, st[0], st[1], st[2]), v = sel3(c, st[3], st[4], st[5]);
     float r = sel3(c, st[6], st[7], st[8]), w = sel3(c, st[9], st[10], st[11]);
     float cost = 0.0f;
+    // EXT: this lane's component of extra_cost_step
+    const float rwc = sel3(c, mc.cost_r[0], mc.cost_r[1], mc.cost_r[2]);
+    float fprev[4];
+    constexpr bool LEGP = !EXT;  // the force phase leg-parallel; EXT keeps the component-parallel form
     const int lq = q4;  // this lane's leg in the force phase
     uint32_t lmask[4];
 #pragma unroll
@@ -117,10 +130,13 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) b
 
     // specialised shapes: every parameter this lane reads over the horizon is loaded before the first step
     constexpr int NPRE = !CT ? 1 : (KIND == SRBD_ZERO_ORDER ? HT : (KIND == SRBD_LINEAR_SPLINE ? ST + 1 : 4 * ST));
-    float pre[3][NPRE];  // pre[q][i] = component q's slot i of this lane's leg
+    // LEGP: pre[q][i] = component q's slot i of this lane's leg; else pre[l][i] = this lane's component's slot i
+    // of leg l
+    float pre[LEGP ? 3 : 4][NPRE];
     // noise through a buffer descriptor over this environment's matrix alone (P ldn 4 < 2^31, checked at create):
     // a lane's offset can never reach another environment's rows
-    const int cblk = lq * PL;
+    const int cblk = LEGP ? lq * PL
+                          : (KIND == SRBD_ZERO_ORDER ? c * HT : (KIND == SRBD_LINEAR_SPLINE ? c * (ST + 1) : 4 * c));
     const auto nrs = __builtin_amdgcn_make_buffer_rsrc((void*)noise, (short)0, mc.P * mc.ldn * 4, 0x00020000);
     const int voff = (cblk * mc.ldn + k) * 4;
     const float* __restrict__ bl = best + cblk;
@@ -129,9 +145,10 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) b
     }
     auto load_slot = [&](const int i) __attribute__((always_inline)) {
 #pragma unroll
-        for (int l = 0; l < 3; ++l) {
-            const int jr = KIND == SRBD_ZERO_ORDER ? l * HT + i
-                           : (KIND == SRBD_LINEAR_SPLINE ? l * (ST + 1) + i : 10 * (i >> 2) + 4 * l + (i & 3));
+        for (int l = 0; l < (LEGP ? 3 : 4); ++l) {
+            const int jr = LEGP ? (KIND == SRBD_ZERO_ORDER ? l * HT + i
+                                   : (KIND == SRBD_LINEAR_SPLINE ? l * (ST + 1) + i : 10 * (i >> 2) + 4 * l + (i & 3)))
+                                : l * PL + (KIND == SRBD_CUBIC_SPLINE ? 10 * (i >> 2) + (i & 3) : i);
             const float nzv = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(nrs, voff, jr * mc.ldn * 4, 0));
             if constexpr (ZST)
                 pre[l][i] = nzv;  // raw: best is added at use, the value staged for the epilogue
@@ -139,9 +156,11 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) b
                 pre[l][i] = bl[jr] + nzv;
         }
     };
+    // EXT zero-order: slot n + PW loads at step n
+    constexpr int PW = (EXT && KIND == SRBD_ZERO_ORDER) ? (NPRE < 4 ? NPRE : 4) : NPRE;
     if constexpr (CT) {
 #pragma unroll
-        for (int i = 0; i < NPRE; ++i) load_slot(i);
+        for (int i = 0; i < PW; ++i) load_slot(i);
     }
     if constexpr (ZST) {  // the LDS copy of best is complete (the noise loads stay in flight)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -150,6 +169,8 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) b
 
     float dep = p;  // step_ptr dependency: set part-way through each step
     auto step = [&](const int n) __attribute__((always_inline)) {
+        if constexpr (CT && PW < NPRE)
+            if (n + PW < NPRE) load_slot(n + PW);  // n is a compile-time constant here (unrolled horizon)
         const auto is = step_ptr(in, dep);
         float cl[4] = {0.0f, 0.0f, 0.0f, 0.0f};
         if constexpr (!ZST)
@@ -159,58 +180,120 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) b
         const float dt = mc.dts[n];
         const float sq = mc.sq[n], somq = mc.somq[n], sa = mc.sa[n], sb = mc.sb[n], scc = mc.sc[n], sd = mc.sd[n];
         const int idx = CT && KIND != SRBD_ZERO_ORDER ? chunk_index(n, HT, ST) : mc.sidx[n];
-        const float clq = ZST ? clreg[ZST ? n : 0]
-                              : __uint_as_float((__float_as_uint(cl[0]) & lmask[0]) | (__float_as_uint(cl[1]) & lmask[1]) |
-                                                (__float_as_uint(cl[2]) & lmask[2]) | (__float_as_uint(cl[3]) & lmask[3]));
-        const int lbase = lq * PL;
-        // component q of this leg's decoded force (slot i, parameter j of the leg when not prefetched)
-        auto PQ = [&](int q, int i, int j) {
-            if constexpr (ZST) {
-                return bls[lbase + j] + pre[q][i];
-            } else if constexpr (CT) {
-                return pre[q][i];
-            } else {
-                const float z = nz[(size_t)(lbase + j) * ldn];
-                return best[lbase + j] + z;
-            }
-        };
-        float rq[3];
+        float ex = 0.0f;
+        if constexpr (LEGP) {
+            const float clq = ZST ? clreg[ZST ? n : 0]
+                                  : __uint_as_float((__float_as_uint(cl[0]) & lmask[0]) | (__float_as_uint(cl[1]) & lmask[1]) |
+                                                    (__float_as_uint(cl[2]) & lmask[2]) | (__float_as_uint(cl[3]) & lmask[3]));
+            const int lbase = lq * PL;
+            // component q of this leg's decoded force (slot i, parameter j of the leg when not prefetched)
+            auto PQ = [&](int q, int i, int j) {
+                if constexpr (ZST) {
+                    return bls[lbase + j] + pre[q][i];
+                } else if constexpr (CT) {
+                    return pre[q][i];
+                } else {
+                    const float z = nz[(size_t)(lbase + j) * ldn];
+                    return best[lbase + j] + z;
+                }
+            };
+            float rq[3];
 #pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            if (KIND == SRBD_ZERO_ORDER) {
-                rq[q] = PQ(q, n, n + q * H);
-            } else if (KIND == SRBD_LINEAR_SPLINE) {
-                const int o = idx + q * (S + 1);
-                rq[q] = somq * PQ(q, idx, o) + sq * PQ(q, idx + 1, o + 1);
-            } else {
-                const int o = 10 * idx + 4 * q;
-                const float p0 = PQ(q, 4 * idx, o), p1 = PQ(q, 4 * idx + 1, o + 1), p2 = PQ(q, 4 * idx + 2, o + 2),
-                            p3 = PQ(q, 4 * idx + 3, o + 3);
-                const float phi = 0.5f * ((p2 - p1) + (p1 - p0));
-                const float phin = 0.5f * ((p3 - p2) + (p2 - p1));
-                rq[q] = sa * p1 + sb * phi + scc * p2 + sd * phin;
+            for (int q = 0; q < 3; ++q) {
+                if (KIND == SRBD_ZERO_ORDER) {
+                    rq[q] = PQ(q, n, n + q * H);
+                } else if (KIND == SRBD_LINEAR_SPLINE) {
+                    const int o = idx + q * (S + 1);
+                    rq[q] = somq * PQ(q, idx, o) + sq * PQ(q, idx + 1, o + 1);
+                } else {
+                    const int o = 10 * idx + 4 * q;
+                    const float p0 = PQ(q, 4 * idx, o), p1 = PQ(q, 4 * idx + 1, o + 1), p2 = PQ(q, 4 * idx + 2, o + 2),
+                                p3 = PQ(q, 4 * idx + 3, o + 3);
+                    const float phi = 0.5f * ((p2 - p1) + (p1 - p0));
+                    const float phin = 0.5f * ((p3 - p2) + (p2 - p1));
+                    rq[q] = sa * p1 + sb * phi + scc * p2 + sd * phin;
+                }
             }
-        }
-        // shape_leg / clip_leg (srbd_core.h), this lane's leg
-        const float fz = clamp_cs((fref + rq[2]) * clq, mc.grf_min, mc.grf_max);
-        const float lo = mc.neg_mu * fz, hi = mc.mu * fz;
-        const float fx = clamp_cs(third(rq[0] * clq), lo, hi), fy = clamp_cs(third(rq[1] * clq), lo, hi);
-        // integrate(): skew_dot(p_foot - p, f) * c (the position's components from their lanes)
-        const float vx = footL[0] - qp<QP_B0>(p), vy = footL[1] - qp<QP_B1>(p), vz = footL[2] - qp<QP_B2>(p);
-        float sm[6] = {fx * clq, fy * clq, fz * clq, ((-vz) * fy + vy * fz) * clq, (vz * fx + (-vx) * fz) * clq,
-                       ((-vy) * fx + vx * fy) * clq};
+            // shape_leg / clip_leg (srbd_core.h), this lane's leg
+            const float fz = clamp_cs((fref + rq[2]) * clq, mc.grf_min, mc.grf_max);
+            const float lo = mc.neg_mu * fz, hi = mc.mu * fz;
+            const float fx = clamp_cs(third(rq[0] * clq), lo, hi), fy = clamp_cs(third(rq[1] * clq), lo, hi);
+            // integrate(): skew_dot(p_foot - p, f) * c (the position's components from their lanes)
+            const float vx = footL[0] - qp<QP_B0>(p), vy = footL[1] - qp<QP_B1>(p), vz = footL[2] - qp<QP_B2>(p);
+            float sm[6] = {fx * clq, fy * clq, fz * clq, ((-vz) * fy + vy * fz) * clq, (vz * fx + (-vx) * fz) * clq,
+                           ((-vy) * fx + vx * fy) * clq};
 #pragma unroll
-        for (int i = 0; i < 6; ++i) {  // quad butterfly: (l0 + l1) + (l2 + l3) on every lane (adds commute)
-            sm[i] = sm[i] + qp<QP_XOR1>(sm[i]);
-            sm[i] = sm[i] + qp<QP_XOR2>(sm[i]);
+            for (int i = 0; i < 6; ++i) {  // quad butterfly: (l0 + l1) + (l2 + l3) on every lane (adds commute)
+                sm[i] = sm[i] + qp<QP_XOR1>(sm[i]);
+                sm[i] = sm[i] + qp<QP_XOR2>(sm[i]);
+            }
+            const float temp = sel3(c, sm[0], sm[1], sm[2]);
+            dep = sm[5];  // the next step's scalar loads issue from here on (step_ptr)
+            quad_rb_apply3(mc, L, quad_rb_prep(L, r, w), temp, sm[3], sm[4], sm[5], dt, p, v, r, w);
+        } else {
+            float tf[4], tt[4];
+#pragma unroll
+            for (int l = 0; l < 4; ++l) {
+                const int base = l * PL;
+                // parameter j of this leg (i: its slot in the prefetched block when the shape is specialised)
+                auto P = [&](int i, int j) {
+                    if constexpr (CT) {
+                        return pre[l][i];
+                    } else {
+                        const float z = nz[(size_t)(base + j) * ldn];
+                        return best[base + j] + z;
+                    }
+                };
+                float raw;
+                if (KIND == SRBD_ZERO_ORDER) {
+                    raw = P(n, n + c * H);
+                } else if (KIND == SRBD_LINEAR_SPLINE) {
+                    const int o = idx + c * (S + 1);
+                    raw = somq * P(idx, o) + sq * P(idx + 1, o + 1);
+                } else {
+                    const int o = 10 * idx + 4 * c;
+                    const float p0 = P(4 * idx, o), p1 = P(4 * idx + 1, o + 1), p2 = P(4 * idx + 2, o + 2),
+                                p3 = P(4 * idx + 3, o + 3);
+                    const float phi = 0.5f * ((p2 - p1) + (p1 - p0));
+                    const float phin = 0.5f * ((p3 - p2) + (p2 - p1));
+                    raw = sa * p1 + sb * phi + scc * p2 + sd * phin;
+                }
+                // shape_leg / clip_leg, component-wise
+                float zp = clamp_cs((fref + raw) * cl[l], mc.grf_min, mc.grf_max);
+                const float xy = third(raw * cl[l]);
+                const float fz = qp<QP_B2>(c == 2 ? zp : xy);
+                const float f = c == 2 ? fz : clamp_cs(xy, mc.neg_mu * fz, mc.mu * fz);
+                tf[l] = f * cl[l];
+                tt[l] = quad_cross(feet[l] - p, f) * cl[l];
+                // extra_cost_step (srbd_core.h), this lane's component, leg by leg
+                const float u = c == 2 ? f - (cl[l] != 0.0f ? fref : 0.0f) : f;
+                float term = (u * rwc) * u;
+                if (n > 0) {
+                    const float d = f - fprev[l];
+                    term = term + (d * mc.cost_smooth) * d;
+                }
+                {  // x / y lanes only, as a select
+                    float vv = fabsf(xy) - mc.mu * fz;
+                    vv = vv > 0.0f ? vv : 0.0f;
+                    const float cone = (vv * mc.cost_cone) * vv;
+                    term = c < 2 ? term + cone : term;
+                }
+                ex = ex + term;
+                fprev[l] = f;
+            }
+            const float temp = (tf[0] + tf[1]) + (tf[2] + tf[3]);
+            const float temp2 = (tt[0] + tt[1]) + (tt[2] + tt[3]);
+            dep = temp2;  // the next step's scalar loads issue from here on (step_ptr)
+            quad_rigid_body(mc, L, temp, temp2, dt, p, v, r, w);
         }
-        const float temp = sel3(c, sm[0], sm[1], sm[2]);
-        dep = sm[5];  // the next step's scalar loads issue from here on (step_ptr)
-        quad_rb_apply3(mc, L, quad_rb_prep(L, r, w), temp, sm[3], sm[4], sm[5], dt, p, v, r, w);
         // tracking cost (NMPC:451), accumulated per component lane
         const float ep = p - rp, ev = v - rv, er_ = r - rr, ew = w - rw;
         const float tp = (ep * Qp) * ep, tv = (ev * Qv) * ev, tr = (er_ * Qr) * er_, tw = (ew * Qw) * ew;
         cost = cost + (((tp + tv) + tr) + tw);
+        if constexpr (EXT) {
+            cost = cost + ex;
+            asm volatile("" : "+v"(cost));  // each step's terms stay in their step
+        }
     };
     if constexpr (CT) {
         unroll_seq([&](auto nc) { step(decltype(nc)::value); }, std::make_integer_sequence<int, (CT ? HT : 1)>{});
@@ -230,6 +313,132 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) b
     const GroupArgs grp{nullptr, nullptr, 1, nullptr};  // gsize 1: leaf records only
     block_epilogue<false, ZST>(mc, in, SPB, q4 == 0 ? sib : -1, valid, cost, noise, recs, rec_stride, 0.0f, grp, nroll,
                                ZST ? zst : nullptr, ZSTR);
+}
+
+// rollout_ga_quad_kernel<KIND, HT> (srbd_kernels.hip) with the environment on blockIdx.y (srbd_batch_set_gait): the
+// sample's step frequency, contact masks, stance counters and per-leg spline coefficients on each of its four lanes,
+// the decode of this lane's component, the rigid-body step, the tracking cost and the frequency term, statement for
+// statement; the leaf record carries the frequency as its tag (-> StepOutput::best_freq).  Everything the sample's
+// gait depends on is environment e's: in[e]'s leg phases, frequency set, seed and counter (the JAX streams:
+// jax_choice_index on in[e]'s key).  Injected frequencies: row k of environment e at ga_freq_arr[e ldn + k] (k < ldn;
+// mc.ga_freq, one context's pointer, is not read).  Left out: the in-launch draws.
+template <int KIND, int HT>
+__global__ void __launch_bounds__(512) batch_rollout_ga_kernel(const ModelConst mc, const StepInput* __restrict__ in_arr,
+                                                               const float* __restrict__ noise_arr,
+                                                               float* __restrict__ costs_arr,
+                                                               float* __restrict__ recs_arr, int rec_stride,
+                                                               const float* __restrict__ ga_freq_arr) {
+    const int env = blockIdx.y;
+    const StepInput* __restrict__ in = in_arr + env;
+    const float* __restrict__ noise = noise_arr + (size_t)env * mc.P * mc.ldn;
+    float* __restrict__ costs = costs_arr + (size_t)env * mc.ldn;
+    float* __restrict__ recs = recs_arr + (size_t)env * mc.nleaf * rec_stride;
+    const int nroll = gridDim.x;
+
+    const int H = HT > 0 ? HT : mc.H, S = mc.S, PL = mc.PL;  // HT: horizon fixed at compile time
+    const int tid = threadIdx.x;
+    const int q4 = tid & 3;
+    const int c = q4 < 3 ? q4 : 2;
+    const int sib = tid >> 2;
+    const int SPB = 64;  // one leaf per block
+    const int k = blockIdx.x * SPB + sib;  // < nleaf 64 <= ldn
+    const bool valid = k < mc.n_local;
+    const size_t ldn = (size_t)mc.ldn;
+    const float* __restrict__ nz = noise + k;
+    const float* __restrict__ best = in->best;
+
+    // ga_sample_freq with the injected row read from this environment's slice
+    const float f = in->ga_explicit ? ga_freq_arr[(size_t)env * ldn + k] : ga_sample_freq(mc, in, k);
+    uint32_t mask[4];
+    ga_contact_masks(in, H, f, mask);
+    float seg[4];
+#pragma unroll
+    for (int l = 0; l < 4; ++l) seg[l] = ((float)__popc(mask[l]) + 1.0f) / (float)S;
+    int cnt[4] = {-1, -1, -1, -1};
+
+    const QuadLane L = quad_lane(mc, c);
+    const float Qp = sel3(c, mc.Q[0], mc.Q[1], mc.Q[2]), Qv = sel3(c, mc.Q[3], mc.Q[4], mc.Q[5]);
+    const float Qr = sel3(c, mc.Q[6], mc.Q[7], mc.Q[8]), Qw = sel3(c, mc.Q[9], mc.Q[10], mc.Q[11]);
+    const float* st_ = in->state;
+    const float* rf = in->ref;
+    const float rp = sel3(c, rf[0], rf[1], rf[2]), rv = sel3(c, rf[3], rf[4], rf[5]);
+    const float rr = sel3(c, rf[6], rf[7], rf[8]), rw = sel3(c, rf[9], rf[10], rf[11]);
+    float feet[4];
+#pragma unroll
+    for (int l = 0; l < 4; ++l) feet[l] = sel3(c, st_[12 + 3 * l], st_[13 + 3 * l], st_[14 + 3 * l]);
+    float p = sel3(c, st_[0], st_[1], st_[2]), v = sel3(c, st_[3], st_[4], st_[5]);
+    float r = sel3(c, st_[6], st_[7], st_[8]), w = sel3(c, st_[9], st_[10], st_[11]);
+    float cost = 0.0f;
+    // unrolled when HT > 0: every step's parameter loads depend only on the contact masks, so they issue ahead of the
+    // physics chain
+    constexpr int UNR = HT > 0 ? HT : 1;
+#pragma unroll UNR
+    for (int n = 0; n < H; ++n) {
+        float cl[4];
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {
+            const uint32_t b = (mask[l] >> n) & 1u;
+            cl[l] = b ? 1.0f : 0.0f;
+            cnt[l] += (int)b;
+        }
+        const float ns = ((cl[0] + cl[1]) + cl[2]) + cl[3];
+        const float fref = mc.fz_ns[(int)ns];
+        float tf[4], tt[4];  // per-leg force / torque contributions, summed pairwise (integrate()'s order)
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {
+            const int base = l * PL;
+            auto acc = [&](int j) {
+                j = j < 0 ? j + PL : j;
+                return best[base + j] + nz[(size_t)(base + j) * ldn];
+            };
+            const int stc = cnt[l];
+            float raw;
+            if (KIND == SRBD_ZERO_ORDER) {
+                raw = acc(stc + c * H);
+            } else {
+                int idx = 0;
+                for (int i = 0; i <= S; ++i)
+                    if (stc >= in->ga_cb[i]) idx = i;
+                float tau = (float)stc / seg[l];
+                tau = tau - (float)idx;
+                const float q = tau / 1.0f;
+                if (KIND == SRBD_LINEAR_SPLINE) {
+                    const float omq = 1.0f - q;
+                    const int o = idx + c * (S + 1);
+                    raw = omq * acc(o) + q * acc(o + 1);
+                } else {
+                    const float a = 2.0f * q * q * q - 3.0f * q * q + 1.0f;
+                    const float bb = (q * q * q - 2.0f * q * q + q) * 1.0f;
+                    const float cc = -2.0f * q * q * q + 3.0f * q * q;
+                    const float d = (q * q * q - q * q) * 1.0f;
+                    const int o = 10 * idx + 4 * c;
+                    const float p0 = acc(o), p1 = acc(o + 1), p2 = acc(o + 2), p3 = acc(o + 3);
+                    const float phi = 0.5f * ((p2 - p1) + (p1 - p0));
+                    const float phin = 0.5f * ((p3 - p2) + (p2 - p1));
+                    raw = a * p1 + bb * phi + cc * p2 + d * phin;
+                }
+            }
+            const float zp = clamp_cs((fref + raw) * cl[l], mc.grf_min, mc.grf_max);
+            const float xy = third(raw * cl[l]);
+            const float fz = qp<QP_B2>(c == 2 ? zp : xy);
+            const float fo = c == 2 ? fz : clamp_cs(xy, mc.neg_mu * fz, mc.mu * fz);
+            tf[l] = fo * cl[l];
+            tt[l] = quad_cross(feet[l] - p, fo) * cl[l];
+        }
+        const float temp = (tf[0] + tf[1]) + (tf[2] + tf[3]), temp2 = (tt[0] + tt[1]) + (tt[2] + tt[3]);
+        quad_rigid_body(mc, L, temp, temp2, mc.dts[n], p, v, r, w);
+        const float ep = p - rp, ev = v - rv, er_ = r - rr, ew = w - rw;
+        const float tp = (ep * Qp) * ep, tv = (ev * Qv) * ev, tr = (er_ * Qr) * er_, tw = (ew * Qw) * ew;
+        cost = cost + (((tp + tv) + tr) + tw);
+    }
+    cost = (qp<QP_B0>(cost) + qp<QP_B1>(cost)) + qp<QP_B2>(cost);
+    cost = cost + in->cost_feet;
+    const float df = f - 1.3f;
+    cost = cost + (df * 100.0f) * df;  // GA:500
+    if (isnan(cost) || isinf(cost)) cost = 1000000.0f;
+    if (valid && q4 == 0) costs[k] = cost;
+    const GroupArgs grp{nullptr, nullptr, 1, nullptr};  // gsize 1: leaf records only
+    block_epilogue<false>(mc, in, SPB, q4 == 0 ? sib : -1, valid, cost, noise, recs, rec_stride, f, grp, nroll);
 }
 
 // One block per environment (blockIdx.y; blockIdx.x == 0, as merge_body's unsplit form expects): the environment's
@@ -286,11 +495,16 @@ void launch_batch_rollout(const ModelConst& mc, const StepInput* in, const float
                           int rec_stride, int E, hipStream_t s) {
     const dim3 grid(mc.nleaf, E);
     const int H = mc.H, S = mc.S;
-#define SRBD_BR(K, HH, SS)                                                                                       \
-    {                                                                                                            \
-        hipLaunchKernelGGL((batch_rollout_kernel<K, HH, SS>), grid, dim3(256), 0, s, mc, in, noise, costs, recs, \
-                           rec_stride);                                                                          \
-        return;                                                                                                  \
+    // mc.cost_on (srbd_batch_set_cost_terms): the EXT instantiations, on the same compile-time shapes
+#define SRBD_BR(K, HH, SS)                                                                                        \
+    {                                                                                                             \
+        if (mc.cost_on)                                                                                           \
+            hipLaunchKernelGGL((batch_rollout_kernel<K, HH, SS, true>), grid, dim3(256), 0, s, mc, in, noise,     \
+                               costs, recs, rec_stride);                                                          \
+        else                                                                                                      \
+            hipLaunchKernelGGL((batch_rollout_kernel<K, HH, SS>), grid, dim3(256), 0, s, mc, in, noise, costs,    \
+                               recs, rec_stride);                                                                 \
+        return;                                                                                                   \
     }
     switch (mc.kind) {  // launch_rollout's compile-time shapes
         case SRBD_ZERO_ORDER:
@@ -308,6 +522,34 @@ void launch_batch_rollout(const ModelConst& mc, const StepInput* in, const float
             SRBD_BR(SRBD_CUBIC_SPLINE, 0, 0);
     }
 #undef SRBD_BR
+}
+
+void launch_batch_rollout_ga(const ModelConst& mc, const StepInput* in, const float* noise, float* costs, float* recs,
+                             int rec_stride, const float* ga_freq, int E, hipStream_t s) {
+    const dim3 grid(mc.nleaf, E);
+    const int H = mc.H;
+#define SRBD_BG(K, HH)                                                                                            \
+    {                                                                                                             \
+        hipLaunchKernelGGL((batch_rollout_ga_kernel<K, HH>), grid, dim3(256), 0, s, mc, in, noise, costs, recs,   \
+                           rec_stride, ga_freq);                                                                  \
+        return;                                                                                                   \
+    }
+    switch (mc.kind) {  // launch_rollout_ga's compile-time shapes
+        case SRBD_ZERO_ORDER:
+            if (H == 10) SRBD_BG(SRBD_ZERO_ORDER, 10);
+            if (H == 12) SRBD_BG(SRBD_ZERO_ORDER, 12);
+            if (H == 16) SRBD_BG(SRBD_ZERO_ORDER, 16);
+            SRBD_BG(SRBD_ZERO_ORDER, 0);
+        case SRBD_LINEAR_SPLINE:
+            if (H == 12) SRBD_BG(SRBD_LINEAR_SPLINE, 12);
+            if (H == 16) SRBD_BG(SRBD_LINEAR_SPLINE, 16);
+            SRBD_BG(SRBD_LINEAR_SPLINE, 0);
+        default:
+            if (H == 12) SRBD_BG(SRBD_CUBIC_SPLINE, 12);
+            if (H == 16) SRBD_BG(SRBD_CUBIC_SPLINE, 16);
+            SRBD_BG(SRBD_CUBIC_SPLINE, 0);
+    }
+#undef SRBD_BG
 }
 
 void launch_batch_merge(const ModelConst& mc, StepInput* in, const float* recs, int rec_stride, const float* noise,

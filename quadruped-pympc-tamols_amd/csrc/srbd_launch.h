@@ -172,9 +172,14 @@ void launch_batch_copy(const StepInput* in_host, StepInput* in, int E, size_t by
 void launch_batch_rng(const ModelConst& mc, const StepInput* in, float* noise, int E, hipStream_t s);
 // injected noise, E x n_local x P row-major -> SoA per environment
 void launch_batch_transpose(const ModelConst& mc, const float* src, float* noise, int E, hipStream_t s);
-// four-lane rollouts, one 64-sample leaf per block: costs and leaf records (no in-launch fold)
+// four-lane rollouts, one 64-sample leaf per block: costs and leaf records (no in-launch fold); mc.cost_on selects
+// the kernels with the opt-in cost terms
 void launch_batch_rollout(const ModelConst& mc, const StepInput* in, const float* noise, float* costs, float* recs,
                           int rec_stride, int E, hipStream_t s);
+// the gait-adaptive four-lane rollouts, keyed by in[e]'s gait fields; ga_freq: E x ldn injected per-row frequencies
+// (read only when in[e].ga_explicit is set; padding rows zero), else may be NULL
+void launch_batch_rollout_ga(const ModelConst& mc, const StepInput* in, const float* noise, float* costs, float* recs,
+                             int rec_stride, const float* ga_freq, int E, hipStream_t s);
 // one block per environment folds its leaf records to the root (merge_body) and writes out[e]; the blocks count
 // themselves in *count (zero between launches: the last arriver resets it) and the last one stores `seq` in *flag.
 // eflag: E device words (each block's own publish word inside merge_body)

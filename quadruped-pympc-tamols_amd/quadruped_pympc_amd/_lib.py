@@ -194,6 +194,9 @@ SIGNATURES.update({
     "srbd_batch_set_rng": (_I, [_P, _I]),
     "srbd_batch_step": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
     "srbd_batch_copy_costs": (_I, [_P, _P]),
+    "srbd_batch_set_gait": (_I, [_P, _FP, _F, _F, _FP, _I, _FP]),
+    "srbd_batch_clear_gait": (_I, [_P]),
+    "srbd_batch_set_cost_terms": (_I, [_P, _FP, _F, _F]),
 })
 
 # srbd_time_launch kinds (include/srbd_mpc.h)
@@ -709,6 +712,38 @@ class BatchContext:
         """srbd_batch_set_rng: 'philox' (default), 'jax' or 'jax_legacy'; in the JAX modes the seeds are packed keys."""
         code = RNG_CODES[kind] if isinstance(kind, str) else int(kind)
         self.check(lib.srbd_batch_set_rng(self.h, code), "srbd_batch_set_rng")
+
+    def set_gait(self, timings, pgg_dt: float, duty: float, freq_sets, freq_rows=None):
+        """srbd_batch_set_gait: gait-adaptive sampling for the following steps.  timings (E, 4) leg phases,
+        freq_sets (E, n_freq) each environment's candidate step frequencies, freq_rows None (device draws) or (E, N)
+        injected per-sample frequencies; pgg_dt and duty are shared."""
+        E = self.E
+        t = np.ascontiguousarray(timings, dtype=np.float32)
+        if t.shape != (E, 4):
+            raise ValueError(f"timings must be ({E}, 4), got {t.shape}")
+        fs = np.ascontiguousarray(freq_sets, dtype=np.float32)
+        if fs.ndim != 2 or fs.shape[0] != E or fs.shape[1] < 1:
+            raise ValueError(f"freq_sets must be ({E}, n_freq) with n_freq >= 1, got {fs.shape}")
+        fr = None
+        if freq_rows is not None:
+            fr = np.ascontiguousarray(freq_rows, dtype=np.float32)
+            if fr.shape != (E, self.N):
+                raise ValueError(f"freq_rows must be ({E}, {self.N}), got {fr.shape}")
+        self.check(lib.srbd_batch_set_gait(self.h, fptr(t), float(pgg_dt), float(duty), fptr(fs), int(fs.shape[1]),
+                                           fptr(fr)), "srbd_batch_set_gait")
+
+    def clear_gait(self):
+        """srbd_batch_clear_gait: back to the caller's contact sequences (best_freq 0)."""
+        self.check(lib.srbd_batch_clear_gait(self.h), "srbd_batch_clear_gait")
+
+    def set_cost_terms(self, r_force=(0.0, 0.0, 0.0), w_smooth: float = 0.0, w_cone: float = 0.0):
+        """srbd_batch_set_cost_terms: the opt-in force regularisation / GRF smoothing / cone-violation terms for every
+        environment (all 0: the reference's cost)."""
+        r = np.ascontiguousarray(r_force, dtype=np.float32)
+        if r.shape != (3,):
+            raise ValueError(f"r_force must have 3 entries, got shape {r.shape}")
+        self.check(lib.srbd_batch_set_cost_terms(self.h, fptr(r), float(w_smooth), float(w_cone)),
+                   "srbd_batch_set_cost_terms")
 
     def step(self, states, refs, contacts, best, noise=None, seeds=None, counters=None, want_costs=False):
         """One step of every environment: states / refs (E, 24), contacts (E, 4, >=H), best (E, P), noise None or

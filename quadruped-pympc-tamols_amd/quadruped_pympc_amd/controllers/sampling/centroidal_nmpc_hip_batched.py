@@ -81,6 +81,10 @@ class Batched_Sampling_MPC:
                 self._ctx.set_rng(self.rng)
         return self._ctx
 
+    def set_cost_terms(self, r_force=(0.0, 0.0, 0.0), w_smooth: float = 0.0, w_cone: float = 0.0):
+        """srbd_batch_set_cost_terms for every environment (all 0: the reference's cost)."""
+        self.context.set_cost_terms(r_force, w_smooth, w_cone)
+
     def with_newkey(self):
         """Every environment's key advanced as Sampling_MPC.with_newkey advances its stream's."""
         one = self._one

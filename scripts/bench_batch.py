@@ -9,8 +9,14 @@ argument addresses (about 1 us of binding cost per call on either side, so a seq
 Inputs cycle over 8 pre-staged sets; the warm starts are fed back; counters advance by one per step.
 
   python scripts/bench_batch.py                      # the table
+  python scripts/bench_batch.py --gait               # the same comparison with gait-adaptive sampling on both
+                                                     # sides (srbd_batch_set_gait / srbd_set_gait, device-drawn
+                                                     # frequencies) -> profiles/batch_ga_c2.json
+  python scripts/bench_batch.py --cost-terms         # ... with the opt-in cost terms on both sides
+                                                     # -> profiles/batch_ext_c2.json
   python scripts/bench_batch.py --one-shape 16       # 200 batch steps at E = 16 and nothing else: the run to put
-                                                     # under `rocprofv3 --kernel-trace --stats`
+                                                     # under `rocprofv3 --kernel-trace --stats` (with --gait or
+                                                     # --cost-terms: that feature's kernels)
   python scripts/bench_batch.py --kernel-stats run_kernel_stats.csv   # add that run's kernel rows and the rollout
                                                                       # launch's roofline fraction to the JSON
 """
@@ -37,7 +43,12 @@ except ImportError:
 from quadruped_pympc_amd import _lib  # noqa: E402
 from quadruped_pympc_amd.synthetic import CONFIGS, inputs  # noqa: E402
 
-OUT = os.path.join(ROOT, "profiles", "batch_c2.json")
+OUT = {None: os.path.join(ROOT, "profiles", "batch_c2.json"), "gait": os.path.join(ROOT, "profiles", "batch_ga_c2.json"),
+       "cost_terms": os.path.join(ROOT, "profiles", "batch_ext_c2.json")}
+# the settings of the feature runs: the leg phases, candidate set and weights the GPU tests use
+GA_TIMINGS = [(0.1, 0.6, 0.6, 0.1), (0.0, 0.5, 0.5, 0.0), (0.64, 0.99, 1.0, 0.3)]
+GA_FREQS, GA_DUTY = (1.4, 2.0, 2.4), 0.65
+COST_TERMS = {"r_force": (0.1, 0.1, 0.001), "w_smooth": 0.01, "w_cone": 5.0}
 HBM_PEAK_GBS = 8000.0  # bench.py's roofline peak
 N_SETS, BLOCK = 8, 100
 
@@ -53,7 +64,7 @@ def c2_config():
 class Runner:
     """E environments: one batch context and E plain contexts over the same pre-staged inputs."""
 
-    def __init__(self, E: int, sequential: bool = True):
+    def __init__(self, E: int, sequential: bool = True, feature: str | None = None):
         self.w, self.cfg = c2_config()
         self.E, self.P, self.H = E, _lib.num_params(self.cfg), self.cfg.horizon
         sets = [[inputs(self.w, s * E + e) for e in range(E)] for s in range(N_SETS)]
@@ -69,6 +80,15 @@ class Runner:
         self.batch = _lib.BatchContext(self.cfg, E)
         self.ctxs = [_lib.Context(self.cfg) for _ in range(E)] if sequential else []
         self.k_b = self.k_s = 0
+        if feature == "gait":  # the same setting on both sides, once: it holds until changed
+            t = np.array([GA_TIMINGS[e % len(GA_TIMINGS)] for e in range(E)], np.float32)
+            fs = np.tile(np.array(GA_FREQS, np.float32), (E, 1))
+            self.batch.set_gait(t, self.w.dt, GA_DUTY, fs)
+            for e, c in enumerate(self.ctxs):
+                c.set_gait(t[e], self.w.dt, GA_DUTY, fs[e])
+        elif feature == "cost_terms":
+            for c in [self.batch] + self.ctxs:
+                c.set_cost_terms(COST_TERMS["r_force"], COST_TERMS["w_smooth"], COST_TERMS["w_cone"])
 
     def close(self):
         self.batch.close()
@@ -113,8 +133,8 @@ class Runner:
         return lat
 
 
-def measure(E: int, steps: int, warmup: int) -> dict:
-    r = Runner(E)
+def measure(E: int, steps: int, warmup: int, feature: str | None = None) -> dict:
+    r = Runner(E, feature=feature)
     try:
         r.batch_steps(warmup)
         r.sequential_rounds(warmup)
@@ -133,7 +153,7 @@ def measure(E: int, steps: int, warmup: int) -> dict:
             "warm_starts_bit_equal": same}
 
 
-def kernel_rows(path: str, E: int) -> dict:
+def kernel_rows(path: str, E: int, feature: str | None = None) -> dict:
     w, cfg = c2_config()
     rows = []
     with open(path, newline="") as f:
@@ -143,8 +163,10 @@ def kernel_rows(path: str, E: int) -> dict:
                              "avg_us": round(float(row["AverageNs"]) * 1e-3, 3),
                              "min_us": round(float(row["MinNs"]) * 1e-3, 3),
                              "max_us": round(float(row["MaxNs"]) * 1e-3, 3)})
-    out = {"E": E, "source": "rocprofv3 --kernel-trace --stats of `bench_batch.py --one-shape %d`" % E, "kernels": rows}
-    roll = [r for r in rows if "batch_rollout_kernel" in r["kernel"]]
+    flag = {None: "", "gait": "--gait ", "cost_terms": "--cost-terms "}[feature]
+    out = {"E": E, "source": "rocprofv3 --kernel-trace --stats of `bench_batch.py %s--one-shape %d`" % (flag, E),
+           "kernels": rows}
+    roll = [r for r in rows if "batch_rollout_" in r["kernel"]]
     if roll:  # bench.py's roofline: each noise row read once + one cost written, per rollout, times E
         algo = E * w.num_samples * (4 * _lib.num_params(cfg) + 4)
         achieved = algo / (roll[0]["avg_us"] * 1e-6) / 1e9
@@ -162,10 +184,16 @@ def main():
     ap.add_argument("--one-shape", type=int, default=0, metavar="E")
     ap.add_argument("--kernel-stats", default=None, metavar="CSV")
     ap.add_argument("--kernel-stats-envs", type=int, default=16)
-    ap.add_argument("--out", default=OUT)
+    ap.add_argument("--gait", action="store_true", help="gait-adaptive sampling on both sides")
+    ap.add_argument("--cost-terms", action="store_true", help="the opt-in cost terms on both sides")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.gait and a.cost_terms:
+        ap.error("--gait with --cost-terms: the batch has no form of that combination")
+    feature = "gait" if a.gait else ("cost_terms" if a.cost_terms else None)
+    a.out = a.out or OUT[feature]
     if a.one_shape:
-        r = Runner(a.one_shape, sequential=False)
+        r = Runner(a.one_shape, sequential=False, feature=feature)
         try:
             lat = r.batch_steps(200)
         finally:
@@ -177,14 +205,18 @@ def main():
         with open(a.out) as f:
             doc = json.load(f)
     if a.kernel_stats:
-        doc["kernel_trace"] = kernel_rows(a.kernel_stats, a.kernel_stats_envs)
+        doc["kernel_trace"] = kernel_rows(a.kernel_stats, a.kernel_stats_envs, feature)
     else:
         w, _ = c2_config()
         doc.update({"workload": w.name, "shape": {"N_per_env": w.num_samples, "H": w.horizon, "method": w.method,
                                                   "parametrization": w.parametrization, "rng": "philox"},
+                    "feature": {None: "none (the plain cost, the caller's contact sequences)",
+                                "gait": {"gait_adaptive": True, "timings": GA_TIMINGS, "freq_set": GA_FREQS,
+                                         "duty": GA_DUTY, "frequencies": "device-drawn"},
+                                "cost_terms": COST_TERMS}[feature],
                     "timing": "host-to-host around the library call (ctypes, pre-staged addresses); blocks of %d batch "
                               "steps alternate with blocks of %d rounds of E sequential srbd_step calls" % (BLOCK, BLOCK),
-                    "rows": [measure(E, a.steps, a.warmup) for E in a.envs]})
+                    "rows": [measure(E, a.steps, a.warmup, feature) for E in a.envs]})
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(doc, f, indent=1)
