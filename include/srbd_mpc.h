@@ -471,7 +471,9 @@ int srbd_interface_step(srbd_ctx* ctx, srbd_interface_io* io, const float* conta
  * reference's replica mode (simulation/batched_simulations.py:40-58, SURVEY 3.4 and 8(e) "Replica mode") inside one
  * process, for evaluation sweeps, dataset generation (simulation/generate_dataset.py) and training loops.  A step
  * costs four launches whatever E is (input copy, draws or the transpose of injected noise, rollouts, merges) and
- * one host wait on one published word.
+ * one host wait on one published word.  The device-resident step (srbd_batch_step_device below) takes and returns
+ * device arrays on the caller's stream: five launches (pack, draws or transpose, rollouts, merges, unpack) and no
+ * host wait.
  *   Shared: the srbd_config -- robot, N (num_samples is per environment), H, method, parametrization, S, dts, Q,
  *   bounds.  Per environment: everything per step -- state, reference, contact sequence, warm start, noise key.
  *   Equivalence: environment e returns exactly what srbd_step returns on a context srbd_create(cfg) (world_size 1)
@@ -487,7 +489,8 @@ int srbd_interface_step(srbd_ctx* ctx, srbd_interface_io* io, const float* conta
  *   the sigma each step produces, and its merge is one context's column-split hand-off), rank / world_size other
  *   than 0 / 1.  use_graph is ignored.  Gait-adaptive sampling and the opt-in cost terms have batch forms
  *   (srbd_batch_set_gait, srbd_batch_set_cost_terms below), but not both at once.  There are no batch forms of CEM,
- *   armed steps or the device-resident chains.  A failed allocation: SRBD_E_NOMEM; no device: SRBD_E_NODEVICE.
+ *   armed steps or the single context's device-resident chains (srbd_device_step_local and its kin); the batch's
+ *   device-resident form is srbd_batch_step_device.  A failed allocation: SRBD_E_NOMEM; no device: SRBD_E_NODEVICE.
  *   A call that returns an error has changed nothing in best_params.  A step whose launches end without publishing
  *   returns SRBD_E_HIP, leaves the arrival count zero and the next step exact. */
 typedef struct srbd_batch srbd_batch;
@@ -532,6 +535,49 @@ int srbd_batch_set_gait(srbd_batch* b, const float* timings, float pgg_dt, float
                         int32_t n_freq, const float* freq_rows);
 int srbd_batch_clear_gait(srbd_batch* b);
 int srbd_batch_set_cost_terms(srbd_batch* b, const float r_force[3], float w_smooth, float w_cone);
+/* The device-resident step: srbd_batch_step with every array in device memory, enqueued on the caller's stream.
+ *   Every pointer is device memory of the batch's device; the layouts are srbd_batch_step's.  costs may be NULL,
+ *   noise NULL selects device draws; every other pointer is required.  Arrays must not overlap.
+ *   Enqueue contract: hip_stream == NULL selects the batch's own stream; the null (legacy default) stream is
+ *   selected by its explicit handle hipStreamLegacy, (hipStream_t)1.  The call enqueues five launches (pack:
+ *   the step inputs built on the device as srbd_batch_step builds them on the host; draws, or the transpose reading
+ *   io->noise in place; rollouts; merges; unpack: the outputs scattered to the caller's arrays) and returns.  It
+ *   makes no synchronising HIP call, does not wait on the published word and touches no device memory from the
+ *   host.  The outputs are ready when the work enqueued on the stream so far has completed: synchronise the stream,
+ *   or enqueue the consumers on it.  The input arrays are read, and best_params rewritten, in stream order, so
+ *   they may be produced by earlier work on that stream and reused by later work on it.
+ *   Equivalence: for the same inputs, keys, noise stream and settings (srbd_batch_set_rng, _set_gait, _clear_gait,
+ *   _set_cost_terms) every output array holds exactly the bytes srbd_batch_step returns in best_params, srbd_result
+ *   and out_costs -- status and best_freq included.
+ *   Ordering: the batch's internal buffers are shared with the host path.  Every device step records an event
+ *   behind its last launch; srbd_batch_step makes its stream wait on it, srbd_batch_copy_costs, _set_gait,
+ *   _clear_gait, _set_cost_terms and _destroy synchronise on it, and a device step on a different stream than the
+ *   previous one makes that stream wait on it.  So the entry points may be mixed freely from one host thread;
+ *   srbd_batch_copy_costs after a device step returns that step's costs.  The arrays of a step still in flight
+ *   must stay allocated until it has completed.
+ *   SRBD_E_INVALID (with a message, before anything is enqueued): b or io NULL, a required pointer NULL,
+ *   contact_stride < H.  Capturing the call into a HIP graph is not supported. */
+typedef struct srbd_batch_device_io {
+    /* inputs, float32 unless noted */
+    const float* states;       /* E x 24 */
+    const float* refs;         /* E x 24 */
+    const float* contacts;     /* E x 4 x contact_stride; the first H columns are used */
+    const float* noise;        /* NULL -> device draws; else E x N x P row-major, row 0 of each environment zero */
+    const uint64_t* seeds;     /* E */
+    const uint64_t* counters;  /* E */
+    int32_t contact_stride, pad;
+    /* in / out */
+    float* best_params;        /* E x P: warm starts in, updated out */
+    /* outputs */
+    float* grf;                /* E x 12 */
+    float* predicted_state;    /* E x 24 */
+    float* best_cost;          /* E */
+    int32_t* best_index;       /* E */
+    float* best_freq;          /* E */
+    int32_t* status;           /* E */
+    float* costs;              /* E x N saturated costs, or NULL */
+} srbd_batch_device_io;
+int srbd_batch_step_device(srbd_batch* b, const srbd_batch_device_io* io, void* hip_stream);
 
 /* Diagnostic: enable != 0 stamps the phases of the following TAMOLS calls; out_us[5] (may be NULL)
  * receives the last call's mean per-block durations of (patch, queries, scores, slice argmin + count)

@@ -2654,12 +2654,30 @@ struct srbd_batch {
     float* d_noise_rm = nullptr;     // injected noise as given (row-major), E x N x P
     float* d_ga_freq = nullptr;      // injected per-row step frequencies (srbd_batch_set_gait), E x ldn, padding zero
     bool stepped = false;
+    // the device-resident step (srbd_batch_step_device): the merge blocks' records in device memory, the event recorded
+    // behind each device step's last launch, and the stream of the last one while no entry point has joined it
+    StepOutput* d_out = nullptr;     // E
+    hipEvent_t dev_done = nullptr;
+    hipStream_t dev_stream = nullptr;
+    bool dev_pending = false;
 };
+
+// The internal buffers (d_in, d_noise, d_rec, d_costs, d_count, d_ga_freq) are shared by the host path and the device
+// steps, which run on the caller's stream.  The host: wait for the last device step.
+static hipError_t batch_join_host(srbd_batch* b) {
+    if (!b->dev_pending) return hipSuccess;
+    const hipError_t e = hipEventSynchronize(b->dev_done);
+    if (e == hipSuccess) b->dev_pending = false;
+    return e;
+}
 
 extern "C" void srbd_batch_destroy(srbd_batch* b) {
     if (!b) return;
     (void)hipSetDevice(b->c.cfg.device_id);
+    (void)batch_join_host(b);
     if (b->c.stream) (void)hipStreamSynchronize(b->c.stream);
+    if (b->dev_done) (void)hipEventDestroy(b->dev_done);
+    (void)hipFree(b->d_out);
     (void)hipFree(b->d_in);
     (void)hipFree(b->d_noise);
     (void)hipFree(b->d_costs);
@@ -2752,12 +2770,16 @@ extern "C" int srbd_batch_create(const srbd_config* cfg, int32_t num_envs, srbd_
     if ((e = hipMalloc((void**)&b->d_rec, rec_bytes)) != hipSuccess) return cleanup_fail("hipMalloc", e);
     if ((e = hipMalloc((void**)&b->d_eflag, sizeof(uint32_t) * E)) != hipSuccess) return cleanup_fail("hipMalloc", e);
     if ((e = hipMalloc((void**)&b->d_count, sizeof(uint32_t))) != hipSuccess) return cleanup_fail("hipMalloc", e);
+    if ((e = hipMalloc((void**)&b->d_out, sizeof(StepOutput) * E)) != hipSuccess) return cleanup_fail("hipMalloc", e);
+    if ((e = hipEventCreateWithFlags(&b->dev_done, hipEventDisableTiming)) != hipSuccess)
+        return cleanup_fail("hipEventCreate", e);
     // the noise padding rows (n_local .. ldn) stay zero, as in a single context
     if ((e = hipMemsetAsync(b->d_noise, 0, noise_bytes, b->c.stream)) != hipSuccess ||
         (e = hipMemsetAsync(b->d_in, 0, sizeof(StepInput) * E, b->c.stream)) != hipSuccess ||
         (e = hipMemsetAsync(b->d_costs, 0, sizeof(float) * E * (size_t)mc.ldn, b->c.stream)) != hipSuccess ||
         (e = hipMemsetAsync(b->d_eflag, 0, sizeof(uint32_t) * E, b->c.stream)) != hipSuccess ||
-        (e = hipMemsetAsync(b->d_count, 0, sizeof(uint32_t), b->c.stream)) != hipSuccess)
+        (e = hipMemsetAsync(b->d_count, 0, sizeof(uint32_t), b->c.stream)) != hipSuccess ||
+        (e = hipMemsetAsync(b->d_out, 0, sizeof(StepOutput) * E, b->c.stream)) != hipSuccess)
         return cleanup_fail("hipMemset", e);
     if ((e = hipStreamSynchronize(b->c.stream)) != hipSuccess) return cleanup_fail("hipStreamSynchronize", e);
     *out = b;
@@ -2790,7 +2812,8 @@ extern "C" int srbd_batch_set_gait(srbd_batch* b, const float* timings, float pg
                     "gait-adaptive sampling with the opt-in cost terms has no batch form (one context runs it on its "
                     "thread-per-sample kernel): clear the cost weights first, or use separate contexts");
     HIP_TRY(c, hipSetDevice(c->cfg.device_id));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));  // no step in flight reads the staging or d_ga_freq
+    HIP_TRY(c, batch_join_host(b));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // no step in flight reads the staging, d_in or d_ga_freq
     const size_t E = (size_t)b->E, ldn = (size_t)mc.ldn, N = (size_t)mc.n_local;
     if (freq_rows) {  // before the staging is touched: a failure leaves the setting as it was
         if (!b->d_ga_freq) {
@@ -2809,6 +2832,11 @@ extern "C" int srbd_batch_set_gait(srbd_batch* b, const float* timings, float pg
     for (size_t e = 0; e < E; ++e)
         fill_gait(mc, b->h_in + e, timings + 4 * e, pgg_dt, duty_factor, freq_sets + (size_t)n_freq * e, n_freq,
                   freq_rows != nullptr);
+    // a device step (srbd_batch_step_device) never reads the staging: the gait fields go to d_in here (the host step's
+    // batch_copy_kernel writes the same bytes over them)
+    constexpr size_t G0 = offsetof(StepInput, ga_nfreq), G1 = offsetof(StepInput, best);
+    HIP_TRY(c, hipMemcpy2D((char*)b->d_in + G0, sizeof(StepInput), (const char*)b->h_in + G0, sizeof(StepInput),
+                           G1 - G0, E, hipMemcpyHostToDevice));
     mc.ga = 1;
     return SRBD_OK;
 }
@@ -2818,6 +2846,7 @@ extern "C" int srbd_batch_clear_gait(srbd_batch* b) {
     srbd_ctx* c = &b->c;
     if (c->mc.ga) {
         HIP_TRY(c, hipSetDevice(c->cfg.device_id));
+        HIP_TRY(c, batch_join_host(b));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         c->mc.ga = 0;
     }
@@ -2840,6 +2869,7 @@ extern "C" int srbd_batch_set_cost_terms(srbd_batch* b, const float* r_force, fl
                     "the opt-in cost terms with gait-adaptive sampling have no batch form (one context runs them on "
                     "its thread-per-sample kernel): srbd_batch_clear_gait first, or use separate contexts");
     HIP_TRY(c, hipSetDevice(c->cfg.device_id));
+    HIP_TRY(c, batch_join_host(b));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     mc.cost_on = on;
     memcpy(mc.cost_r, r_force, sizeof(mc.cost_r));
@@ -2854,6 +2884,7 @@ extern "C" int srbd_batch_copy_costs(srbd_batch* b, float* out_costs) {
     srbd_ctx* c = &b->c;
     const ModelConst& mc = c->mc;
     HIP_TRY(c, hipSetDevice(c->cfg.device_id));
+    HIP_TRY(c, batch_join_host(b));
     HIP_TRY(c, hipMemcpy2DAsync(out_costs, sizeof(float) * mc.n_local, b->d_costs, sizeof(float) * mc.ldn,
                                 sizeof(float) * mc.n_local, b->E, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -2869,6 +2900,10 @@ extern "C" int srbd_batch_step(srbd_batch* b, const float* states, const float* 
     if (!states || !refs || !contacts || !best_params || !seeds || !counters || !out || contact_stride < mc.H)
         return fail(c, SRBD_E_INVALID, "invalid step arguments");
     HIP_TRY(c, hipSetDevice(c->cfg.device_id));
+    if (b->dev_pending) {  // a device step in flight on another stream: this step's launches follow it
+        HIP_TRY(c, hipStreamWaitEvent(c->stream, b->dev_done, 0));
+        b->dev_pending = false;
+    }
     const int E = b->E, P = mc.P;
     for (int e = 0; e < E; ++e) {
         StepInput* in = b->h_in + e;
@@ -2922,5 +2957,64 @@ extern "C" int srbd_batch_step(srbd_batch* b, const float* states, const float* 
         out[e].best_freq = o.best_freq;
         out[e].status = o.status;
     }
+    return SRBD_OK;
+}
+
+// srbd_batch_step with every array in the caller's device memory, enqueued on the caller's stream: batch_pack_kernel
+// builds d_in[e] as fill_input does, the draws / transpose (reading io->noise in place), rollouts and merges are the
+// host step's launches, the merge blocks write their records to d_out (device memory) and batch_unpack_kernel scatters
+// them and the costs rows to the caller's arrays.  The sequence word is advanced and stored as in the host step, and
+// not waited on.  No synchronising call: the event behind the last launch orders the other entry points after it.
+extern "C" int srbd_batch_step_device(srbd_batch* b, const srbd_batch_device_io* io, void* hip_stream) {
+    // the arguments first, so a bad io is named as such whatever b is (b == NULL: the calling thread's error text)
+    srbd_ctx* c = b ? &b->c : nullptr;
+    if (!io) return fail(c, SRBD_E_INVALID, "srbd_batch_step_device: null io");
+    {
+        const struct {
+            const void* p;
+            const char* name;
+        } req[] = {{io->states, "states"},         {io->refs, "refs"},
+                   {io->contacts, "contacts"},     {io->seeds, "seeds"},
+                   {io->counters, "counters"},     {io->best_params, "best_params"},
+                   {io->grf, "grf"},               {io->predicted_state, "predicted_state"},
+                   {io->best_cost, "best_cost"},   {io->best_index, "best_index"},
+                   {io->best_freq, "best_freq"},   {io->status, "status"}};
+        for (const auto& r : req)
+            if (!r.p)
+                return fail(c, SRBD_E_INVALID, std::string("srbd_batch_step_device: null required pointer: ") + r.name);
+    }
+    if (!b) return fail(nullptr, SRBD_E_INVALID, "srbd_batch_step_device: null batch");
+    const ModelConst& mc = c->mc;
+    if (io->contact_stride < mc.H)
+        return fail(c, SRBD_E_INVALID, "srbd_batch_step_device: contact_stride is smaller than the horizon");
+    HIP_TRY(c, hipSetDevice(c->cfg.device_id));
+    // NULL is the batch's own stream, so the null stream goes by its explicit handle (handed on as the null stream)
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (!s) s = c->stream;
+    else if (s == hipStreamLegacy) s = nullptr;
+    const int E = b->E;
+    // the previous device step on another stream still owns the internal buffers
+    if (b->dev_pending && b->dev_stream != s) HIP_TRY(c, hipStreamWaitEvent(s, b->dev_done, 0));
+    launch_batch_pack(mc, c->cfg.q_diag + 12, *io, b->d_in, E, s);
+    if (io->noise)
+        launch_batch_transpose(mc, io->noise, b->d_noise, E, s);
+    else
+        launch_batch_rng(mc, b->d_in, b->d_noise, E, s);
+    if (mc.ga)
+        launch_batch_rollout_ga(mc, b->d_in, b->d_noise, b->d_costs, b->d_rec, c->wrec_stride, b->d_ga_freq, E, s);
+    else
+        launch_batch_rollout(mc, b->d_in, b->d_noise, b->d_costs, b->d_rec, c->wrec_stride, E, s);
+    const uint32_t seq = ++c->seq;
+    launch_batch_merge(mc, b->d_in, b->d_rec, c->wrec_stride, b->d_noise, b->d_out, b->d_eflag, b->d_count, c->d_flag,
+                       seq, E, s);
+    launch_batch_unpack(mc, *io, b->d_out, b->d_costs, E, s);
+    const hipError_t le = hipGetLastError();
+    // recorded whatever the launches returned: what was enqueued still orders the other entry points
+    const hipError_t re = hipEventRecord(b->dev_done, s);
+    b->dev_stream = s;
+    b->dev_pending = re == hipSuccess;
+    HIP_TRY(c, le);
+    HIP_TRY(c, re);
+    b->stepped = true;
     return SRBD_OK;
 }

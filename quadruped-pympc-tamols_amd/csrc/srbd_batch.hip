@@ -14,6 +14,9 @@
 //   batch_rollout_ga_kernel rollout_ga_quad_kernel (gait-adaptive sampling), the same block and record layout
 //   batch_merge_kernel      one block per environment: merge_body over its leaf records -> out[e]; the last block to
 //                           finish publishes the step's sequence word
+// The device-resident step (srbd_batch_step_device) replaces the input copy and the host's read of out[e]:
+//   batch_pack_kernel       in[e] from the caller's device arrays, as fill_input (srbd_api.hip) builds it on the host
+//   batch_unpack_kernel     out[e] (device memory on this path) and the costs row -> the caller's device arrays
 #include <algorithm>
 
 #include "srbd_device.h"
@@ -26,6 +29,94 @@ __global__ void __launch_bounds__(256) batch_copy_kernel(const uint4* __restrict
                                                          int nwords, int stride_words) {
     const size_t o = (size_t)blockIdx.x * stride_words;
     for (int i = threadIdx.x; i < nwords; i += 256) dst[o + i] = src[o + i];
+}
+
+// fill_input (srbd_api.hip) on the device, one wave per environment: state | ref, the contact columns (the first H
+// from the caller's stride, the rest of MAXH zero), fzref, cost_feet, the key halves, noise_scaled and best.  Every
+// float operation is the host's, in its order and unfused (the pragma: the host compiles this sum without FMA, and the
+// division is the compiler's correctly rounded one), so in[e] is the host path's bit for bit.  The gait fields and
+// sigma of in[e] are not written.  vec: states, refs and best_params are 16-byte aligned.
+struct BatchPackConst {
+    float q_feet[12];  // srbd_config::q_diag[12..23]
+    float mg;
+    int H, P;
+};
+__global__ void __launch_bounds__(64) batch_pack_kernel(const srbd_batch_device_io io, const BatchPackConst pc, int vec,
+                                                        StepInput* __restrict__ in_arr) {
+#pragma clang fp contract(off)
+    const int e = blockIdx.x, tid = threadIdx.x;
+    StepInput* __restrict__ in = in_arr + e;
+    const float* __restrict__ st = io.states + 24 * (size_t)e;
+    const float* __restrict__ rf = io.refs + 24 * (size_t)e;
+    const float* __restrict__ bp = io.best_params + (size_t)e * pc.P;
+    static_assert(offsetof(StepInput, state) == 0 && offsetof(StepInput, ref) == 96, "state | ref head the input");
+    if (vec) {
+        if (tid < 12)
+            reinterpret_cast<float4*>(in)[tid] =
+                tid < 6 ? reinterpret_cast<const float4*>(st)[tid] : reinterpret_cast<const float4*>(rf)[tid - 6];
+        for (int i = tid; i < pc.P / 4; i += 64)
+            reinterpret_cast<float4*>(in->best)[i] = reinterpret_cast<const float4*>(bp)[i];
+    } else {
+        if (tid < 48) reinterpret_cast<float*>(in)[tid] = tid < 24 ? st[tid] : rf[tid - 24];
+        for (int i = tid; i < pc.P; i += 64) in->best[i] = bp[i];
+    }
+    if (tid < MAXH) {  // column n of the four legs
+        const int n = tid;
+        const float* __restrict__ ct = io.contacts + (size_t)e * 4 * io.contact_stride + n;
+        float c[4];
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {
+            c[l] = n < pc.H ? ct[(size_t)l * io.contact_stride] : 0.0f;
+            in->contact[l][n] = c[l];
+        }
+        if (n < pc.H) in->fzref[n] = pc.mg / (((c[0] + c[1]) + c[2]) + c[3]);  // inf when no leg is in stance
+    } else if (tid == MAXH) {
+        float cf = 0.0f;
+#pragma unroll
+        for (int i = 12; i < 24; ++i) {
+            const float d = st[i] - rf[i];
+            cf = cf + (d * pc.q_feet[i - 12]) * d;
+        }
+        in->cost_feet = cf;
+        const uint64_t seed = io.seeds[e], counter = io.counters[e];
+        in->seed_lo = (uint32_t)seed;
+        in->seed_hi = (uint32_t)(seed >> 32);
+        in->ctr_lo = (uint32_t)counter;
+        in->ctr_hi = (uint32_t)(counter >> 32);
+        in->noise_scaled = io.noise ? 1 : 0;
+    }
+}
+
+// out[e] (the merge blocks' records, device memory) and environment e's costs row into the caller's arrays: copies
+// only.  vec: best_params, grf and predicted_state are 16-byte aligned.
+__global__ void __launch_bounds__(256) batch_unpack_kernel(const srbd_batch_device_io io,
+                                                           const StepOutput* __restrict__ out_arr,
+                                                           const float* __restrict__ costs_arr, int P, int N, int ldn,
+                                                           int vec) {
+    const int e = blockIdx.x, tid = threadIdx.x;
+    const StepOutput* __restrict__ o = out_arr + e;
+    static_assert(offsetof(StepOutput, grf) % 16 == 0 && offsetof(StepOutput, pred) % 16 == 0, "float4 reads");
+    if (vec) {
+        for (int i = tid; i < P / 4; i += 256)
+            reinterpret_cast<float4*>(io.best_params + (size_t)e * P)[i] = reinterpret_cast<const float4*>(o->best)[i];
+        if (tid >= 64 && tid < 67)
+            reinterpret_cast<float4*>(io.grf + 12 * (size_t)e)[tid - 64] = reinterpret_cast<const float4*>(o->grf)[tid - 64];
+        if (tid >= 67 && tid < 73)
+            reinterpret_cast<float4*>(io.predicted_state + 24 * (size_t)e)[tid - 67] =
+                reinterpret_cast<const float4*>(o->pred)[tid - 67];
+    } else {
+        for (int i = tid; i < P; i += 256) io.best_params[(size_t)e * P + i] = o->best[i];
+        if (tid >= 64 && tid < 76) io.grf[12 * (size_t)e + tid - 64] = o->grf[tid - 64];
+        if (tid >= 76 && tid < 100) io.predicted_state[24 * (size_t)e + tid - 76] = o->pred[tid - 76];
+    }
+    if (tid == 128) {
+        io.best_cost[e] = o->best_cost;
+        io.best_index[e] = o->best_index;
+        io.best_freq[e] = o->best_freq;
+        io.status[e] = o->status;
+    }
+    if (io.costs)
+        for (int i = tid; i < N; i += 256) io.costs[(size_t)e * N + i] = costs_arr[(size_t)e * ldn + i];
 }
 
 __global__ void __launch_bounds__(256) batch_rng_kernel(const ModelConst mc, const StepInput* __restrict__ in,
@@ -478,6 +569,25 @@ void batch_prepare() {
 void launch_batch_copy(const StepInput* in_host, StepInput* in, int E, size_t bytes, hipStream_t s) {
     hipLaunchKernelGGL(batch_copy_kernel, dim3(E), dim3(256), 0, s, (const uint4*)in_host, (uint4*)in,
                        (int)(bytes / 16), (int)(sizeof(StepInput) / 16));
+}
+
+static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+void launch_batch_pack(const ModelConst& mc, const float* q_feet, const srbd_batch_device_io& io, StepInput* in, int E,
+                       hipStream_t s) {
+    BatchPackConst pc;
+    for (int i = 0; i < 12; ++i) pc.q_feet[i] = q_feet[i];
+    pc.mg = mc.mg;
+    pc.H = mc.H;
+    pc.P = mc.P;
+    const int vec = aligned16(io.states) && aligned16(io.refs) && aligned16(io.best_params);
+    hipLaunchKernelGGL(batch_pack_kernel, dim3(E), dim3(64), 0, s, io, pc, vec, in);
+}
+
+void launch_batch_unpack(const ModelConst& mc, const srbd_batch_device_io& io, const StepOutput* out,
+                         const float* costs, int E, hipStream_t s) {
+    const int vec = aligned16(io.best_params) && aligned16(io.grf) && aligned16(io.predicted_state);
+    hipLaunchKernelGGL(batch_unpack_kernel, dim3(E), dim3(256), 0, s, io, out, costs, mc.P, mc.n_local, mc.ldn, vec);
 }
 
 void launch_batch_rng(const ModelConst& mc, const StepInput* in, float* noise, int E, hipStream_t s) {

@@ -168,6 +168,12 @@ constexpr int BATCH_MAX_SAMPLES = 16384;  // 256 leaves: what one merge block fo
 void batch_prepare();  // once per batch context: the staged merge's dynamic LDS limit
 // in_host[e] -> in[e], the first `bytes` (a multiple of 16) of every StepInput; one block per environment
 void launch_batch_copy(const StepInput* in_host, StepInput* in, int E, size_t bytes, hipStream_t s);
+// the device-resident step: in[e] from the caller's device arrays as fill_input builds it (q_feet: q_diag[12..23];
+// the gait fields and sigma are left alone), and out[e] (device memory) with the costs rows into the caller's arrays
+void launch_batch_pack(const ModelConst& mc, const float* q_feet, const srbd_batch_device_io& io, StepInput* in, int E,
+                       hipStream_t s);
+void launch_batch_unpack(const ModelConst& mc, const srbd_batch_device_io& io, const StepOutput* out,
+                         const float* costs, int E, hipStream_t s);
 // environment e's draws keyed by in[e]'s seed and counter (rng_items)
 void launch_batch_rng(const ModelConst& mc, const StepInput* in, float* noise, int E, hipStream_t s);
 // injected noise, E x n_local x P row-major -> SoA per environment

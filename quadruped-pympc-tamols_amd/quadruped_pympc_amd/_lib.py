@@ -82,6 +82,17 @@ class InterfaceIO(C.Structure):
     ]
 
 
+class BatchDeviceIO(C.Structure):
+    """srbd_batch_device_io (include/srbd_mpc.h): the device arrays of one srbd_batch_step_device call."""
+    _fields_ = [
+        ("states", _P), ("refs", _P), ("contacts", _P), ("noise", _P), ("seeds", _P), ("counters", _P),
+        ("contact_stride", _I), ("pad", _I),
+        ("best_params", _P),
+        ("grf", _P), ("predicted_state", _P), ("best_cost", _P), ("best_index", _P), ("best_freq", _P),
+        ("status", _P), ("costs", _P),
+    ]
+
+
 SIGNATURES = {
     "srbd_num_params": (_I, [C.POINTER(SrbdConfig)]),
     "srbd_device_count": (_I, [_IP]),
@@ -197,6 +208,7 @@ SIGNATURES.update({
     "srbd_batch_set_gait": (_I, [_P, _FP, _F, _F, _FP, _I, _FP]),
     "srbd_batch_clear_gait": (_I, [_P]),
     "srbd_batch_set_cost_terms": (_I, [_P, _FP, _F, _F]),
+    "srbd_batch_step_device": (_I, [_P, C.POINTER(BatchDeviceIO), _P]),
 })
 
 # srbd_time_launch kinds (include/srbd_mpc.h)
@@ -775,4 +787,70 @@ class BatchContext:
     def copy_costs(self) -> np.ndarray:
         out = np.empty((self.E, self.N), np.float32)
         self.check(lib.srbd_batch_copy_costs(self.h, out.ctypes.data), "srbd_batch_copy_costs")
+        return out
+
+    def step_device(self, states, refs, contacts, best, seeds, counters, *, noise=None, want_costs=False,
+                    stream=None):
+        """srbd_batch_step_device: one step of every environment on torch tensors of the context's device, enqueued
+        on ``stream`` (None: ``torch.cuda.current_stream()``) without a host synchronisation.  states / refs (E, 24),
+        contacts (E, 4, >=H), best (E, P) float32, updated in place; seeds / counters (E,) int64 or uint64
+        (reinterpreted); noise None or (E, N, P) float32.  Every tensor contiguous.  Returns a dict of freshly
+        allocated tensors: grf (E, 12), predicted_state (E, 24), best_cost, best_freq (E,) float32, best_index, status
+        (E,) int32, and costs (E, N) with ``want_costs``.  The values are what ``step`` returns for the same inputs,
+        bit for bit; they are ready in stream order (consume them on ``stream``, or synchronise it).  The inputs are
+        read in stream order too: tensors produced on another stream need the usual event / ``record_stream`` care."""
+        import torch
+
+        E, H, P, N = self.E, self.cfg.horizon, self.P, self.N
+        dev = torch.device("cuda", self.cfg.device_id)
+        keys = (torch.int64, torch.uint64) if hasattr(torch, "uint64") else (torch.int64,)
+
+        given = []
+
+        def want(name, t, shape, dtypes=(torch.float32,)):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{name} must be a torch tensor, got {type(t).__name__}")
+            if t.dtype not in dtypes:
+                raise ValueError(f"{name} must be {' or '.join(str(d) for d in dtypes)}, got {t.dtype}")
+            if tuple(t.shape) != shape:
+                raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
+            if not t.is_contiguous():
+                raise ValueError(f"{name} must be contiguous")
+            given.append((name, t))
+
+        want("states", states, (E, 24))
+        want("refs", refs, (E, 24))
+        if not isinstance(contacts, torch.Tensor) or contacts.dim() != 3 or contacts.shape[2] < H:
+            raise ValueError(f"contacts must be a torch tensor of shape ({E}, 4, >={H})")
+        want("contacts", contacts, (E, 4, int(contacts.shape[2])))
+        want("best", best, (E, P))
+        want("seeds", seeds, (E,), keys)
+        want("counters", counters, (E,), keys)
+        if noise is not None:
+            want("noise", noise, (E, N, P))
+        for name, t in given:  # dtypes and shapes first, so a CPU tensor of the wrong shape is refused for its shape
+            if t.device != dev:
+                raise ValueError(f"{name} must be on {dev}, got {t.device}")
+        s = torch.cuda.current_stream(dev) if stream is None else stream
+        with torch.cuda.stream(s):  # the outputs belong to the stream that writes them
+            out = {"grf": torch.empty((E, 12), dtype=torch.float32, device=dev),
+                   "predicted_state": torch.empty((E, 24), dtype=torch.float32, device=dev),
+                   "best_cost": torch.empty(E, dtype=torch.float32, device=dev),
+                   "best_index": torch.empty(E, dtype=torch.int32, device=dev),
+                   "best_freq": torch.empty(E, dtype=torch.float32, device=dev),
+                   "status": torch.empty(E, dtype=torch.int32, device=dev)}
+            if want_costs:
+                out["costs"] = torch.empty((E, N), dtype=torch.float32, device=dev)
+        io = BatchDeviceIO(states=states.data_ptr(), refs=refs.data_ptr(), contacts=contacts.data_ptr(),
+                           noise=None if noise is None else noise.data_ptr(), seeds=seeds.data_ptr(),
+                           counters=counters.data_ptr(), contact_stride=int(contacts.shape[2]), pad=0,
+                           best_params=best.data_ptr(), grf=out["grf"].data_ptr(),
+                           predicted_state=out["predicted_state"].data_ptr(), best_cost=out["best_cost"].data_ptr(),
+                           best_index=out["best_index"].data_ptr(), best_freq=out["best_freq"].data_ptr(),
+                           status=out["status"].data_ptr(),
+                           costs=out["costs"].data_ptr() if want_costs else None)
+        # torch's default stream is the null stream, handle 0, which the C call reads as "the batch's own stream":
+        # hand it on by its explicit handle (hipStreamLegacy)
+        self.check(lib.srbd_batch_step_device(self.h, C.byref(io), C.c_void_p(s.cuda_stream or 1)),
+                   "srbd_batch_step_device")
         return out

@@ -121,6 +121,55 @@ class Batched_Sampling_MPC:
         return (grf, np.zeros((E, 12), dtype=np.int32), pred, best, cost, np.full(E, 1.4),
                 LazyBatchCosts(ctx, self._calls, self))
 
+    # the step frequencies compute_control_device returns: the constant of compute_control, or (the gait-adaptive
+    # class) the best rows' frequencies
+    _device_step_frequencies_from_result = False
+
+    def compute_control_device(self, states, references, contact_sequences, best_control_parameters, keys, *,
+                               noise=None, stream=None):
+        """``compute_control`` on torch tensors of the context's device (``srbd_batch_step_device``): nothing crosses
+        to the host and nothing waits for the device; the step is enqueued on ``stream`` (None: torch's current
+        stream) and the returned tensors are ready in that stream's order.
+
+        states, references (E, 24), contact_sequences (E, 4, >=H), best_control_parameters (E, P): contiguous float32
+        tensors; best_control_parameters is updated in place and returned.  keys, int64 or uint64: for
+        ``rng == 'philox'`` the (E, 2) (seed, counter) tensor; for the JAX streams the (E,) packed keys
+        (``_lib.pack_key``), the step number being the counter as in ``compute_control``.  Advancing JAX keys on the
+        device is not provided: split them on the host (``with_newkey``) and upload the packed keys.
+
+        Returns the single class's tuple: (GRFs (E, 12), footholds (E, 12), predicted states (E, 24), best parameters
+        (E, P), best costs (E,), step frequencies (E,), costs (E, N) lazy -- fetched to the host on first use)."""
+        import torch
+
+        ctx = self.context
+        E = self.num_envs
+        if not isinstance(keys, torch.Tensor):
+            raise ValueError("keys must be a torch tensor")
+        dev = keys.device
+        if self.rng == "philox":
+            if keys.dim() != 2 or tuple(keys.shape) != (E, 2):
+                raise ValueError(f"keys must be ({E}, 2) (seed, counter), got {tuple(keys.shape)}")
+            s = torch.cuda.current_stream(dev) if stream is None else stream
+            with torch.cuda.stream(s):
+                seeds, counters = keys[:, 0].contiguous(), keys[:, 1].contiguous()
+        else:
+            if tuple(keys.shape) != (E,):
+                raise ValueError(f"keys must be ({E},) packed JAX keys, got {tuple(keys.shape)}")
+            s = torch.cuda.current_stream(dev) if stream is None else stream
+            seeds = keys
+            with torch.cuda.stream(s):
+                counters = torch.full((E,), self._calls + 1, dtype=torch.int64, device=dev)
+        out = ctx.step_device(states, references, contact_sequences, best_control_parameters, seeds, counters,
+                              noise=noise, stream=stream)
+        self._calls += 1
+        with torch.cuda.stream(s):
+            footholds = torch.zeros((E, 12), dtype=torch.int32, device=dev)
+            freq = (out["best_freq"] if self._device_step_frequencies_from_result
+                    else torch.full((E,), 1.4, dtype=torch.float64, device=dev))
+        self.last_device_result = out
+        return (out["grf"], footholds, out["predicted_state"], best_control_parameters, out["best_cost"], freq,
+                LazyBatchCosts(ctx, self._calls, self))
+
     def prepare_state_and_reference(self, states_current, reference_states, current_contacts, previous_contacts,
                                     mpc_frequency=100):
         """Sampling_MPC.prepare_state_and_reference (srbd_prepare_state) per environment: sequences of E state /

@@ -33,6 +33,10 @@ class Batched_Sampling_MPC(_BatchedBase):
         self.step_freq_delta = self._one_ga.step_freq_delta
         self.dt = self._one_ga.dt
 
+    # compute_control_device (inherited) steps with the gait setting of the last compute_control / context.set_gait
+    # call -- the leg phases and candidate sets are host values -- and returns the best rows' step frequencies
+    _device_step_frequencies_from_result = True
+
     def freq_sets(self, nominal_step_frequencies, optimize_swings) -> np.ndarray:
         """(E, n_freq): environment e's ``_freq_set(nominal_step_frequencies[e], optimize_swings[e])``."""
         E = self.num_envs
