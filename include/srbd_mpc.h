@@ -579,6 +579,56 @@ typedef struct srbd_batch_device_io {
 } srbd_batch_device_io;
 int srbd_batch_step_device(srbd_batch* b, const srbd_batch_device_io* io, void* hip_stream);
 
+/* The producers of the device-resident step on the device: the periodic gait generator and
+ * prepare_state_and_reference (srbd_host.h: srbd_pgg_run, srbd_pgg_contact_sequence, srbd_prepare_state) for
+ * num_envs environments per call, so that generator.run -> contact sequence -> prepare -> srbd_batch_step_device
+ * never leaves the GPU.  Reference lines restated per environment (paths as in srbd_host.h):
+ *   srbd_pgg_run_device              <- PeriodicGaitGenerator.run                       periodic_gait_generator.py:48-76
+ *   srbd_pgg_contact_sequence_device <- PeriodicGaitGenerator.compute_contact_sequence  :93-118
+ *   srbd_prepare_state_device        <- Sampling_MPC.prepare_state_and_reference        centroidal_nmpc_jax.py:563-627
+ *   Generator state: d_pgg is an array of num_envs srbd_pgg structs (srbd_host.h, unchanged plain data) in device
+ *   memory.  The caller initialises them on the host with srbd_pgg_init, uploads them, and may download and inspect
+ *   them at any time.
+ *   srbd_pgg_run_device: every environment's phases advanced by dt * d_step_freqs[e] (d_step_freqs NULL: by dt * its
+ *   own step_freq field), the start-up hold (init) honoured against phase_offset and cleared on release, the state
+ *   written back, and the contact flags written as float32 1.0 / 0.0 to d_contact_out (num_envs x 4).
+ *   srbd_pgg_contact_sequence_device: the run(0) column, then horizon - 1 run(dts[j]) steps with j advanced by lens
+ *   (dts[j] holds for the steps i < lens[j]), written to d_contacts[e][leg][0 .. horizon) of a num_envs x 4 x
+ *   contact_stride array -- the layout srbd_batch_step_device reads; the columns at and beyond horizon are not
+ *   written.  The `horizon` argument is used; the structs' horizon field is not read.  The state is left as found,
+ *   except in a SRBD_GAIT_FULL_STANCE environment, which gets ones in its horizon columns and its generator reset, as
+ *   the host does (the step reads only `horizon` columns, so the host's 2 x horizon is not reproduced).  dts and lens
+ *   are host arrays of n_dts entries shared by all environments; they are checked on the host and travel in the
+ *   kernel arguments.
+ *   srbd_prepare_state_device: d_state_in, d_ref_in num_envs x 24 float64 (srbd_prepare_state's layouts),
+ *   d_current_contact, d_previous_contact num_envs x 4 float32; d_states, d_refs num_envs x 24 float32.  Swing feet
+ *   (current 0) take the reference foot; a leg lifting off (previous 1, current 0) zeroes its params_per_leg entries
+ *   of d_best_params[e] (num_envs x num_params float32, in place; may be NULL).
+ *   Equivalence: for environment e the device state after any sequence of these calls holds the bytes of a host
+ *   srbd_pgg that received the same calls, and the outputs are the host functions' float64 values cast to float32:
+ *   exact for the contact flags, and for states and refs the cast the host step makes when it stages them.  The
+ *   arithmetic is float64 in the order of the host functions, unfused.
+ *   Enqueue contract: each call enqueues exactly one launch on hip_stream and returns; it makes no synchronising HIP
+ *   call and touches no device memory from the host.  The stream handle is read as srbd_batch_step_device reads it,
+ *   except that NULL also selects the legacy null stream (there is no batch here to own a stream).  The pointers
+ *   are memory of the current device.  None of a batch's internal buffers are used, so the calls need no event and
+ *   do not enter the ordering rule above: order them against a step as any work on a stream.
+ *   SRBD_E_INVALID (before any HIP call): a NULL required pointer; num_envs outside 1..4096; horizon outside
+ *   1..SRBD_MAX_HORIZON; contact_stride < horizon; n_dts outside 1..32; lens that would run past n_dts before step
+ *   horizon - 1 (where the reference raises IndexError); params_per_leg < 1 or 4 * params_per_leg > num_params when
+ *   d_best_params is given.  A failed launch: SRBD_E_HIP, or SRBD_E_NODEVICE where no device exists. */
+struct srbd_pgg;
+int srbd_pgg_run_device(struct srbd_pgg* d_pgg, int32_t num_envs, double dt,
+                        const double* d_step_freqs /* E, or NULL: each entry's own step_freq */,
+                        float* d_contact_out /* E x 4 */, void* hip_stream);
+int srbd_pgg_contact_sequence_device(struct srbd_pgg* d_pgg, int32_t num_envs, int32_t horizon, const double* dts,
+                                     const int32_t* lens, int32_t n_dts /* host arrays */, float* d_contacts,
+                                     int32_t contact_stride, void* hip_stream);
+int srbd_prepare_state_device(int32_t num_envs, const double* d_state_in, const double* d_ref_in,
+                              const float* d_current_contact, const float* d_previous_contact, int32_t params_per_leg,
+                              int32_t num_params, float* d_best_params /* or NULL */, float* d_states, float* d_refs,
+                              void* hip_stream);
+
 /* Diagnostic: enable != 0 stamps the phases of the following TAMOLS calls; out_us[5] (may be NULL)
  * receives the last call's mean per-block durations of (patch, queries, scores, slice argmin + count)
  * and the span from the first block's start to the last leg's end, in us.  enable == 0 turns it off. */

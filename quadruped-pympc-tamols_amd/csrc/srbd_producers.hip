@@ -1,0 +1,208 @@
+// srbd_producers.hip -- the producers of the batched device-resident step on the device: the periodic gait generator
+// and prepare_state_and_reference for E environments per launch (srbd_pgg_run_device,
+// srbd_pgg_contact_sequence_device, srbd_prepare_state_device; include/srbd_mpc.h).  Each kernel restates one host
+// producer of srbd_host.cpp per environment -- float64, the same operations in the same order, unfused -- so the
+// generator state keeps the bytes the host functions would leave and the outputs are the host's values cast to
+// float32.  Reference paths as in srbd_host.cpp:
+//   PGG  = quadruped_pympc/helpers/periodic_gait_generator.py
+//   NMPC = quadruped_pympc/controllers/sampling/centroidal_nmpc_jax.py
+//   pgg_run_kernel               srbd_pgg_run               PGG:48-76
+//   pgg_contact_sequence_kernel  srbd_pgg_contact_sequence  PGG:93-118
+//   prepare_state_kernel         srbd_prepare_state         NMPC:563-627 (no solution shift)
+// Legs are independent in all three, so one lane owns one (environment, leg): lane t of the grid is leg t & 3 of
+// environment t >> 2, 64 environments per 256-thread block, the lanes past 4 E idle.  No LDS, no cross-lane traffic.
+#include <hip/hip_runtime.h>
+#include <math.h>
+
+#include "../../include/srbd_host.h"
+#include "../../include/srbd_mpc.h"
+
+namespace srbd {
+
+constexpr int PROD_BLOCK = 256;
+constexpr int PROD_MAX_ENVS = 4096;  // srbd_batch_create's range
+constexpr int PROD_MAX_DTS = 32;
+
+// Python's float `x % 1.0` (srbd_host.cpp pymod1; the float64 fmod is exact on both sides).
+__device__ inline double pymod1_dev(double x) {
+    double r = fmod(x, 1.0);
+    if (r != 0.0) {
+        if (r < 0.0) r += 1.0;
+    } else {
+        r = copysign(0.0, 1.0);
+    }
+    return r;
+}
+
+// One leg's srbd_pgg_run: the phase and the start-up hold are advanced in place, the contact flag returned.
+__device__ inline float pgg_leg_run(double& ph, int32_t& ini, double offset, double duty, double inc) {
+#pragma clang fp contract(off)
+    ph = pymod1_dev(ph + inc);
+    if (ini) {
+        if (!(ph <= offset)) {
+            ini = 0;
+            ph = 0.0;
+        }
+        return 1.0f;
+    }
+    return ph < duty ? 1.0f : 0.0f;
+}
+
+__global__ void __launch_bounds__(PROD_BLOCK) pgg_run_kernel(srbd_pgg* __restrict__ pgg, int E, double dt,
+                                                             const double* __restrict__ step_freqs,
+                                                             float* __restrict__ contact_out) {
+#pragma clang fp contract(off)
+    const int t = blockIdx.x * PROD_BLOCK + threadIdx.x;
+    if (t >= 4 * E) return;
+    const int e = t >> 2, l = t & 3;
+    srbd_pgg* g = pgg + e;
+    const double inc = dt * (step_freqs ? step_freqs[e] : g->step_freq);
+    double ph = g->phase_signal[l];
+    int32_t ini = g->init[l];
+    const float c = pgg_leg_run(ph, ini, g->phase_offset[l], g->duty_factor, inc);
+    g->phase_signal[l] = ph;
+    g->init[l] = ini;
+    contact_out[t] = c;
+}
+
+// dts[j] holds for the steps i < lens[j]; validated on the host (the walk below never reaches n_dts).
+struct PggSeqConst {
+    double dts[PROD_MAX_DTS];
+    int32_t lens[PROD_MAX_DTS];
+    int32_t n_dts, H, stride;
+};
+
+__global__ void __launch_bounds__(PROD_BLOCK) pgg_contact_sequence_kernel(srbd_pgg* __restrict__ pgg, int E,
+                                                                          const PggSeqConst sc,
+                                                                          float* __restrict__ contacts) {
+#pragma clang fp contract(off)
+    const int t = blockIdx.x * PROD_BLOCK + threadIdx.x;
+    if (t >= 4 * E) return;
+    const int e = t >> 2, l = t & 3;
+    srbd_pgg* g = pgg + e;
+    float* __restrict__ row = contacts + (size_t)t * sc.stride;
+    if (g->gait_type == SRBD_GAIT_FULL_STANCE) {  // ones, and srbd_pgg_reset (gait_offsets' row of this gait)
+        for (int i = 0; i < sc.H; ++i) row[i] = 1.0f;
+        const double off = (l == 1 || l == 2) ? 0.5 : 0.0;
+        g->phase_offset[l] = off;
+        g->phase_signal[l] = off;
+        g->init[l] = 0;
+        return;
+    }
+    double ph = g->phase_signal[l];
+    int32_t ini = g->init[l];
+    const int32_t ini0 = ini;
+    const double offset = g->phase_offset[l], duty = g->duty_factor, freq = g->step_freq;
+    row[0] = pgg_leg_run(ph, ini, offset, duty, 0.0 * freq);
+    int j = 0;
+    for (int i = 1; i < sc.H; ++i) {
+        if (i >= sc.lens[j]) ++j;
+        if (j >= sc.n_dts) break;  // refused on the host; never an index past the arrays
+        row[i] = pgg_leg_run(ph, ini, offset, duty, sc.dts[j] * freq);
+    }
+    // the state is left as found; the host restores it through srbd_pgg_set_phase_signal, which stores init != 0
+    if (ini0 != (ini0 != 0)) g->init[l] = 1;
+}
+
+// Lane (e, l) copies the base entries 3 l .. 3 l + 2 and foot l of state and reference, and zeroes leg l's warm start
+// when it lifts off.
+__global__ void __launch_bounds__(PROD_BLOCK) prepare_state_kernel(int E, const double* __restrict__ state_in,
+                                                                   const double* __restrict__ ref_in,
+                                                                   const float* __restrict__ current_contact,
+                                                                   const float* __restrict__ previous_contact,
+                                                                   int params_per_leg, int num_params,
+                                                                   float* __restrict__ best_params,
+                                                                   float* __restrict__ states,
+                                                                   float* __restrict__ refs) {
+    const int t = blockIdx.x * PROD_BLOCK + threadIdx.x;
+    if (t >= 4 * E) return;
+    const int e = t >> 2, l = t & 3;
+    const double* __restrict__ si = state_in + 24 * (size_t)e;
+    const double* __restrict__ ri = ref_in + 24 * (size_t)e;
+    float* __restrict__ so = states + 24 * (size_t)e;
+    float* __restrict__ ro = refs + 24 * (size_t)e;
+    const bool swing = (double)current_contact[t] == 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int b = 3 * l + k, f = 12 + 3 * l + k;
+        so[b] = (float)si[b];
+        ro[b] = (float)ri[b];
+        const double rf = ri[f];
+        so[f] = (float)(swing ? rf : si[f]);
+        ro[f] = (float)rf;
+    }
+    if (best_params && swing && (double)previous_contact[t] == 1.0) {
+        float* __restrict__ bp = best_params + (size_t)e * num_params + (size_t)l * params_per_leg;
+        for (int j = 0; j < params_per_leg; ++j) bp[j] = 0.0f;
+    }
+}
+
+}  // namespace srbd
+
+using namespace srbd;
+
+namespace {
+
+// NULL and hipStreamLegacy both name the legacy null stream: there is no batch here to own one.
+hipStream_t stream_of(void* hip_stream) {
+    hipStream_t s = (hipStream_t)hip_stream;
+    return s == hipStreamLegacy ? nullptr : s;
+}
+
+int launch_status() {
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return SRBD_OK;
+    int ndev = 0;
+    return (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) ? SRBD_E_NODEVICE : SRBD_E_HIP;
+}
+
+unsigned blocks_of(int E) { return (unsigned)((4 * E + PROD_BLOCK - 1) / PROD_BLOCK); }
+
+bool envs_ok(int32_t E) { return E >= 1 && E <= PROD_MAX_ENVS; }
+
+}  // namespace
+
+extern "C" int srbd_pgg_run_device(srbd_pgg* d_pgg, int32_t num_envs, double dt, const double* d_step_freqs,
+                                   float* d_contact_out, void* hip_stream) {
+    if (!d_pgg || !d_contact_out || !envs_ok(num_envs)) return SRBD_E_INVALID;
+    hipLaunchKernelGGL(pgg_run_kernel, dim3(blocks_of(num_envs)), dim3(PROD_BLOCK), 0, stream_of(hip_stream), d_pgg,
+                       num_envs, dt, d_step_freqs, d_contact_out);
+    return launch_status();
+}
+
+extern "C" int srbd_pgg_contact_sequence_device(srbd_pgg* d_pgg, int32_t num_envs, int32_t horizon, const double* dts,
+                                                const int32_t* lens, int32_t n_dts, float* d_contacts,
+                                                int32_t contact_stride, void* hip_stream) {
+    if (!d_pgg || !dts || !lens || !d_contacts || !envs_ok(num_envs)) return SRBD_E_INVALID;
+    if (horizon < 1 || horizon > SRBD_MAX_HORIZON || contact_stride < horizon) return SRBD_E_INVALID;
+    if (n_dts < 1 || n_dts > PROD_MAX_DTS) return SRBD_E_INVALID;
+    for (int i = 1, j = 0; i < horizon; ++i) {  // srbd_pgg_contact_sequence's walk: the reference's IndexError
+        if (i >= lens[j]) ++j;
+        if (j >= n_dts) return SRBD_E_INVALID;
+    }
+    PggSeqConst sc = {};
+    for (int j = 0; j < n_dts; ++j) {
+        sc.dts[j] = dts[j];
+        sc.lens[j] = lens[j];
+    }
+    sc.n_dts = n_dts;
+    sc.H = horizon;
+    sc.stride = contact_stride;
+    hipLaunchKernelGGL(pgg_contact_sequence_kernel, dim3(blocks_of(num_envs)), dim3(PROD_BLOCK), 0,
+                       stream_of(hip_stream), d_pgg, num_envs, sc, d_contacts);
+    return launch_status();
+}
+
+extern "C" int srbd_prepare_state_device(int32_t num_envs, const double* d_state_in, const double* d_ref_in,
+                                         const float* d_current_contact, const float* d_previous_contact,
+                                         int32_t params_per_leg, int32_t num_params, float* d_best_params,
+                                         float* d_states, float* d_refs, void* hip_stream) {
+    if (!d_state_in || !d_ref_in || !d_current_contact || !d_previous_contact || !d_states || !d_refs ||
+        !envs_ok(num_envs))
+        return SRBD_E_INVALID;
+    if (d_best_params && (params_per_leg < 1 || (int64_t)4 * params_per_leg > num_params)) return SRBD_E_INVALID;
+    hipLaunchKernelGGL(prepare_state_kernel, dim3(blocks_of(num_envs)), dim3(PROD_BLOCK), 0, stream_of(hip_stream),
+                       num_envs, d_state_in, d_ref_in, d_current_contact, d_previous_contact, params_per_leg,
+                       num_params, d_best_params, d_states, d_refs);
+    return launch_status();
+}

@@ -209,6 +209,10 @@ SIGNATURES.update({
     "srbd_batch_clear_gait": (_I, [_P]),
     "srbd_batch_set_cost_terms": (_I, [_P, _FP, _F, _F]),
     "srbd_batch_step_device": (_I, [_P, C.POINTER(BatchDeviceIO), _P]),
+    # the device producers: device arrays as plain addresses, dts / lens host arrays
+    "srbd_pgg_run_device": (_I, [_P, _I, _D, _P, _P, _P]),
+    "srbd_pgg_contact_sequence_device": (_I, [_P, _I, _I, _DP, _IP, _I, _P, _I, _P]),
+    "srbd_prepare_state_device": (_I, [_I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
 })
 
 # srbd_time_launch kinds (include/srbd_mpc.h)
@@ -854,3 +858,145 @@ class BatchContext:
         self.check(lib.srbd_batch_step_device(self.h, C.byref(io), C.c_void_p(s.cuda_stream or 1)),
                    "srbd_batch_step_device")
         return out
+
+
+# ---------------------------------------------------------------------- device producers (include/srbd_mpc.h)
+PGG_BYTES = C.sizeof(SrbdPgg)
+MAX_ENVS = 4096
+MAX_DTS = 32
+
+
+def _device_tensors(specs):
+    """Check (name, tensor, shape, dtypes) entries the way BatchContext.step_device does -- type, dtype, shape,
+    contiguity, and only then the device, so a CPU tensor of the wrong shape is refused for its shape -- and return
+    the cuda device they share (the first entry's)."""
+    import torch
+
+    for name, t, shape, dtypes in specs:
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch tensor, got {type(t).__name__}")
+        if t.dtype not in dtypes:
+            raise ValueError(f"{name} must be {' or '.join(str(d) for d in dtypes)}, got {t.dtype}")
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    dev = specs[0][1].device
+    for name, t, _, _ in specs:
+        if t.device.type != "cuda":
+            raise ValueError(f"{name} must be on a cuda device, got {t.device}")
+        if t.device != dev:
+            raise ValueError(f"{name} must be on {dev}, got {t.device}")
+    return dev
+
+
+def _num_envs_of(pgg):
+    E = int(pgg.shape[0]) if hasattr(pgg, "shape") and len(pgg.shape) == 2 else 0
+    if not 1 <= E <= MAX_ENVS:
+        raise ValueError(f"the generator state must be (1..{MAX_ENVS}, {PGG_BYTES}) uint8, got "
+                         f"{tuple(getattr(pgg, 'shape', ()))}")
+    return E
+
+
+def _enqueue(dev, stream, alloc, call, what):
+    """Allocate the outputs on the stream that writes them, then make the C call with `dev` current."""
+    import torch
+
+    s = torch.cuda.current_stream(dev) if stream is None else stream
+    with torch.cuda.stream(s):
+        outs = alloc()
+    if torch.cuda.current_device() != dev.index:
+        with torch.cuda.device(dev):
+            rc = call(outs, C.c_void_p(s.cuda_stream))
+    else:
+        rc = call(outs, C.c_void_p(s.cuda_stream))  # handle 0: torch's default stream, the legacy null stream
+    if rc != OK:
+        raise RuntimeError(f"{what} failed ({rc})")
+    return outs
+
+
+def pgg_run_device(pgg, dt: float, step_freqs=None, out=None, stream=None):
+    """srbd_pgg_run_device: one ``run(dt)`` of every environment's generator, enqueued on ``stream`` (None: torch's
+    current stream) without a host synchronisation.  pgg (E, PGG_BYTES) uint8: the srbd_pgg structs, advanced in
+    place; step_freqs None (each struct's own step_freq) or (E,) float64; out None (allocated) or (E, 4) float32.
+    Returns the contact flags (E, 4)."""
+    import torch
+
+    E = _num_envs_of(pgg)
+    specs = [("pgg", pgg, (E, PGG_BYTES), (torch.uint8,))]
+    if step_freqs is not None:
+        specs.append(("step_freqs", step_freqs, (E,), (torch.float64,)))
+    if out is not None:
+        specs.append(("out", out, (E, 4), (torch.float32,)))
+    dev = _device_tensors(specs)
+    return _enqueue(
+        dev, stream, lambda: torch.empty((E, 4), dtype=torch.float32, device=dev) if out is None else out,
+        lambda o, s: lib.srbd_pgg_run_device(pgg.data_ptr(), E, float(dt),
+                                             None if step_freqs is None else step_freqs.data_ptr(), o.data_ptr(), s),
+        "srbd_pgg_run_device")
+
+
+def pgg_contact_sequence_device(pgg, horizon: int, dts, lens, out=None, stream=None):
+    """srbd_pgg_contact_sequence_device: every environment's look-ahead contact sequence, enqueued on ``stream``.
+    pgg as in ``pgg_run_device`` (left as found, FULL_STANCE environments reset); dts / lens: host sequences shared by
+    the environments; out None (an (E, 4, horizon) tensor is allocated) or (E, 4, >=horizon) float32, whose first
+    ``horizon`` columns are written.  Returns the tensor written."""
+    import torch
+
+    E, H = _num_envs_of(pgg), int(horizon)
+    if not 1 <= H <= MAX_HORIZON:
+        raise ValueError(f"horizon must be 1..{MAX_HORIZON}, got {H}")
+    dts = np.ascontiguousarray(dts, dtype=np.float64).reshape(-1)
+    lens = np.ascontiguousarray(lens, dtype=np.int32).reshape(-1)
+    n = min(dts.size, lens.size)
+    if not 1 <= n <= MAX_DTS:
+        raise ValueError(f"dts / lens must have 1..{MAX_DTS} entries, got {dts.size} / {lens.size}")
+    specs = [("pgg", pgg, (E, PGG_BYTES), (torch.uint8,))]
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or out.dim() != 3 or out.shape[2] < H:
+            raise ValueError(f"out must be a torch tensor of shape ({E}, 4, >={H})")
+        specs.append(("out", out, (E, 4, int(out.shape[2])), (torch.float32,)))
+    dev = _device_tensors(specs)
+    try:
+        return _enqueue(
+            dev, stream, lambda: torch.empty((E, 4, H), dtype=torch.float32, device=dev) if out is None else out,
+            lambda o, s: lib.srbd_pgg_contact_sequence_device(pgg.data_ptr(), E, H, dptr(dts), iptr(lens), n,
+                                                              o.data_ptr(), int(o.shape[2]), s),
+            "srbd_pgg_contact_sequence_device")
+    except RuntimeError as err:
+        if f"({E_INVALID})" in str(err):  # every other argument was checked above
+            raise IndexError("contact sequence lengths run past the dts before the horizon ends") from None
+        raise
+
+
+def prepare_state_device(state_in, ref_in, current_contact, previous_contact, params_per_leg: int = 0, best=None,
+                         stream=None):
+    """srbd_prepare_state_device: prepare_state_and_reference of every environment, enqueued on ``stream``.
+    state_in / ref_in (E, 24) float64, current_contact / previous_contact (E, 4) float32; best None or the (E, P)
+    float32 warm starts, whose lift-off legs (``params_per_leg`` entries each) are zeroed in place.  Returns
+    (states, refs), (E, 24) float32: what ``step_device`` takes."""
+    import torch
+
+    E = int(state_in.shape[0]) if isinstance(state_in, torch.Tensor) and state_in.dim() == 2 else 0
+    if not 1 <= E <= MAX_ENVS:
+        raise ValueError(f"state_in must be a torch tensor of shape (1..{MAX_ENVS}, 24)")
+    specs = [("state_in", state_in, (E, 24), (torch.float64,)), ("ref_in", ref_in, (E, 24), (torch.float64,)),
+             ("current_contact", current_contact, (E, 4), (torch.float32,)),
+             ("previous_contact", previous_contact, (E, 4), (torch.float32,))]
+    P = 0
+    if best is not None:
+        if not isinstance(best, torch.Tensor) or best.dim() != 2:
+            raise ValueError(f"best must be a torch tensor of shape ({E}, P)")
+        P = int(best.shape[1])
+        if params_per_leg < 1 or 4 * int(params_per_leg) > P:
+            raise ValueError(f"params_per_leg must be 1..P / 4 (P = {P}), got {params_per_leg}")
+        specs.append(("best", best, (E, P), (torch.float32,)))
+    dev = _device_tensors(specs)
+    return _enqueue(
+        dev, stream, lambda: (torch.empty((E, 24), dtype=torch.float32, device=dev),
+                              torch.empty((E, 24), dtype=torch.float32, device=dev)),
+        lambda o, s: lib.srbd_prepare_state_device(E, state_in.data_ptr(), ref_in.data_ptr(),
+                                                   current_contact.data_ptr(), previous_contact.data_ptr(),
+                                                   int(params_per_leg), P, None if best is None else best.data_ptr(),
+                                                   o[0].data_ptr(), o[1].data_ptr(), s),
+        "srbd_prepare_state_device")

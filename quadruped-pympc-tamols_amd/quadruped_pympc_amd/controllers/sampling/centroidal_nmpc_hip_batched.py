@@ -188,6 +188,30 @@ class Batched_Sampling_MPC:
         self.best_control_parameters = best
         return states, refs
 
+    def prepare_state_and_reference_device(self, state_in, ref_in, current_contacts, previous_contacts, stream=None,
+                                           *, best_control_parameters=None):
+        """``prepare_state_and_reference`` on torch tensors of one cuda device (``srbd_prepare_state_device``),
+        enqueued on ``stream`` (None: torch's current stream) without a host synchronisation.
+
+        state_in (E, 24) float64: per environment [position, linear_velocity, orientation, angular_velocity,
+        foot_FL, foot_FR, foot_RL, foot_RR]; ref_in (E, 24) float64: [ref_position, ref_linear_velocity,
+        ref_orientation, ref_angular_velocity, ref_foot_FL..RR] (a float32 simulator state is widened exactly by
+        ``.double()``).  current_contacts, previous_contacts (E, 4) float32: ``contact_sequences[:, :, 0]`` made
+        contiguous, and the one of the previous step.  Returns (states, refs), (E, 24) float32: the host method's
+        float64 outputs rounded as the step stages them, ready for ``compute_control_device``.
+
+        The warm start: the device loop's warm start is the tensor the caller hands to ``compute_control_device``,
+        which updates it in place, so the caller passes that same (E, P) float32 tensor here as
+        ``best_control_parameters`` and the lift-off legs are zeroed in it in place.  The controller keeps no device
+        copy of its own, and the host attribute ``self.best_control_parameters`` is not touched.  None: no zeroing.
+
+        ``shift_solution`` configurations are refused: the device form restates the unshifted path only."""
+        if self._one._cfg.mpc_params["shift_solution"]:
+            raise NotImplementedError("prepare_state_and_reference_device: shift_solution has no device form")
+        return _lib.prepare_state_device(state_in, ref_in, current_contacts, previous_contacts,
+                                         self.num_control_parameters_single_leg, best_control_parameters,
+                                         stream=stream)
+
     def reset(self):
         print("Resetting the controller")
 

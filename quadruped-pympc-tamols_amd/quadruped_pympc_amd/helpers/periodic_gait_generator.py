@@ -112,3 +112,145 @@ class PeriodicGaitGenerator:
     def restore_previous_gait(self):
         self.gait_type = self.previous_gait_type
         self.reset()
+
+
+class BatchedPeriodicGaitGenerator:
+    """``num_envs`` periodic gait generators whose state lives on the device (``srbd_pgg_run_device``,
+    ``srbd_pgg_contact_sequence_device``, include/srbd_mpc.h): the producer of the (E, 4, H) contact sequences
+    ``BatchContext.step_device`` consumes, with no host round trip.
+
+    Environment ``e`` behaves as a ``PeriodicGaitGenerator(duty_factor[e], step_freq[e], gait_type[e], horizon)``
+    that received the same calls: its state keeps the host struct's bytes and its contact flags are the host's,
+    as float32.  ``duty_factor``, ``step_freq`` and ``gait_type`` are scalars or length-E sequences; the gait types
+    are fixed at construction.  The state is one (E, sizeof(srbd_pgg)) uint8 tensor, ``state``, built from host
+    ``srbd_pgg_init`` structs; ``phase_signal`` (E, 4) float64 and ``init`` (E, 4) int32 are views of it.  Every
+    method enqueues on ``stream`` (None: torch's current stream) and does not wait for the device, except
+    ``state_dict``.  A FULL_STANCE environment's sequence is H columns of ones (the step reads no more), not the
+    host class's 2 H."""
+
+    n_contact = 4
+
+    def __init__(self, num_envs, duty_factor, step_freq, gait_type, horizon, device=None):
+        E = int(num_envs)
+        if not 1 <= E <= _lib.MAX_ENVS:
+            raise ValueError(f"num_envs must be 1..{_lib.MAX_ENVS}, got {num_envs}")
+        if not 1 <= int(horizon) <= _lib.MAX_HORIZON:
+            raise ValueError(f"horizon must be 1..{_lib.MAX_HORIZON}, got {horizon}")
+
+        def per_env(name, v, dtype):
+            a = np.asarray([getattr(x, "value", x) for x in v] if isinstance(v, (list, tuple)) else
+                           getattr(v, "value", v), dtype=dtype)
+            if a.ndim == 0:
+                return np.full(E, a, dtype=dtype)
+            if a.shape != (E,):
+                raise ValueError(f"{name} must be a scalar or have {E} entries, got shape {a.shape}")
+            return a
+
+        duty = per_env("duty_factor", duty_factor, np.float64)
+        freq = per_env("step_freq", step_freq, np.float64)
+        gait = per_env("gait_type", gait_type, np.int32)
+        self.num_envs, self.horizon = E, int(horizon)
+        host = (_lib.SrbdPgg * E)()
+        for e in range(E):
+            _check(_lib.lib.srbd_pgg_init(C.byref(host[e]), int(gait[e]), float(duty[e]), float(freq[e]),
+                                          self.horizon), "srbd_pgg_init")
+        self._seq_key = None
+        # everything above is host work; the upload is the first use of the device
+        import torch
+
+        if not torch.cuda.is_available():
+            raise RuntimeError("BatchedPeriodicGaitGenerator: no HIP device visible (the generator state lives in "
+                               "device memory; PeriodicGaitGenerator is the host form)")
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.state = torch.empty((E, _lib.PGG_BYTES), dtype=torch.uint8, device=self.device)
+        self.load_state_dict(host)
+
+    def _views(self):
+        import torch
+
+        f = _lib.SrbdPgg
+        d, i = self.state.view(torch.float64), self.state.view(torch.int32)
+        return (d[:, f.phase_signal.offset // 8:f.phase_signal.offset // 8 + 4],
+                d[:, f.phase_offset.offset // 8:f.phase_offset.offset // 8 + 4],
+                i[:, f.init.offset // 4:f.init.offset // 4 + 4])
+
+    @property
+    def phase_signal(self):
+        """(E, 4) float64 view of the state's phase signals."""
+        return self._views()[0]
+
+    @property
+    def phase_offset(self):
+        """(E, 4) float64 view of the state's phase offsets."""
+        return self._views()[1]
+
+    @property
+    def init(self):
+        """(E, 4) int32 view of the state's start-up holds."""
+        return self._views()[2]
+
+    def _on(self, stream):
+        import torch
+
+        return torch.cuda.stream(torch.cuda.current_stream(self.device) if stream is None else stream)
+
+    def state_dict(self):
+        """The host structs, a ``(SrbdPgg * E)`` ctypes array (waits for the device): for checkpoints and tests.
+        ``bytes()`` of it is a plain byte string; ``load_state_dict`` takes either."""
+        raw = self.state.cpu().numpy().tobytes()
+        return (_lib.SrbdPgg * self.num_envs).from_buffer_copy(raw)
+
+    def load_state_dict(self, structs, stream=None):
+        import torch
+
+        raw = np.frombuffer(bytes(structs), dtype=np.uint8)
+        if raw.size != self.num_envs * _lib.PGG_BYTES:
+            raise ValueError(f"{self.num_envs} srbd_pgg structs expected ({self.num_envs * _lib.PGG_BYTES} bytes), got "
+                             f"{raw.size} bytes")
+        with self._on(stream):
+            self.state.copy_(torch.from_numpy(raw.reshape(self.num_envs, _lib.PGG_BYTES).copy()))
+
+    def reset(self, stream=None):
+        """``PeriodicGaitGenerator.reset`` of every environment: the phases back to the gaits' offsets, the holds
+        cleared."""
+        ph, off, ini = self._views()
+        with self._on(stream):
+            ph.copy_(off)
+            ini.zero_()
+
+    def set_phase_signal(self, phase_signal, init=None, stream=None):
+        """``set_phase_signal`` of every environment: phase_signal (E, 4) float64 values (array or tensor); init None
+        (the holds are cleared) or (E, 4), stored as ``init != 0``."""
+        import torch
+
+        ph, _, ini = self._views()
+        src = torch.as_tensor(phase_signal, dtype=torch.float64)
+        if tuple(src.shape) != (self.num_envs, 4):
+            raise ValueError(f"phase_signal must be ({self.num_envs}, 4), got {tuple(src.shape)}")
+        flags = None if init is None else torch.as_tensor(init)
+        if flags is not None and tuple(flags.shape) != (self.num_envs, 4):
+            raise ValueError(f"init must be ({self.num_envs}, 4), got {tuple(flags.shape)}")
+        with self._on(stream):
+            ph.copy_(src)
+            if flags is None:
+                ini.zero_()
+            else:
+                ini.copy_((flags != 0).to(torch.int32))
+
+    def run(self, dt, step_freqs=None, stream=None):
+        """``run(dt, step_freqs[e])`` of every environment -> the contact flags, (E, 4) float32.  step_freqs None:
+        each environment's own step frequency; else an (E,) float64 tensor."""
+        return _lib.pgg_run_device(self.state, dt, step_freqs, stream=stream)
+
+    def compute_contact_sequence(self, contact_sequence_dts, contact_sequence_lenghts, out=None, stream=None):
+        """Every environment's look-ahead sequence -> (E, 4, H) float32, or ``out`` (E, 4, >=H) with its first H
+        columns written: what ``step_device`` takes as ``contacts``.  The dts and lengths are host sequences shared
+        by the environments; IndexError where the reference's loop would run past them."""
+        key = (np.asarray(contact_sequence_dts, dtype=np.float64).tobytes(),
+               np.asarray(contact_sequence_lenghts, dtype=np.int32).tobytes())
+        if key != self._seq_key:  # the control loop passes the same arrays every step
+            self._dts = np.frombuffer(key[0], dtype=np.float64).copy()
+            self._lens = np.frombuffer(key[1], dtype=np.int32).copy()
+            self._seq_key = key
+        return _lib.pgg_contact_sequence_device(self.state, self.horizon, self._dts, self._lens, out=out,
+                                                stream=stream)
