@@ -629,6 +629,62 @@ int srbd_prepare_state_device(int32_t num_envs, const double* d_state_in, const 
                               int32_t num_params, float* d_best_params /* or NULL */, float* d_states, float* d_refs,
                               void* hip_stream);
 
+/* The foothold search of the device-resident loop: TAMOLS (srbd_tamols_run / srbd_tamols_run_terrain above, i.e.
+ * VisualFootholdAdaptation.compute_adaptation, strategy 'tamols', visual_foothold_adaptation.py:153-231 with its
+ * helpers :261-714, and the heightmap raycast of wb_interface.py:233-234) for num_envs environments in one launch,
+ * device in and device out, so that generator.run -> footholds -> prepare -> srbd_batch_step_device never leaves
+ * the GPU.  Stateless: no context, no allocation.
+ *   Forms: terrain != NULL raycasts every leg's rows x cols patch from the one scene all environments share, centred
+ *   at the leg's seed and yawed by yaws[e] (what srbd_tamols_run_terrain does per call); terrain == NULL reads the
+ *   caller's patches from `heightmaps` (what srbd_tamols_run does).  params, rows, cols, the spacings and ray_z are
+ *   shared by the environments; NULL forward_vel / base_pos / contact / feet mean what they mean in srbd_tamols_run,
+ *   for every environment.  contact is float32 as srbd_pgg_run_device writes it (stance iff 1.0f).
+ *   Outputs per environment as srbd_tamols_run's; an infeasible leg (valid 0, NaN box) returns the seed at its
+ *   terrain height (VFA:223-228).  ref, when given, is srbd_prepare_state_device's d_ref_in: entries 12..23 of row e
+ *   (ref_foot_FL..RR) receive environment e's footholds, entries 0..11 are not written.
+ *   Equivalence: for environment e every output holds the bytes the single-environment call returns for that
+ *   environment's inputs (NaNs position for position); the kernel runs the single kernel's device functions, float64
+ *   in the same order.  Environments are independent.  One caveat, terrain form: the single call forms cos / sin of
+ *   its yaw with the host's libm, this call on the device, correctly rounded (csrc/yaw_sincos.h;
+ *   srbd_selftest_yaw_sincos is its host twin).  For a yaw where libm's value is not the correctly rounded one
+ *   (glibc 2.35: about 3 in 1000 yaws, by one ulp) the patch coordinates, and with them the footholds, differ in
+ *   the last place.
+ *   Enqueue contract (the producers' above): exactly one launch on hip_stream, no synchronising HIP call, no device
+ *   memory touched from the host; the stream handle is read as srbd_prepare_state_device reads it; every pointer is
+ *   memory of the current device, which must be the terrain's; no event and no ordering rule.  The terrain must
+ *   outlive the launch.
+ *   SRBD_E_INVALID (before any HIP call): a NULL params, io or required pointer (seeds, hips, footholds, boxes,
+ *   valid); num_envs outside 1..4096; rows or cols below 1 or rows * cols above 320; terrain form without yaws or with
+ *   a dist_x or dist_y that is not positive (the lattice patch, the only one the plugin API produces); patch form
+ *   without heightmaps; heightmaps_out in patch form.  A failed launch: SRBD_E_HIP, or SRBD_E_NODEVICE where no device
+ *   exists. */
+typedef struct srbd_tamols_batch_io {
+    /* inputs: device memory, float64 unless noted; E = num_envs */
+    const double* seeds;        /* E x 4 x 3 */
+    const double* hips;         /* E x 4 x 3 */
+    const double* forward_vel;  /* E x 3, or NULL */
+    const double* base_pos;     /* E x 3, or NULL */
+    const float* contact;       /* E x 4 float32: stance iff == 1.0f; NULL -> all swing */
+    const double* feet;         /* E x 4 x 3, or NULL */
+    const double* yaws;         /* E: terrain form only */
+    const double* heightmaps;   /* E x 4 x rows x cols x 3: patch form only (terrain == NULL) */
+    int32_t rows, cols;
+    double dist_x, dist_y, ray_z; /* terrain form */
+    /* outputs: device memory */
+    double* footholds;          /* E x 4 x 3 */
+    double* boxes;              /* E x 4 x 2 x 3; NaN for an infeasible leg */
+    int32_t* valid;             /* E x 4 */
+    double* seed_heights;       /* E x 4, or NULL */
+    double* scores;             /* E x 4 x rows*cols, or NULL */
+    double* heightmaps_out;     /* E x 4 x rows x cols x 3, terrain form, or NULL */
+    double* ref;                /* E x 24 or NULL: entries 12..23 of row e receive environment e's footholds */
+} srbd_tamols_batch_io;
+int srbd_tamols_batch_device(srbd_terrain* terrain /* NULL: patch form */, const srbd_tamols_params* params,
+                             int32_t num_envs, const srbd_tamols_batch_io* io, void* hip_stream);
+/* Self-test: out_cs[2 i], out_cs[2 i + 1] = the cos and sin srbd_tamols_batch_device's kernel forms of yaws[i],
+ * evaluated on the host by the same function (plain float64 operations and fma: the same bits on both sides). */
+int srbd_selftest_yaw_sincos(const double* yaws, int32_t n, double* out_cs);
+
 /* Diagnostic: enable != 0 stamps the phases of the following TAMOLS calls; out_us[5] (may be NULL)
  * receives the last call's mean per-block durations of (patch, queries, scores, slice argmin + count)
  * and the span from the first block's start to the last leg's end, in us.  enable == 0 turns it off. */

@@ -302,4 +302,24 @@ struct TamolsJob {
 void launch_tamols_fused(const TamolsJob& j, hipStream_t s, const StepInputK* ksi = nullptr);
 int tamols_prepare();  // once per context: the staged scene's dynamic LDS limit (0 on success)
 
+// The batched, device-resident search (srbd_tamols_batch_device; tamols_batch_kernel): one block per
+// (environment, leg), every array a device pointer of the caller's, E rows each (include/srbd_mpc.h
+// srbd_tamols_batch_io).  Only the values all environments share travel in the kernel argument.
+constexpr int TAMOLS_BATCH_THREADS = 256;
+constexpr int TAMOLS_BATCH_CULL = 128;  // culled primitives kept in LDS per patch; past it, the whole scene is walked
+struct TamolsBatchJob {
+    const double *seeds, *hips, *vel, *base, *feet, *yaws, *hm;  // vel, base, feet may be NULL; yaws or hm by form
+    const float* contact;                                         // E x 4 or NULL
+    double *footholds, *boxes, *seed_heights, *scores, *hm_out, *ref;
+    int32_t* valid;
+    srbd_tamols_params p;
+    TerrainDev t;
+    int E, rows, cols;
+    int use_terrain;  // 1: raycast from `t` (centres = the seeds, yaws[e]), 0: read `hm`
+    int lattice;      // use_terrain with finite spacings: the lattice queries, for a finite yaw cos / sin
+    double dist_x, dist_y, inv_dx, inv_dy, ray_z;
+};
+size_t tamols_batch_lds(int rows, int cols);  // dynamic LDS bytes of one block
+void launch_tamols_batch(const TamolsBatchJob& j, hipStream_t s);
+
 }  // namespace srbd

@@ -11,11 +11,15 @@
 //   prepare_state_kernel         srbd_prepare_state         NMPC:563-627 (no solution shift)
 // Legs are independent in all three, so one lane owns one (environment, leg): lane t of the grid is leg t & 3 of
 // environment t >> 2, 64 environments per 256-thread block, the lanes past 4 E idle.  No LDS, no cross-lane traffic.
+// srbd_tamols_batch_device, the loop's foothold search, is validated and enqueued here too; its kernel lives with the
+// single-environment one (tamols_kernel.hip tamols_batch_kernel), whose device functions it runs.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
 #include "../../include/srbd_host.h"
 #include "../../include/srbd_mpc.h"
+#include "srbd_launch.h"
+#include "yaw_sincos.h"
 
 namespace srbd {
 
@@ -205,4 +209,57 @@ extern "C" int srbd_prepare_state_device(int32_t num_envs, const double* d_state
                        num_envs, d_state_in, d_ref_in, d_current_contact, d_previous_contact, params_per_leg,
                        num_params, d_best_params, d_states, d_refs);
     return launch_status();
+}
+
+extern "C" int srbd_tamols_batch_device(srbd_terrain* terrain, const srbd_tamols_params* params, int32_t num_envs,
+                                        const srbd_tamols_batch_io* io, void* hip_stream) {
+    if (!params || !io || !io->seeds || !io->hips || !io->footholds || !io->boxes || !io->valid || !envs_ok(num_envs))
+        return SRBD_E_INVALID;
+    if (io->rows < 1 || io->cols < 1 || (int64_t)io->rows * io->cols > TAMOLS_MAXCAND) return SRBD_E_INVALID;
+    if (terrain) {
+        if (!io->yaws || !(io->dist_x > 0.0) || !(io->dist_y > 0.0)) return SRBD_E_INVALID;
+    } else if (!io->heightmaps || io->heightmaps_out) {
+        return SRBD_E_INVALID;
+    }
+    TamolsBatchJob j = {};
+    j.seeds = io->seeds;
+    j.hips = io->hips;
+    j.vel = io->forward_vel;
+    j.base = io->base_pos;
+    j.feet = io->feet;
+    j.contact = io->contact;
+    j.footholds = io->footholds;
+    j.boxes = io->boxes;
+    j.valid = io->valid;
+    j.seed_heights = io->seed_heights;
+    j.scores = io->scores;
+    j.ref = io->ref;
+    j.p = *params;
+    j.E = num_envs;
+    j.rows = io->rows;
+    j.cols = io->cols;
+    if (terrain) {
+        int dev = -1;
+        if (hipGetDevice(&dev) == hipSuccess && dev != terrain->device) return SRBD_E_INVALID;
+        j.use_terrain = 1;
+        j.t = terrain->dev;
+        j.yaws = io->yaws;
+        j.hm_out = io->heightmaps_out;
+        j.dist_x = io->dist_x;
+        j.dist_y = io->dist_y;
+        j.inv_dx = 1.0 / io->dist_x;  // as tamols_terrain_job (srbd_api.hip) forms them
+        j.inv_dy = 1.0 / io->dist_y;
+        j.ray_z = io->ray_z;
+        j.lattice = std::isfinite(io->dist_x) && std::isfinite(io->dist_y);
+    } else {
+        j.hm = io->heightmaps;
+    }
+    launch_tamols_batch(j, stream_of(hip_stream));
+    return launch_status();
+}
+
+extern "C" int srbd_selftest_yaw_sincos(const double* yaws, int32_t n, double* out_cs) {
+    if (!yaws || !out_cs || n < 0) return SRBD_E_INVALID;
+    for (int32_t i = 0; i < n; ++i) yaw_sincos(yaws[i], out_cs[2 * i], out_cs[2 * i + 1]);
+    return SRBD_OK;
 }

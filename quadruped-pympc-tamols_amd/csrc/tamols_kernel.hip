@@ -19,6 +19,7 @@
 // fence and flag behind the data).  A raycast lattice patch takes one block per leg (TamolsJob::lattice).
 // float64 keeps the host oracle's decisions (reach bounds, argmin) bit-for-bit comparable.
 #include "terrain_ray.h"
+#include "yaw_sincos.h"
 
 namespace srbd {
 
@@ -722,6 +723,243 @@ void launch_tamols_fused(const TamolsJob& j, hipStream_t s, const StepInputK* ks
         hipLaunchKernelGGL(tamols_fused_kernel<true>, dim3(nb, 5), dim3(TAMOLS_THREADS), smem, s, *ksi, j);
     else
         hipLaunchKernelGGL(tamols_fused_kernel<false>, dim3(nb, 4), dim3(TAMOLS_THREADS), smem, s, KsNone{0}, j);
+}
+
+// ------------------------------------------------------------------ the batched, device-resident search
+// srbd_tamols_batch_device: grid (4 legs, E environments), TAMOLS_BATCH_THREADS threads; block (leg, e) owns leg
+// `leg` of environment e from its patch to its outputs, so nothing crosses blocks: no partials, no counters, no
+// tagged words, no wait.  The stages are tamols_fused_kernel's with one block per leg, through the same device
+// functions (every float64 operation and its order the same, so the outputs are the single-environment call's
+// bytes); what differs is the throughput shape: one lane per ray and per query, a block of four waves, and LDS
+// sized from the patch (dynamic: px, py, pz, sc of rows * cols doubles and the query stage nn), so several
+// blocks share a CU.  The environment's TamolsArgs / TamolsJob (what the device functions read) is assembled in LDS
+// from the caller's per-environment arrays; the yaw's cos / sin by yaw_sincos.h (two lanes of wave 2).
+__global__ void __launch_bounds__(TAMOLS_BATCH_THREADS) tamols_batch_kernel(const TamolsBatchJob bj) {
+    extern __shared__ double bsm[];
+    __shared__ TamolsJob j;
+    __shared__ int pn;
+    __shared__ double wbs[TAMOLS_BATCH_THREADS / 64];
+    __shared__ int wbi[TAMOLS_BATCH_THREADS / 64];
+    constexpr int T = TAMOLS_BATCH_THREADS;
+    const int leg = blockIdx.x, e = blockIdx.y, tid = threadIdx.x;
+    const int nc = bj.rows * bj.cols, nq = nc * TAMOLS_NQ + 1;
+    const size_t el = (size_t)e * 4 + leg;
+    double* px = bsm;
+    double* py = px + nc;
+    double* pz = py + nc;
+    double* sc = pz + nc;
+    double* nn = sc + nc;  // nq doubles, or the culled primitives before phase A (tamols_batch_lds)
+
+    // ---- the environment's arguments
+    TamolsArgs& a = j.a;
+    if (tid < 12) {
+        a.seeds[tid] = bj.seeds[12 * (size_t)e + tid];
+        a.hips[tid] = bj.hips[12 * (size_t)e + tid];
+        a.feet[tid] = bj.feet ? bj.feet[12 * (size_t)e + tid] : 0.0;
+    } else if (tid < 15) {
+        const int k = tid - 12;
+        a.vel[k] = bj.vel ? bj.vel[3 * (size_t)e + k] : 0.0;
+        a.base[k] = bj.base ? bj.base[3 * (size_t)e + k] : 0.0;
+    } else if (tid < 19) {
+        const int k = tid - 15;
+        a.contact[k] = bj.contact ? (bj.contact[4 * (size_t)e + k] == 1.0f ? 1 : 0) : 0;
+    } else if (tid == 19) {
+        a.rows = bj.rows;
+        a.cols = bj.cols;
+        a.ncand = nc;
+        a.has_vel = bj.vel != nullptr;
+        a.has_base = bj.base != nullptr;
+        a.has_feet = bj.feet != nullptr;
+        j.rows = bj.rows;
+        j.cols = bj.cols;
+        j.dist_x = bj.dist_x;
+        j.dist_y = bj.dist_y;
+        j.inv_dx = bj.inv_dx;
+        j.inv_dy = bj.inv_dy;
+        j.ray_z = bj.ray_z;
+        pn = 0;
+    } else if (tid == 64) {
+        a.p = bj.p;
+    }
+    if (bj.use_terrain && tid >= 128 && tid < 130) {  // a wave of their own: the sine's series and the cosine's
+        const double yaw = bj.yaws[e];
+        DD r;
+        const int q = yaw_reduce(yaw, r);
+        const double v = yaw_series_value(r, tid == 129);
+        const double sv = __shfl(v, 0, 64), cv = __shfl(v, 1, 64);
+        if (tid == 128) {
+            double c, s;
+            yaw_finish(yaw, q, sv, cv, c, s);
+            j.yaw_c = c;
+            j.yaw_s = s;
+            // the lattice queries under the single call's condition (tamols_terrain_job), else every point scanned
+            j.lattice = bj.lattice && isfinite(c) && isfinite(s);
+        }
+    } else if (!bj.use_terrain && tid == 128) {
+        j.lattice = 0;
+    }
+    __syncthreads();
+
+    // ---- patch -> LDS
+    if (bj.use_terrain) {
+        const TerrainDev& t = bj.t;
+        const int np = t.nprims;
+        // the primitives that can touch this patch, culled from global memory into a compact copy (tamols_fused_kernel's
+        // test); a ray's result is a maximum over primitives, so the copy's order (atomic slots) does not matter.  Past
+        // TAMOLS_BATCH_CULL of them every ray walks the whole scene from global memory.
+        srbd_terrain_prim* cp = reinterpret_cast<srbd_terrain_prim*>(nn);
+        double* ccs = nn + TAMOLS_BATCH_CULL * (sizeof(srbd_terrain_prim) / sizeof(double));
+        if (np > 0) {
+            const double hx = 0.5 * (double)(bj.rows - 1) * fabs(bj.dist_x), hy = 0.5 * (double)(bj.cols - 1) * fabs(bj.dist_y);
+            const double rp = sqrt(hx * hx + hy * hy);
+            for (int q = tid; q < np; q += T) {
+                const srbd_terrain_prim pr = t.prims[q];
+                const bool box = pr.type == SRBD_PRIM_BOX;
+                const double r = box ? fabs(pr.a) + fabs(pr.b) : fabs(pr.a);
+                const double dx = pr.cx - a.seeds[3 * leg], dy = pr.cy - a.seeds[3 * leg + 1];
+                const double lim = (r + rp) * 1.000001 + 1e-9;
+                if (!(dx * dx + dy * dy > lim * lim)) {  // NaN / inf geometry is kept: the walk decides
+                    const int slot = atomicAdd(&pn, 1);
+                    if (slot < TAMOLS_BATCH_CULL) {
+                        cp[slot] = pr;
+                        ccs[2 * slot] = box ? t.cs[2 * q] : 0.0;
+                        ccs[2 * slot + 1] = box ? t.cs[2 * q + 1] : 0.0;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+        const int nlist = np > 0 ? pn : 0;
+        const bool listed = nlist <= TAMOLS_BATCH_CULL;
+        double* hmo = bj.hm_out ? bj.hm_out + 3 * el * nc : nullptr;
+        for (int i = tid; i < nc; i += T) {  // one lane per ray
+            double x, y, best = -INFINITY;
+            int hit = 0;
+            ray_xy(a.seeds[3 * leg], a.seeds[3 * leg + 1], j.yaw_c, j.yaw_s, bj.rows, bj.cols, i / bj.cols, i % bj.cols,
+                   bj.dist_x, bj.dist_y, x, y);
+            ray_walk_fields(t, x, y, bj.ray_z, best, hit);
+            if (listed)
+                ray_walk_prims(cp, ccs, 0, nlist, x, y, bj.ray_z, best, hit);
+            else
+                ray_walk_prims(t.prims, t.cs, 0, np, x, y, bj.ray_z, best, hit);
+            const double z = hit ? best : t.miss_z;
+            px[i] = x;
+            py[i] = y;
+            pz[i] = z;
+            if (hmo) {
+                hmo[3 * i] = x;
+                hmo[3 * i + 1] = y;
+                hmo[3 * i + 2] = z;
+            }
+        }
+    } else {
+        const double* hm = bj.hm + 3 * el * nc;
+        for (int i = tid; i < nc; i += T) {
+            px[i] = hm[3 * i];
+            py[i] = hm[3 * i + 1];
+            pz[i] = hm[3 * i + 2];
+        }
+    }
+    __syncthreads();  // the patch is whole; the culled copy in nn is done with
+
+    // ---- phase A: the 19 nc + 1 queries, one lane each (sample-major over the candidates, so a wave's lanes mostly
+    // share tamols_query_point's branch); nn keeps the (candidate, sample) layout, the seed's query last
+    if (j.lattice) {
+        for (int u = tid; u < nq; u += T) {
+            const int q = u < nq - 1 ? u / nc : 0, c = u < nq - 1 ? u - q * nc : 0;
+            const int t = u < nq - 1 ? c * TAMOLS_NQ + q : nq - 1;
+            nn[t] = tamols_query_lattice(j, leg, t, px, py, pz) + 0.02;
+        }
+    } else {  // the whole patch in index order, strict <: the first nearest point wins
+        for (int u = tid; u < nq; u += T) {
+            const int q = u < nq - 1 ? u / nc : 0, c = u < nq - 1 ? u - q * nc : 0;
+            const int t = u < nq - 1 ? c * TAMOLS_NQ + q : nq - 1;
+            double bd = INFINITY, bh = 0.0;
+            tamols_query_part(a, leg, t, px, py, pz, 0, nc, bd, bh);
+            nn[t] = bh + 0.02;
+        }
+    }
+    __syncthreads();
+
+    // ---- phase B: one lane per candidate
+    double* sco = bj.scores ? bj.scores + el * nc : nullptr;
+    for (int c = tid; c < nc; c += T) {
+        const double s = tamols_score(a, leg, px[c], py[c], nn + c * TAMOLS_NQ);
+        sc[c] = s;
+        if (sco) sco[c] = s;
+    }
+    __syncthreads();
+
+    // ---- phase C: (score, index) of the scores < INFINITY, the lower index on equal scores -- the first minimum of
+    // the sequential strict-< scan (NaN and INFINITY never win: no candidate)
+    double bs = INFINITY;
+    int bi = 0x7fffffff;
+    for (int c = tid; c < nc; c += T)
+        if (sc[c] < bs) {  // strided and increasing: a later equal score never replaces
+            bs = sc[c];
+            bi = c;
+        }
+    for (int m = 32; m >= 1; m >>= 1) {
+        const double os = __shfl_xor(bs, m, 64);
+        const int oi = __shfl_xor(bi, m, 64);
+        if (os < bs || (os == bs && oi < bi)) {
+            bs = os;
+            bi = oi;
+        }
+    }
+    if ((tid & 63) == 0) {
+        wbs[tid >> 6] = bs;
+        wbi[tid >> 6] = bi;
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    for (int w = 1; w < T / 64; ++w)
+        if (wbs[w] < bs || (wbs[w] == bs && wbi[w] < bi)) {
+            bs = wbs[w];
+            bi = wbi[w];
+        }
+
+    // ---- the leg's outputs (tamols_leg_out's values) as plain stores
+    const srbd_tamols_params& p = a.p;
+    const double seedh = nn[nq - 1];
+    double f[3], b[6];
+    int valid;
+    if (bs < INFINITY) {  // VFA:193-222
+        f[0] = px[bi];
+        f[1] = py[bi];
+        f[2] = nn[bi * TAMOLS_NQ] + 0.005;
+        b[0] = f[0] - p.box_dx;
+        b[1] = f[1] - p.box_dy;
+        b[2] = f[2];
+        b[3] = f[0] + p.box_dx;
+        b[4] = f[1] + p.box_dy;
+        b[5] = f[2];
+        valid = 1;
+    } else {  // VFA:223-228: no feasible candidate -> the seed at its terrain height
+        f[0] = a.seeds[3 * leg];
+        f[1] = a.seeds[3 * leg + 1];
+        f[2] = seedh;
+        for (int k = 0; k < 6; ++k) b[k] = NAN;
+        valid = 0;
+    }
+    for (int k = 0; k < 3; ++k) bj.footholds[3 * el + k] = f[k];
+    for (int k = 0; k < 6; ++k) bj.boxes[6 * el + k] = b[k];
+    bj.valid[el] = valid;
+    if (bj.seed_heights) bj.seed_heights[el] = seedh;
+    if (bj.ref)
+        for (int k = 0; k < 3; ++k) bj.ref[24 * (size_t)e + 12 + 3 * leg + k] = f[k];
+}
+
+size_t tamols_batch_lds(int rows, int cols) {
+    const size_t nc = (size_t)rows * cols;
+    const size_t cull = TAMOLS_BATCH_CULL * (sizeof(srbd_terrain_prim) / sizeof(double) + 2);
+    const size_t nq = nc * TAMOLS_NQ + 1;
+    return sizeof(double) * (4 * nc + (nq > cull ? nq : cull));
+}
+
+void launch_tamols_batch(const TamolsBatchJob& j, hipStream_t s) {
+    hipLaunchKernelGGL(tamols_batch_kernel, dim3(4, j.E), dim3(TAMOLS_BATCH_THREADS), tamols_batch_lds(j.rows, j.cols),
+                       s, j);
 }
 
 }  // namespace srbd

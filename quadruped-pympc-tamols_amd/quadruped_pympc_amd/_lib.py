@@ -93,6 +93,16 @@ class BatchDeviceIO(C.Structure):
     ]
 
 
+class TamolsBatchIO(C.Structure):
+    """srbd_tamols_batch_io (include/srbd_mpc.h): the device arrays of one srbd_tamols_batch_device call."""
+    _fields_ = [
+        ("seeds", _P), ("hips", _P), ("forward_vel", _P), ("base_pos", _P), ("contact", _P), ("feet", _P),
+        ("yaws", _P), ("heightmaps", _P), ("rows", _I), ("cols", _I), ("dist_x", _D), ("dist_y", _D), ("ray_z", _D),
+        ("footholds", _P), ("boxes", _P), ("valid", _P), ("seed_heights", _P), ("scores", _P),
+        ("heightmaps_out", _P), ("ref", _P),
+    ]
+
+
 SIGNATURES = {
     "srbd_num_params": (_I, [C.POINTER(SrbdConfig)]),
     "srbd_device_count": (_I, [_IP]),
@@ -213,6 +223,8 @@ SIGNATURES.update({
     "srbd_pgg_run_device": (_I, [_P, _I, _D, _P, _P, _P]),
     "srbd_pgg_contact_sequence_device": (_I, [_P, _I, _I, _DP, _IP, _I, _P, _I, _P]),
     "srbd_prepare_state_device": (_I, [_I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "srbd_tamols_batch_device": (_I, [_P, C.POINTER(TamolsParams), _I, C.POINTER(TamolsBatchIO), _P]),
+    "srbd_selftest_yaw_sincos": (_I, [_P, _I, _P]),
 })
 
 # srbd_time_launch kinds (include/srbd_mpc.h)
@@ -1000,3 +1012,87 @@ def prepare_state_device(state_in, ref_in, current_contact, previous_contact, pa
                                                    int(params_per_leg), P, None if best is None else best.data_ptr(),
                                                    o[0].data_ptr(), o[1].data_ptr(), s),
         "srbd_prepare_state_device")
+
+
+MAX_CAND = 320
+
+
+def tamols_batch_device(seeds, hips, params, *, terrain=None, yaws=None, heightmaps=None, rows=13, cols=7,
+                        dist_x=0.04, dist_y=0.04, ray_z=10.0, forward_vel=None, base_pos=None, contact=None, feet=None,
+                        ref=None, out=None, want_seed_heights=False, want_scores=False, want_heightmaps=False,
+                        stream=None):
+    """srbd_tamols_batch_device: the TAMOLS foothold search of every environment, one launch enqueued on ``stream``
+    (None: torch's current stream) without a host synchronisation.  seeds / hips (E, 4, 3) float64, ``params`` a
+    TamolsParams.  Terrain form: ``terrain`` a GpuTerrain on the tensors' device and ``yaws`` (E,) float64; the
+    patches are raycast around the seeds (rows x cols, dist_x, dist_y, ray_z).  Patch form: ``heightmaps``
+    (E, 4, rows, cols, 3) float64, whose shape gives rows and cols.  Optional per-environment inputs: forward_vel /
+    base_pos (E, 3) float64, contact (E, 4) float32 (stance iff 1.0), feet (E, 4, 3) float64.  ``ref`` (E, 24)
+    float64: its entries 12..23 receive the footholds.  ``out``: a dict of preallocated outputs (any of footholds
+    (E, 4, 3), boxes (E, 4, 2, 3), valid (E, 4) int32, seed_heights (E, 4), scores (E, 4, rows * cols), heightmaps
+    (E, 4, rows, cols, 3)); absent footholds / boxes / valid are allocated, the other three only when asked for by
+    their ``want_`` flag.  Returns the dict of the tensors written."""
+    import torch
+
+    E = int(seeds.shape[0]) if isinstance(seeds, torch.Tensor) and seeds.dim() == 3 else 0
+    if not 1 <= E <= MAX_ENVS:
+        raise ValueError(f"seeds must be a torch tensor of shape (1..{MAX_ENVS}, 4, 3)")
+    if not isinstance(params, TamolsParams):
+        raise ValueError("params must be a TamolsParams")
+    if (terrain is None) == (heightmaps is None):
+        raise ValueError("give either terrain (with yaws) or heightmaps")
+    f64, f32, i32 = (torch.float64,), (torch.float32,), (torch.int32,)
+    specs = [("seeds", seeds, (E, 4, 3), f64), ("hips", hips, (E, 4, 3), f64)]
+    if terrain is None:
+        if not isinstance(heightmaps, torch.Tensor) or heightmaps.dim() != 5:
+            raise ValueError(f"heightmaps must be a torch tensor of shape ({E}, 4, rows, cols, 3)")
+        rows, cols = int(heightmaps.shape[2]), int(heightmaps.shape[3])
+        specs.append(("heightmaps", heightmaps, (E, 4, rows, cols, 3), f64))
+        if yaws is not None or want_heightmaps or (out and "heightmaps" in out):
+            raise ValueError("yaws and the heightmaps output belong to the terrain form")
+    else:
+        rows, cols = int(rows), int(cols)
+        if yaws is None:
+            raise ValueError("the terrain form needs yaws")
+        specs.append(("yaws", yaws, (E,), f64))
+        if not (float(dist_x) > 0.0 and float(dist_y) > 0.0):
+            raise ValueError(f"dist_x and dist_y must be positive, got {dist_x}, {dist_y}")
+    if rows < 1 or cols < 1 or rows * cols > MAX_CAND:
+        raise ValueError(f"the patch must have 1..{MAX_CAND} points, got {rows} x {cols}")
+    nc = rows * cols
+    for name, t, shape, dt in (("forward_vel", forward_vel, (E, 3), f64), ("base_pos", base_pos, (E, 3), f64),
+                               ("contact", contact, (E, 4), f32), ("feet", feet, (E, 4, 3), f64),
+                               ("ref", ref, (E, 24), f64)):
+        if t is not None:
+            specs.append((name, t, shape, dt))
+    shapes = {"footholds": ((E, 4, 3), f64), "boxes": ((E, 4, 2, 3), f64), "valid": ((E, 4), i32),
+              "seed_heights": ((E, 4), f64), "scores": ((E, 4, nc), f64), "heightmaps": ((E, 4, rows, cols, 3), f64)}
+    given = dict(out or {})
+    for name, t in given.items():
+        if name not in shapes:
+            raise ValueError(f"unknown output {name!r}")
+        specs.append((f"out[{name!r}]", t, *shapes[name]))
+    dev = _device_tensors(specs)
+    wanted = ["footholds", "boxes", "valid"] + [n for n, w in (("seed_heights", want_seed_heights),
+                                                                 ("scores", want_scores),
+                                                                 ("heightmaps", want_heightmaps)) if w]
+
+    def alloc():
+        o = dict(given)
+        for n in wanted:
+            if n not in o:
+                o[n] = torch.empty(shapes[n][0], dtype=shapes[n][1][0], device=dev)
+        return o
+
+    def ptr(t):
+        return None if t is None else t.data_ptr()
+
+    def call(o, s):
+        io = TamolsBatchIO(seeds=ptr(seeds), hips=ptr(hips), forward_vel=ptr(forward_vel), base_pos=ptr(base_pos),
+                           contact=ptr(contact), feet=ptr(feet), yaws=ptr(yaws), heightmaps=ptr(heightmaps),
+                           rows=rows, cols=cols, dist_x=float(dist_x), dist_y=float(dist_y), ray_z=float(ray_z),
+                           footholds=ptr(o["footholds"]), boxes=ptr(o["boxes"]), valid=ptr(o["valid"]),
+                           seed_heights=ptr(o.get("seed_heights")), scores=ptr(o.get("scores")),
+                           heightmaps_out=ptr(o.get("heightmaps")), ref=ptr(ref))
+        return lib.srbd_tamols_batch_device(None if terrain is None else terrain.h, C.byref(params), E, C.byref(io), s)
+
+    return _enqueue(dev, stream, alloc, call, "srbd_tamols_batch_device")

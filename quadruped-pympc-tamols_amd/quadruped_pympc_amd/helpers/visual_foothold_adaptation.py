@@ -301,3 +301,42 @@ class VisualFootholdAdaptation:
                         reference_footholds[n][2] = h
         self.update_footholds_adaptation(reference_footholds)
         return True
+
+
+class BatchedVisualFootholdAdaptation:
+    """TAMOLS foothold adaptation of ``num_envs`` environments on the device (``srbd_tamols_batch_device``): the
+    batched, device-resident counterpart of ``VisualFootholdAdaptation.compute_adaptation`` with the strategy
+    ``'tamols'``, for the loop ``gait.run -> compute_adaptation_device -> prepare_state_and_reference_device ->
+    compute_control_device``.  Every environment gets what the single-environment call computes for its inputs; the
+    parameters (``tamols_params`` and the robot's reach limits, through ``tamols_params_struct``) are shared.  The
+    constructor touches no device."""
+
+    def __init__(self, num_envs: int, config_module=None):
+        num_envs = int(num_envs)
+        if not 1 <= num_envs <= _lib.MAX_ENVS:
+            raise ValueError(f"num_envs must be 1..{_lib.MAX_ENVS}, got {num_envs}")
+        cfg = active_config(config_module)
+        self.num_envs = num_envs
+        self.tamols_params = cfg.simulation_params.get("tamols_params", {})
+        self.robot_name = cfg.robot
+        self._params_src = self._params_struct = self._params_robot = None
+
+    _params = VisualFootholdAdaptation._params
+
+    def compute_adaptation_device(self, seeds, hips, forward_vel, base_position, current_contact, current_feet_pos, *,
+                                  terrain=None, yaws=None, heightmaps=None, ref=None, stream=None, **patch):
+        """One search per environment, enqueued on ``stream`` (None: torch's current stream); nothing is synchronised.
+        seeds / hips (E, 4, 3) float64 device tensors (legs FL FR RL RR); forward_vel / base_position (E, 3) float64,
+        current_contact (E, 4) float32 as the device gait generator writes it, current_feet_pos (E, 4, 3) float64, each
+        of them or None as in ``compute_adaptation``.  Either ``terrain`` (a GpuTerrain) with ``yaws`` (E,) -- the
+        patches are raycast around the seeds; ``patch`` may give rows, cols, dist_x, dist_y, ray_z -- or ``heightmaps``
+        (E, 4, rows, cols, 3).  ``ref`` (E, 24) float64: the reference ``prepare_state_and_reference_device`` takes,
+        whose feet (entries 12..23) receive the footholds.  Returns (footholds (E, 4, 3), boxes (E, 4, 2, 3) -- NaN
+        for a leg without a feasible candidate, whose foothold is the seed at its terrain height --, valid (E, 4)
+        int32)."""
+        if getattr(seeds, "shape", (0,))[0] != self.num_envs:
+            raise ValueError(f"seeds must hold {self.num_envs} environments, got {tuple(getattr(seeds, 'shape', ()))}")
+        out = _lib.tamols_batch_device(seeds, hips, self._params(), terrain=terrain, yaws=yaws, heightmaps=heightmaps,
+                                       forward_vel=forward_vel, base_pos=base_position, contact=current_contact,
+                                       feet=current_feet_pos, ref=ref, stream=stream, **patch)
+        return out["footholds"], out["boxes"], out["valid"]
