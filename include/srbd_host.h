@@ -9,6 +9,9 @@
  *   srbd_pgg_contact_sequence        <- PeriodicGaitGenerator.compute_contact_sequence :93-118
  *   srbd_prepare_state               <- Sampling_MPC.prepare_state_and_reference
  *                                       quadruped_pympc/controllers/sampling/centroidal_nmpc_jax.py:563-627
+ *   srbd_frg_init / _compute / _update_lift_off / _update_touch_down / _mean
+ *                                    <- FootholdReferenceGenerator
+ *                                       quadruped_pympc/helpers/foothold_reference_generator.py:15-199
  *   srbd_shm_publish / srbd_shm_read <- the MPC -> WBC shared-memory seqlock of ros2/run_controller.py
  *                                       (payload layout :50-83, writer :343-358, reader :565-580)
  *
@@ -70,6 +73,65 @@ int srbd_pgg_contact_sequence(srbd_pgg* g, const double* dts, const int32_t* len
 int srbd_prepare_state(const double state_in[24], const double ref_in[24], const double current_contact[4],
                        const double previous_contact[4], int32_t params_per_leg, float* best_params,
                        double state_out[24], double ref_out[24]);
+
+/* ---- Foothold reference generator: the seeds of the foothold adaptation, and on flat ground the reference's feet
+ * directly (quadruped_pympc/helpers/foothold_reference_generator.py, run by WBInterface.update_state_and_reference
+ * every step between the gait generator and the foothold adaptation, wb_interface.py:202-227).
+ *   srbd_frg_init              <- FootholdReferenceGenerator.__init__                     :15-51
+ *   srbd_frg_compute           <- FootholdReferenceGenerator.compute_footholds_reference  :53-157
+ *   srbd_frg_update_lift_off   <- FootholdReferenceGenerator.update_lift_off_positions    :159-178
+ *   srbd_frg_update_touch_down <- FootholdReferenceGenerator.update_touch_down_positions  :180-199
+ * State (plain data: the caller may copy, inspect or persist it; sizeof is a multiple of 8, so an array of them in
+ * device memory keeps every double aligned).  Legs FL FR RL RR, positions xyz.  vel_hist is the reference's
+ * deque(maxlen = 20) of horizontal-frame base velocities as a ring: hist_len entries are held; hist_head is the slot
+ * the next entry goes to -- equal to hist_len while the ring fills (the oldest entry is slot 0), the oldest entry
+ * once it is full. */
+#define SRBD_FRG_HIST 20
+typedef struct srbd_frg {
+    double stance_time, hip_height;
+    double hip_offset;                       /* 0.1 (:44); y offset of the nominal foothold from the hip */
+    double lift_off[4][3], lift_off_h[4][3]; /* world frame, and the horizontal frame of the lift-off instant */
+    double touch_down[4][3], touch_down_h[4][3];
+    double last_reference_footholds[4][3];   /* the last srbd_frg_compute result */
+    double vel_hist[SRBD_FRG_HIST][2];
+    int32_t hist_len, hist_head;             /* two words: no further padding is needed */
+} srbd_frg;
+
+/* All four position tables start as copies of lift_off (4 x 3), the _h tables too (the reference's "TODO wrong" is
+ * reproduced); the history starts empty and last_reference_footholds at zero.  SRBD_E_INVALID: a NULL pointer, a
+ * stance_time or hip_height that is not finite. */
+int srbd_frg_init(srbd_frg* g, double stance_time, double hip_height, const double* lift_off /* 4 x 3 */);
+/* The lift-off and touch-down bookkeeping.  Contacts are doubles compared with == 1 and == 0 as the reference compares
+ * them; full_stance != 0 is the reference's gait_type == FULL_STANCE branch (every leg takes its foot, the _h tables
+ * are left alone).  Otherwise a leg lifting off (1 -> 0) takes its foot and stores it in the horizontal frame,
+ * R_W2H @ (foot - base_pos); a leg in swing (0 -> 0) is carried with the base, R_W2H.T @ lift_off_h + base_pos.  Touch
+ * down is the same with 0 -> 1 and 1 -> 1.  R_W2H is the 3 x 3 yaw rotation, written out element by element:
+ * (c x + s y, -s x + c y, z), transposed (c x + (-s) y, s x + c y, z).  feet is 4 x 3. */
+int srbd_frg_update_lift_off(srbd_frg* g, const double previous_contact[4], const double current_contact[4],
+                             const double* feet, int32_t full_stance, const double base_pos[3], double yaw);
+int srbd_frg_update_touch_down(srbd_frg* g, const double previous_contact[4], const double current_contact[4],
+                               const double* feet, int32_t full_stance, const double base_pos[3], double yaw);
+/* The Raibert-style reference footholds, in the reference's order: both velocities rotated into the horizontal
+ * frame; the base velocity pushed into the ring and the mean of what the ring holds taken (the sum starts from the
+ * oldest entry, adds oldest to newest and is divided by the count, as np.mean of the deque's rows: an all -0.0
+ * history has a -0.0 mean); delta = clip((stance_time / 2) * ref_vel_H, -1.5 hip_height, 1.5 hip_height); err =
+ * sqrt(com_height_nominal / gravity) * (mean - ref_vel_H) limited to +-0.05 (a NaN passes); per leg R_W2H @ (hip_xy -
+ * base_xy), y +- hip_offset (+ FL RL, - FR RR), + (delta + err), R_W2H.T @ ... + base_xy, + com_pos_offset_w[0:2],
+ * z = lift_off[leg][2].  out (4 x 3) receives the footholds, and so does last_reference_footholds.
+ *   com_pos_offset_w: 3 doubles, or NULL for the reference's zero offset (the additions of +0.0 still happen).  The
+ *   reference forms it as Rotation.from_euler('xyz', rpy) @ com_pos_offset_b, and the body offset is zero unless set
+ *   by hand from the ROS console: that rotation is the caller's, this call takes only the world offset.
+ * cos and sin of the yaw are the correctly rounded values in all three functions (csrc/yaw_sincos.h;
+ * srbd_selftest_yaw_sincos shows them): the same bits as the device form, srbd_frg_step_device (srbd_mpc.h); libm's
+ * differ from them in the last place for about 3 in 1000 yaws.
+ * SRBD_E_INVALID: a NULL pointer (com_pos_offset_w excepted).  Nothing else is refused: NaN inputs flow through as in
+ * NumPy. */
+int srbd_frg_compute(srbd_frg* g, const double base_pos[3], double yaw, const double base_xy_vel[2],
+                     const double ref_xy_vel[2], const double* hips /* 4 x 3 */, double com_height_nominal,
+                     double gravity, const double* com_pos_offset_w /* 3, or NULL */, double* out /* 4 x 3 */);
+/* The moving average srbd_frg_compute uses: the mean of what the ring holds, summed oldest to newest from the oldest
+ * entry (not from zero) and divided by the count; NaN for an empty ring.  For inspection and tests. */
+int srbd_frg_mean(const srbd_frg* g, double mean_out[2]);
 
 /* ---- MPC -> WBC shared-memory seqlock (single writer, any number of readers) ---- */
 #define SRBD_SHM_DOUBLES 75

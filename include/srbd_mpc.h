@@ -685,6 +685,54 @@ int srbd_tamols_batch_device(srbd_terrain* terrain /* NULL: patch form */, const
  * evaluated on the host by the same function (plain float64 operations and fma: the same bits on both sides). */
 int srbd_selftest_yaw_sincos(const double* yaws, int32_t n, double* out_cs);
 
+/* The foothold reference generator of the device-resident loop: the `seeds` srbd_tamols_batch_device reads, and on
+ * flat ground the reference's feet directly (FootholdReferenceGenerator, foothold_reference_generator.py:53-199, run
+ * by WBInterface.update_state_and_reference every step between the gait generator and the foothold adaptation,
+ * wb_interface.py:202-227), for num_envs environments in one launch, so that generator.run -> seeds -> footholds ->
+ * prepare -> srbd_batch_step_device never leaves the GPU.
+ *   Generator state: d_frg is an array of num_envs srbd_frg structs (srbd_host.h, plain data) in device memory.  The
+ *   caller initialises them on the host with srbd_frg_init, uploads them, and may download and inspect them at any
+ *   time.  Stance time, hip height and hip offset are per environment, read from the struct; com_height_nominal and
+ *   gravity are shared.
+ *   Equivalence: for environment e the call does what these three host calls do in order on a host srbd_frg with the
+ *   same bytes: srbd_frg_update_lift_off, srbd_frg_update_touch_down, srbd_frg_compute (srbd_host.h), with the
+ *   contacts widened to double, full_stance = (pgg != NULL and pgg[e].gait_type == SRBD_GAIT_FULL_STANCE), base_pos[e],
+ *   yaws[e], the x and y of base_lin_vel[e] and ref_lin_vel[e], and com_pos_offset_w[e] or NULL.  Afterwards d_frg[e]
+ *   holds exactly the host struct's bytes and seeds[e] the host's `out`, bit for bit, NaNs position for position.  The
+ *   arithmetic is float64 in the order of the host functions, unfused -- both sides compile the same per-leg
+ *   functions -- with cos / sin of the yaw correctly rounded on both (csrc/yaw_sincos.h) and sqrt(com_height_nominal
+ *   / gravity) evaluated once on the host.  Environments are independent: a NaN in one changes nothing in another.
+ *   ref, when given, is srbd_prepare_state_device's d_ref_in: entries 12..23 of row e (ref_foot_FL..RR) receive
+ *   environment e's footholds, entries 0..11 are not written -- the flat-ground loop ('blind') needs no other
+ *   foothold call.  previous_contact / current_contact are float32 as srbd_pgg_run_device writes them.  Only
+ *   gait_type is read from pgg.
+ *   Enqueue contract (the producers' above, srbd_prepare_state_device's): exactly one launch on hip_stream, no
+ *   synchronising HIP call, no device memory touched from the host; the stream handle is read as
+ *   srbd_prepare_state_device reads it (NULL and hipStreamLegacy both select the legacy null stream); every pointer is
+ *   memory of the current device; no event and no ordering rule.  Arrays must not overlap.
+ *   SRBD_E_INVALID (before any HIP call): a NULL d_frg, io or required pointer (every pointer except pgg,
+ *   com_pos_offset_w and ref); a com_height_nominal or gravity that is not finite; gravity <= 0; num_envs outside
+ *   1..4096.  A failed launch: SRBD_E_HIP, or SRBD_E_NODEVICE where no device exists. */
+struct srbd_frg;
+typedef struct srbd_frg_batch_io {
+    /* inputs: device memory, float64 unless noted; E = num_envs */
+    const double* base_pos;           /* E x 3 */
+    const double* yaws;               /* E */
+    const double* base_lin_vel;       /* E x 3, x and y used */
+    const double* ref_lin_vel;        /* E x 3, x and y used */
+    const double* hips;               /* E x 4 x 3 */
+    const double* feet;               /* E x 4 x 3 */
+    const float* previous_contact;    /* E x 4 float32, as srbd_pgg_run_device writes it */
+    const float* current_contact;     /* E x 4 float32 */
+    const struct srbd_pgg* pgg;       /* E, or NULL; only gait_type is read: FULL_STANCE -> the full-stance branch */
+    const double* com_pos_offset_w;   /* E x 3, or NULL */
+    double com_height_nominal, gravity; /* shared */
+    /* outputs */
+    double* seeds;                    /* E x 4 x 3: the layout srbd_tamols_batch_device reads */
+    double* ref;                      /* E x 24 or NULL: entries 12..23 of row e receive the footholds */
+} srbd_frg_batch_io;
+int srbd_frg_step_device(struct srbd_frg* d_frg, int32_t num_envs, const srbd_frg_batch_io* io, void* hip_stream);
+
 /* Diagnostic: enable != 0 stamps the phases of the following TAMOLS calls; out_us[5] (may be NULL)
  * receives the last call's mean per-block durations of (patch, queries, scores, slice argmin + count)
  * and the span from the first block's start to the last leg's end, in us.  enable == 0 turns it off. */

@@ -3,12 +3,14 @@
 //   PGG  = quadruped_pympc/helpers/periodic_gait_generator.py
 //   NMPC = quadruped_pympc/controllers/sampling/centroidal_nmpc_jax.py
 //   ROS  = ros2/run_controller.py
+//   FRG  = quadruped_pympc/helpers/foothold_reference_generator.py
 // Built with -ffp-contract=off: every float64 operation rounds as NumPy's does.
 #include <math.h>
 #include <string.h>
 
 #include "../../include/srbd_host.h"
 #include "../../include/srbd_mpc.h"
+#include "srbd_frg.h"
 #include "srbd_jaxrng.h"
 
 namespace {
@@ -139,6 +141,83 @@ extern "C" int srbd_prepare_state(const double state_in[24], const double ref_in
         for (int l = 0; l < 4; ++l)
             if (previous_contact[l] == 1.0 && current_contact[l] == 0.0)
                 for (int j = 0; j < params_per_leg; ++j) best_params[l * params_per_leg + j] = 0.0f;
+    return SRBD_OK;
+}
+
+// ------------------------------------------------------------------ foothold reference generator (srbd_frg.h)
+extern "C" int srbd_frg_init(srbd_frg* g, double stance_time, double hip_height, const double* lift_off) {  // FRG:15-51
+    if (!g || !lift_off || !std::isfinite(stance_time) || !std::isfinite(hip_height)) return SRBD_E_INVALID;
+    memset(g, 0, sizeof(*g));
+    g->stance_time = stance_time;
+    g->hip_height = hip_height;
+    g->hip_offset = 0.1;
+    memcpy(g->lift_off, lift_off, sizeof(g->lift_off));
+    memcpy(g->lift_off_h, lift_off, sizeof(g->lift_off_h));  // the reference's "TODO wrong", reproduced
+    memcpy(g->touch_down, lift_off, sizeof(g->touch_down));
+    memcpy(g->touch_down_h, lift_off, sizeof(g->touch_down_h));
+    return SRBD_OK;
+}
+
+extern "C" int srbd_frg_update_lift_off(srbd_frg* g, const double previous_contact[4], const double current_contact[4],
+                                        const double* feet, int32_t full_stance, const double base_pos[3],
+                                        double yaw) {  // FRG:159-178
+    if (!g || !previous_contact || !current_contact || !feet || !base_pos) return SRBD_E_INVALID;
+    double c, s;
+    srbd::yaw_sincos(yaw, c, s);
+    for (int l = 0; l < 4; ++l)
+        srbd::frg_leg_lift_off(g, l, previous_contact[l], current_contact[l], feet + 3 * l, full_stance != 0, base_pos,
+                               c, s);
+    return SRBD_OK;
+}
+
+extern "C" int srbd_frg_update_touch_down(srbd_frg* g, const double previous_contact[4],
+                                          const double current_contact[4], const double* feet, int32_t full_stance,
+                                          const double base_pos[3], double yaw) {  // FRG:180-199
+    if (!g || !previous_contact || !current_contact || !feet || !base_pos) return SRBD_E_INVALID;
+    double c, s;
+    srbd::yaw_sincos(yaw, c, s);
+    for (int l = 0; l < 4; ++l)
+        srbd::frg_leg_touch_down(g, l, previous_contact[l], current_contact[l], feet + 3 * l, full_stance != 0,
+                                 base_pos, c, s);
+    return SRBD_OK;
+}
+
+extern "C" int srbd_frg_compute(srbd_frg* g, const double base_pos[3], double yaw, const double base_xy_vel[2],
+                                const double ref_xy_vel[2], const double* hips, double com_height_nominal,
+                                double gravity, const double* com_pos_offset_w, double* out) {  // FRG:53-157
+    if (!g || !base_pos || !base_xy_vel || !ref_xy_vel || !hips || !out) return SRBD_E_INVALID;
+    double c, s;
+    srbd::yaw_sincos(yaw, c, s);
+    const double vx = c * base_xy_vel[0] + s * base_xy_vel[1], vy = -s * base_xy_vel[0] + c * base_xy_vel[1];
+    const double rx = c * ref_xy_vel[0] + s * ref_xy_vel[1], ry = -s * ref_xy_vel[0] + c * ref_xy_vel[1];
+    double mx, my;
+    srbd::frg_mean_with(g, g->hist_len, g->hist_head, vx, vy, mx, my);
+    int len, head;
+    const int slot = srbd::frg_ring_next(g->hist_len, g->hist_head, len, head);
+    g->vel_hist[slot][0] = vx;
+    g->vel_hist[slot][1] = vy;
+    g->hist_len = len;
+    g->hist_head = head;
+    double ox, oy;
+    srbd::frg_compensation(g, rx, ry, mx, my, sqrt(com_height_nominal / gravity), ox, oy);
+    for (int l = 0; l < 4; ++l)
+        srbd::frg_leg_foothold(g, l, hips + 3 * l, base_pos, c, s, ox, oy, com_pos_offset_w, out + 3 * l);
+    return SRBD_OK;
+}
+
+// The mean srbd_frg_compute formed at its last push: the ring as it was before that push, plus the newest entry.
+extern "C" int srbd_frg_mean(const srbd_frg* g, double mean_out[2]) {
+    if (!g || !mean_out) return SRBD_E_INVALID;
+    int len = g->hist_len, head = g->hist_head;
+    srbd::frg_ring_sane(len, head);
+    if (len == 0) {
+        mean_out[0] = mean_out[1] = NAN;
+        return SRBD_OK;
+    }
+    const int newest = head == 0 ? SRBD_FRG_HIST - 1 : head - 1;
+    const bool full = len == SRBD_FRG_HIST;  // the ring before the push: full with its head at `newest`, or one shorter
+    srbd::frg_mean_with(g, full ? len : len - 1, newest, g->vel_hist[newest][0], g->vel_hist[newest][1], mean_out[0],
+                        mean_out[1]);
     return SRBD_OK;
 }
 

@@ -11,6 +11,11 @@
 //   prepare_state_kernel         srbd_prepare_state         NMPC:563-627 (no solution shift)
 // Legs are independent in all three, so one lane owns one (environment, leg): lane t of the grid is leg t & 3 of
 // environment t >> 2, 64 environments per 256-thread block, the lanes past 4 E idle.  No LDS, no cross-lane traffic.
+// frg_step_kernel (srbd_frg_step_device) is the foothold reference generator of the same loop, one lane per
+// (environment, leg) too: srbd_frg_update_lift_off, _update_touch_down and _compute of srbd_host.cpp in that order,
+// through the per-leg functions both sides share (srbd_frg.h; FRG = quadruped_pympc/helpers/
+// foothold_reference_generator.py:53-199).  Its one piece of cross-lane traffic is a quad broadcast of the velocity
+// ring's length and head (see the kernel).
 // srbd_tamols_batch_device, the loop's foothold search, is validated and enqueued here too; its kernel lives with the
 // single-environment one (tamols_kernel.hip tamols_batch_kernel), whose device functions it runs.
 #include <hip/hip_runtime.h>
@@ -18,6 +23,7 @@
 
 #include "../../include/srbd_host.h"
 #include "../../include/srbd_mpc.h"
+#include "srbd_frg.h"
 #include "srbd_launch.h"
 #include "yaw_sincos.h"
 
@@ -141,6 +147,69 @@ __global__ void __launch_bounds__(PROD_BLOCK) prepare_state_kernel(int E, const 
     }
 }
 
+// The arrays of one srbd_frg_step_device call (srbd_frg_batch_io) and the values formed on the host.
+struct FrgJob {
+    const double *base_pos, *yaws, *base_vel, *ref_vel, *hips, *feet, *com_off;
+    const float *prev, *cur;
+    const srbd_pgg* pgg;
+    double root;  // sqrt(com_height_nominal / gravity)
+    double *seeds, *ref;
+};
+
+// Lane (e, l) owns row l of the five position tables of environment e and writes nothing else, lane (e, 0) the
+// velocity ring besides.  All four lanes need the ring's mean: each forms it from the ring as it was and the new entry
+// it holds in registers (frg_mean_with), and lane 0 alone stores that entry -- into a slot that is unused (ring not
+// full) or holds the evicted oldest entry (ring full), which the new mean excludes.  The ring's length and head are
+// rewritten by lane 0 as well, so lane 0 alone loads them and hands them to its three neighbours with a quad
+// broadcast (4 E lanes are live and a quad is one environment, so its lane 0 is live whenever the others are).  No
+// lane reads a word another lane of the launch writes.
+__global__ void __launch_bounds__(PROD_BLOCK) frg_step_kernel(srbd_frg* __restrict__ frg, int E, const FrgJob j) {
+#pragma clang fp contract(off)
+    const int t = blockIdx.x * PROD_BLOCK + threadIdx.x;
+    if (t >= 4 * E) return;
+    const int e = t >> 2, l = t & 3;
+    srbd_frg* g = frg + e;
+    int len = 0, head = 0;
+    if (l == 0) {
+        len = g->hist_len;
+        head = g->hist_head;
+    }
+    len = __shfl(len, 0, 4);
+    head = __shfl(head, 0, 4);
+    const double base[3] = {j.base_pos[3 * (size_t)e], j.base_pos[3 * (size_t)e + 1], j.base_pos[3 * (size_t)e + 2]};
+    const double* foot = j.feet + 3 * (size_t)t;
+    const double prev = (double)j.prev[t], cur = (double)j.cur[t];
+    const bool full_stance = j.pgg && j.pgg[e].gait_type == SRBD_GAIT_FULL_STANCE;
+    double c, s;
+    yaw_sincos(j.yaws[e], c, s);
+    frg_leg_lift_off(g, l, prev, cur, foot, full_stance, base, c, s);
+    frg_leg_touch_down(g, l, prev, cur, foot, full_stance, base, c, s);
+    const double bx = j.base_vel[3 * (size_t)e], by = j.base_vel[3 * (size_t)e + 1];
+    const double qx = j.ref_vel[3 * (size_t)e], qy = j.ref_vel[3 * (size_t)e + 1];
+    const double vx = c * bx + s * by, vy = -s * bx + c * by;
+    const double rx = c * qx + s * qy, ry = -s * qx + c * qy;
+    double mx, my, ox, oy;
+    frg_mean_with(g, len, head, vx, vy, mx, my);
+    frg_compensation(g, rx, ry, mx, my, j.root, ox, oy);
+    double out[3];
+    frg_leg_foothold(g, l, j.hips + 3 * (size_t)t, base, c, s, ox, oy, j.com_off ? j.com_off + 3 * (size_t)e : nullptr,
+                     out);
+    double* __restrict__ seed = j.seeds + 3 * (size_t)t;
+    seed[0] = out[0], seed[1] = out[1], seed[2] = out[2];
+    if (j.ref) {
+        double* __restrict__ r = j.ref + 24 * (size_t)e + 12 + 3 * l;
+        r[0] = out[0], r[1] = out[1], r[2] = out[2];
+    }
+    if (l == 0) {
+        int len1, head1;
+        const int slot = frg_ring_next(len, head, len1, head1);
+        g->vel_hist[slot][0] = vx;
+        g->vel_hist[slot][1] = vy;
+        g->hist_len = len1;
+        g->hist_head = head1;
+    }
+}
+
 }  // namespace srbd
 
 using namespace srbd;
@@ -208,6 +277,32 @@ extern "C" int srbd_prepare_state_device(int32_t num_envs, const double* d_state
     hipLaunchKernelGGL(prepare_state_kernel, dim3(blocks_of(num_envs)), dim3(PROD_BLOCK), 0, stream_of(hip_stream),
                        num_envs, d_state_in, d_ref_in, d_current_contact, d_previous_contact, params_per_leg,
                        num_params, d_best_params, d_states, d_refs);
+    return launch_status();
+}
+
+extern "C" int srbd_frg_step_device(srbd_frg* d_frg, int32_t num_envs, const srbd_frg_batch_io* io, void* hip_stream) {
+    if (!d_frg || !io || !envs_ok(num_envs)) return SRBD_E_INVALID;
+    if (!io->base_pos || !io->yaws || !io->base_lin_vel || !io->ref_lin_vel || !io->hips || !io->feet ||
+        !io->previous_contact || !io->current_contact || !io->seeds)
+        return SRBD_E_INVALID;
+    if (!std::isfinite(io->com_height_nominal) || !std::isfinite(io->gravity) || !(io->gravity > 0.0))
+        return SRBD_E_INVALID;
+    FrgJob j = {};
+    j.base_pos = io->base_pos;
+    j.yaws = io->yaws;
+    j.base_vel = io->base_lin_vel;
+    j.ref_vel = io->ref_lin_vel;
+    j.hips = io->hips;
+    j.feet = io->feet;
+    j.com_off = io->com_pos_offset_w;
+    j.prev = io->previous_contact;
+    j.cur = io->current_contact;
+    j.pgg = io->pgg;
+    j.root = sqrt(io->com_height_nominal / io->gravity);  // once, here: srbd_frg_compute's value
+    j.seeds = io->seeds;
+    j.ref = io->ref;
+    hipLaunchKernelGGL(frg_step_kernel, dim3(blocks_of(num_envs)), dim3(PROD_BLOCK), 0, stream_of(hip_stream), d_frg,
+                       num_envs, j);
     return launch_status();
 }
 

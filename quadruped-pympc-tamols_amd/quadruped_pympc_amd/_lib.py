@@ -163,6 +163,26 @@ class SrbdPgg(C.Structure):
                 ("init", _I * 4), ("gait_type", _I), ("previous_gait_type", _I), ("horizon", _I)]
 
 
+FRG_HIST = 20
+
+
+class SrbdFrg(C.Structure):
+    """srbd_frg (include/srbd_host.h): FootholdReferenceGenerator state."""
+    _fields_ = [("stance_time", _D), ("hip_height", _D), ("hip_offset", _D),
+                ("lift_off", _D * 3 * 4), ("lift_off_h", _D * 3 * 4), ("touch_down", _D * 3 * 4),
+                ("touch_down_h", _D * 3 * 4), ("last_reference_footholds", _D * 3 * 4),
+                ("vel_hist", _D * 2 * FRG_HIST), ("hist_len", _I), ("hist_head", _I)]
+
+
+class SrbdFrgBatchIo(C.Structure):
+    """srbd_frg_batch_io (include/srbd_mpc.h): the device arrays of one srbd_frg_step_device call."""
+    _fields_ = [
+        ("base_pos", _P), ("yaws", _P), ("base_lin_vel", _P), ("ref_lin_vel", _P), ("hips", _P), ("feet", _P),
+        ("previous_contact", _P), ("current_contact", _P), ("pgg", _P), ("com_pos_offset_w", _P),
+        ("com_height_nominal", _D), ("gravity", _D), ("seeds", _P), ("ref", _P),
+    ]
+
+
 SHM_DOUBLES = 75
 
 
@@ -187,6 +207,11 @@ SIGNATURES.update({
     "srbd_pgg_set_phase_signal": (_I, [C.POINTER(SrbdPgg), _DP, _IP]),
     "srbd_pgg_contact_sequence": (_I, [C.POINTER(SrbdPgg), _DP, _IP, _I, _DP, _I]),
     "srbd_prepare_state": (_I, [_DP, _DP, _DP, _DP, _I, _FP, _DP, _DP]),
+    "srbd_frg_init": (_I, [C.POINTER(SrbdFrg), _D, _D, _DP]),
+    "srbd_frg_update_lift_off": (_I, [C.POINTER(SrbdFrg), _DP, _DP, _DP, _I, _DP, _D]),
+    "srbd_frg_update_touch_down": (_I, [C.POINTER(SrbdFrg), _DP, _DP, _DP, _I, _DP, _D]),
+    "srbd_frg_compute": (_I, [C.POINTER(SrbdFrg), _DP, _D, _DP, _DP, _DP, _D, _D, _DP, _DP]),
+    "srbd_frg_mean": (_I, [C.POINTER(SrbdFrg), _DP]),
     "srbd_shm_publish": (_I, [_P, _P, C.POINTER(ShmMsg)]),
     "srbd_shm_read": (_I, [_P, _P, C.POINTER(ShmMsg), _U64P]),
     "srbd_terrain_create": (_I, [_I, C.POINTER(TerrainPrim), _I, _I, _D, _DP, _I, _I, _D, _D, _D, _D, _D,
@@ -225,6 +250,7 @@ SIGNATURES.update({
     "srbd_prepare_state_device": (_I, [_I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "srbd_tamols_batch_device": (_I, [_P, C.POINTER(TamolsParams), _I, C.POINTER(TamolsBatchIO), _P]),
     "srbd_selftest_yaw_sincos": (_I, [_P, _I, _P]),
+    "srbd_frg_step_device": (_I, [_P, _I, C.POINTER(SrbdFrgBatchIo), _P]),
 })
 
 # srbd_time_launch kinds (include/srbd_mpc.h)
@@ -1096,3 +1122,52 @@ def tamols_batch_device(seeds, hips, params, *, terrain=None, yaws=None, heightm
         return lib.srbd_tamols_batch_device(None if terrain is None else terrain.h, C.byref(params), E, C.byref(io), s)
 
     return _enqueue(dev, stream, alloc, call, "srbd_tamols_batch_device")
+
+
+FRG_BYTES = C.sizeof(SrbdFrg)
+
+
+def frg_step_device(frg, base_pos, yaws, base_lin_vel, ref_lin_vel, hips, feet, previous_contact, current_contact,
+                    com_height_nominal: float, gravity: float, *, pgg=None, com_pos_offset_w=None, ref=None, out=None,
+                    stream=None):
+    """srbd_frg_step_device: the lift-off and touch-down bookkeeping and the reference footholds of every
+    environment, one launch enqueued on ``stream`` (None: torch's current stream) without a host synchronisation.
+    frg (E, FRG_BYTES) uint8: the srbd_frg structs, advanced in place.  base_pos / base_lin_vel / ref_lin_vel (E, 3),
+    yaws (E,), hips / feet (E, 4, 3) float64; previous_contact / current_contact (E, 4) float32.  Optional: pgg
+    (E, PGG_BYTES) uint8 (FULL_STANCE environments take the full-stance branch), com_pos_offset_w (E, 3) float64, ref
+    (E, 24) float64 (its entries 12..23 receive the footholds), out (E, 4, 3) float64.  Returns the seeds (E, 4, 3)."""
+    import math
+
+    import torch
+
+    E = int(frg.shape[0]) if isinstance(frg, torch.Tensor) and frg.dim() == 2 else 0
+    if not 1 <= E <= MAX_ENVS:
+        raise ValueError(f"the generator state must be (1..{MAX_ENVS}, {FRG_BYTES}) uint8, got "
+                         f"{tuple(getattr(frg, 'shape', ()))}")
+    chn, grav = float(com_height_nominal), float(gravity)
+    if not (math.isfinite(chn) and math.isfinite(grav) and grav > 0.0):
+        raise ValueError(f"com_height_nominal must be finite and gravity finite and positive, got {chn}, {grav}")
+    f64, f32, u8 = (torch.float64,), (torch.float32,), (torch.uint8,)
+    specs = [("frg", frg, (E, FRG_BYTES), u8), ("base_pos", base_pos, (E, 3), f64), ("yaws", yaws, (E,), f64),
+             ("base_lin_vel", base_lin_vel, (E, 3), f64), ("ref_lin_vel", ref_lin_vel, (E, 3), f64),
+             ("hips", hips, (E, 4, 3), f64), ("feet", feet, (E, 4, 3), f64),
+             ("previous_contact", previous_contact, (E, 4), f32), ("current_contact", current_contact, (E, 4), f32)]
+    for name, t, shape, dt in (("pgg", pgg, (E, PGG_BYTES), u8), ("com_pos_offset_w", com_pos_offset_w, (E, 3), f64),
+                               ("ref", ref, (E, 24), f64), ("out", out, (E, 4, 3), f64)):
+        if t is not None:
+            specs.append((name, t, shape, dt))
+    dev = _device_tensors(specs)
+
+    def ptr(t):
+        return None if t is None else t.data_ptr()
+
+    def call(o, s):
+        io = SrbdFrgBatchIo(base_pos=ptr(base_pos), yaws=ptr(yaws), base_lin_vel=ptr(base_lin_vel),
+                            ref_lin_vel=ptr(ref_lin_vel), hips=ptr(hips), feet=ptr(feet),
+                            previous_contact=ptr(previous_contact), current_contact=ptr(current_contact),
+                            pgg=ptr(pgg), com_pos_offset_w=ptr(com_pos_offset_w), com_height_nominal=chn,
+                            gravity=grav, seeds=ptr(o), ref=ptr(ref))
+        return lib.srbd_frg_step_device(frg.data_ptr(), E, C.byref(io), s)
+
+    return _enqueue(dev, stream, lambda: torch.empty((E, 4, 3), dtype=torch.float64, device=dev) if out is None
+                    else out, call, "srbd_frg_step_device")
