@@ -9,14 +9,30 @@ cited per function, with parameters from ``quadruped_pympc/config.py:209-243``.
 Nearest-neighbour height lookups use ``scipy.spatial.cKDTree`` exactly as the
 reference's ``FastHeightMap`` does (VFA:21-35).
 
-PARITY STATUS: parity unpinned against the reference itself (it imports
-``gym_quadruped`` at module import, which is absent; the reference has no
-tests or fixtures).  Pinned by analytic known-answer tests (flat patch: edge =
-roughness = 0 and the winner is the reachable candidate nearest the seed).
+PARITY STATUS: pinned to the reference's own scores.  The reference file loads
+by path once stand-ins replace the two modules it imports that are absent
+(``gym_quadruped``'s ``LegsAttr`` and ``quadruped_pympc.config``);
+``oracle/record_tamols_reference.py`` runs its ``compute_adaptation`` with
+``_compute_tamols_score`` wrapped and writes every candidate's score, the
+footholds, the boxes and validity to ``tests/golden/tamols_ref_*.npz``.
+``tests/test_tamols_reference.py`` holds this oracle to them bit for bit (inf
+and NaN positions included, both ``nn`` modes) over seven patch shapes, three
+robots' reach bounds, non-zero nominal-kinematic weights, infeasible legs, NaN
+heights and every branch of the cost (the recorder counts them with the
+reference's own helpers); the mirrored ``tamols_params`` are held to the
+reference's ``config.py``, read as data.
 
-The original ``HeightMap.get_height`` used by the all-infeasible fallback
-(VFA:223-228) lives in the absent gym_quadruped; it is inferred to be the same
-nearest-neighbour + 0.02 lookup that ``FastHeightMap`` accelerates (VFA:22).
+Still unpinned:
+
+* The original ``HeightMap.get_height`` used by the all-infeasible fallback
+  (VFA:223-228) lives in the absent gym_quadruped; it is inferred to be the same
+  nearest-neighbour + 0.02 lookup that ``FastHeightMap`` accelerates (VFA:22).
+  The recorder hands the reference a stand-in with that lookup, so the recorded
+  fallback heights restate the inference.
+* cKDTree's choice between exactly equidistant patch points (the recorded cases
+  hold none; ``tests/test_tamols_ties.py``).
+* The patch itself: the recorded patches come from ``oracle/terrain_oracle.py``,
+  not from the MuJoCo sensor.
 """
 from __future__ import annotations
 

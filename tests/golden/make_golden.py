@@ -1,12 +1,17 @@
 #!/usr/bin/env python3
 """Generate the golden fixtures under tests/golden/ (run from the repo root).
 
-The reference ships no golden vectors and cannot run here (JAX and gym_quadruped are absent:
-ordinary ModuleNotFoundError), so these fixtures are produced by the CPU oracle
-restatements (oracle/*.py) on fixed-seed synthetic inputs.  They pin the oracle against drift
-(tests/test_golden.py) and give the GPU path fixed input/output pairs that do not need the
+The reference ships no golden vectors and its controller cannot run here (JAX and gym_quadruped
+are absent: ordinary ModuleNotFoundError), so these fixtures are produced by the CPU
+oracle restatements (oracle/*.py) on fixed-seed synthetic inputs.  They pin the oracle against
+drift (tests/test_golden.py) and give the GPU path fixed input/output pairs that do not need the
 oracle at run time (tests/test_gpu_golden.py).  Every fixture stores its inputs with its
-outputs.  Parity with the reference itself stays unpinned.
+outputs.  For the fixtures written here, parity with the reference itself stays unpinned:
+tamols_go2.npz too is the oracle's own output.
+
+Not written here: tamols_ref_*.npz, the reference's own TAMOLS scores and footholds.
+oracle/record_tamols_reference.py records them from a checkout of the reference
+(tests/test_tamols_reference.py, tests/test_gpu_tamols_reference.py).
 
     python tests/golden/make_golden.py
 """
