@@ -12,6 +12,11 @@
  *   srbd_frg_init / _compute / _update_lift_off / _update_touch_down / _mean
  *                                    <- FootholdReferenceGenerator
  *                                       quadruped_pympc/helpers/foothold_reference_generator.py:15-199
+ *   srbd_stc_init / _set_timing / _update_swing_time / _reference / _step / _apex / _full_stance
+ *                                    <- SwingTrajectoryController and the leg law of
+ *                                       WBInterface.compute_stance_and_swing_torque
+ *                                       quadruped_pympc/helpers/swing_trajectory_controller.py:5-146
+ *                                       quadruped_pympc/interfaces/wb_interface.py:369-415, :435-465
  *   srbd_shm_publish / srbd_shm_read <- the MPC -> WBC shared-memory seqlock of ros2/run_controller.py
  *                                       (payload layout :50-83, writer :343-358, reader :565-580)
  *
@@ -132,6 +137,93 @@ int srbd_frg_compute(srbd_frg* g, const double base_pos[3], double yaw, const do
 /* The moving average srbd_frg_compute uses: the mean of what the ring holds, summed oldest to newest from the oldest
  * entry (not from zero) and divided by the count; NaN for an empty ring.  For inspection and tests. */
 int srbd_frg_mean(const srbd_frg* g, double mean_out[2]);
+
+/* ---- Stance and swing leg controller: the joint torques of one control step from the MPC's ground-reaction forces,
+ * the last stage of the reference's step (WBInterface.compute_stance_and_swing_torque, quadruped_pympc/interfaces/
+ * wb_interface.py:304-467, with SwingTrajectoryController, quadruped_pympc/helpers/swing_trajectory_controller.py).
+ *   srbd_stc_init              <- SwingTrajectoryController.__init__                              :5-33
+ *   srbd_stc_set_timing        <- SwingTrajectoryController.regenerate_swing_trajectory_generator :35-46
+ *   srbd_stc_update_swing_time <- SwingTrajectoryController.update_swing_time                     :120-127
+ *   srbd_stc_reference         <- SwingTrajectoryGenerator.compute_trajectory_references of
+ *                                 swing_generators/bezier_ref_swing_trajectory_generator.py:222-265 ('bezier_ref', the
+ *                                 reference's default) and explicit_swing_trajectory_generator.py:57-113 ('explicit')
+ *   srbd_stc_step              <- wb_interface.py:369-415 and :435-465 with compute_swing_control_cartesian_space :48-94
+ *   srbd_stc_apex              <- SwingTrajectoryController.check_apex_condition                  :129-138
+ *   srbd_stc_full_stance       <- SwingTrajectoryController.check_full_stance_condition           :140-146
+ * State (plain data, sizeof 80: the caller may copy, inspect or persist it, and an array of them in device memory
+ * keeps every double aligned).  Legs FL FR RL RR.  The arithmetic is float64 in the fixed order csrc/srbd_stc.h writes
+ * out, which the device form (srbd_stc_step_device, srbd_mpc.h) compiles too; integer powers are repeated
+ * multiplication where the reference's `**` calls pow, so values agree with the reference to rounding, not to the bit.
+ * Deviation: the reference inverts the leg Jacobian with np.linalg.pinv (an SVD); here Jinv is the 3 x 3 inverse by
+ * cofactors over the determinant.  For a well-conditioned Jacobian the two agree to rounding.  For a singular one they
+ * do not: when the determinant is zero or not finite Jinv is the zero matrix, so every output stays finite and the
+ * feedback-linearisation term reduces to the bias force.
+ * Out of scope: the early-stance detector (neither generator reads its hit moment or hit point, and
+ * reflex_next_steps_height_enhancement is off by default: it changes no output of this path), inverse kinematics and
+ * des_joints_pos, the kinodynamic branch, the 'scipy' generator, and the re-timing from optimize_swing /
+ * best_sample_freq (wb_interface.py:354-358; srbd_stc_set_timing is the call it would make). */
+enum { SRBD_SWING_BEZIER_REF = 0, SRBD_SWING_EXPLICIT = 1 };
+typedef struct srbd_stc {
+    double step_height, swing_period, position_gain_fb, velocity_gain_fb;
+    int32_t generator;                  /* SRBD_SWING_BEZIER_REF, SRBD_SWING_EXPLICIT */
+    int32_t use_feedback_linearization; /* 1 after init */
+    int32_t use_friction_compensation;  /* 1 after init */
+    int32_t reserved;                   /* 0: the fourth word, so that no padding is left to chance */
+    double swing_time[4];               /* the per-leg swing clocks */
+} srbd_stc;
+
+/* One environment's step.  Matrices are 4 x 3 x 3 row-major, already sliced to the leg's own three joint columns;
+ * vectors are 4 x 3. */
+typedef struct srbd_stc_io {
+    /* inputs */
+    const double *jac, *jac_dot, *mass_matrix;                 /* 4 x 3 x 3 */
+    const double *q_dot, *foot_pos, *foot_vel;                 /* 4 x 3 */
+    const double *qfrc_passive, *qfrc_bias, *grfs;             /* 4 x 3 */
+    const double *lift_off, *touch_down;                       /* 4 x 3 */
+    const double* contact;                                     /* 4: a leg is in swing iff its flag == 0 */
+    double apex_interval;
+    /* outputs */
+    double *tau, *des_foot_pos, *des_foot_vel;                 /* 4 x 3 */
+    double* des_joint_vel;                                     /* 4 x 3, or NULL */
+    int32_t *apex, *full_stance;                               /* one word each, or NULL */
+} srbd_stc_io;
+
+/* Clocks at zero, both switches on.  SRBD_E_INVALID (nothing written): a NULL g, a swing_period that is not positive
+ * or not finite, an unknown generator. */
+int srbd_stc_init(srbd_stc* g, double step_height, double swing_period, double position_gain_fb,
+                  double velocity_gain_fb, int32_t generator);
+/* regenerate_swing_trajectory_generator: the new step height and swing period; the clocks are left alone.
+ * SRBD_E_INVALID as srbd_stc_init. */
+int srbd_stc_set_timing(srbd_stc* g, double step_height, double swing_period);
+/* A swing leg (contact == 0) whose clock is below swing_period advances by dt (so a clock passes swing_period by
+ * less than dt and then holds); a stance leg's clock is zero.  SRBD_E_INVALID: NULL, a dt that is not finite. */
+int srbd_stc_update_swing_time(srbd_stc* g, const double contact[4], double dt);
+/* The generator alone at leg's current clock: desired foot position, velocity and acceleration (3 each).
+ *   bezier_ref: s = clip(swing_time / swing_period, 0, 1); the degree-6 Bezier with control points P0 = P1 = P2 =
+ *   lift_off, P4 = P5 = P6 = touch_down, P3 = (mid_x, mid_y, (64 z_mid - 22 z0 - 22 zf) / 20), z_mid = max(z0, zf) +
+ *   step_height; velocity / swing_period, acceleration / swing_period^2.
+ *   explicit, with the reference's quirks: two cubic Beziers split at half = swing_period / 2 by swing_time <= half,
+ *   local time fmod(swing_time, half) / half -- so swing_time == half evaluates the first curve at its start, and a
+ *   clock past swing_period wraps to the start of the second curve; the apex control points sit at the absolute
+ *   height step_height; velocity and acceleration are not rescaled to time.
+ * SRBD_E_INVALID: NULL, leg outside 0..3, a struct srbd_stc_init would refuse. */
+int srbd_stc_reference(const srbd_stc* g, int32_t leg, const double lift_off[3], const double touch_down[3],
+                       double pos[3], double vel[3], double acc[3]);
+/* The whole step of one environment, in this order: the clock update (srbd_stc_update_swing_time); then per leg
+ *   stance (contact != 0): tau = -(J.T @ grf), des_foot_pos = touch_down, des_foot_vel = 0;
+ *   swing (contact == 0): e_p = des_pos - foot_pos, e_v = des_vel - foot_vel, fb = kp e_p + kd e_v, tau = J.T @ fb,
+ *     and with use_feedback_linearization tau += ((M @ Jinv) @ ((des_acc + fb) - J_dot @ q_dot)) + h;
+ *   des_joint_vel = q_dot + clip(Jinv @ des_foot_vel - q_dot, -10, 10) (wb_interface.py:435-465);
+ * then, with use_friction_compensation, tau -= qfrc_passive for every leg, stance or swing; then apex and full_stance
+ * from the clocks as this call leaves them -- what the next step's update_state_and_reference would see.
+ * SRBD_E_INVALID (nothing written): a NULL g, io or required pointer; a struct srbd_stc_init would refuse; a dt or
+ * apex_interval that is not finite.  NaN inputs flow through as in NumPy. */
+int srbd_stc_step(srbd_stc* g, const srbd_stc_io* io, double dt);
+/* 1 if a swing leg's clock lies strictly inside swing_period / 2 +- interval (the reference's two comparisons),
+ * else 0; negative: NULL, or an interval that is not finite. */
+int srbd_stc_apex(const srbd_stc* g, const double contact[4], double interval);
+/* 1 if no contact equals 0, else 0; negative: NULL. */
+int srbd_stc_full_stance(const double contact[4]);
 
 /* ---- MPC -> WBC shared-memory seqlock (single writer, any number of readers) ---- */
 #define SRBD_SHM_DOUBLES 75

@@ -733,6 +733,63 @@ typedef struct srbd_frg_batch_io {
 } srbd_frg_batch_io;
 int srbd_frg_step_device(struct srbd_frg* d_frg, int32_t num_envs, const srbd_frg_batch_io* io, void* hip_stream);
 
+/* The stance and swing leg controller of the device-resident loop: the joint torques a simulator applies, from the
+ * ground-reaction forces srbd_batch_step_device returns (WBInterface.compute_stance_and_swing_torque,
+ * wb_interface.py:369-415 and :435-465, with SwingTrajectoryController, swing_trajectory_controller.py:48-146, and the
+ * 'bezier_ref' and 'explicit' swing generators), for num_envs environments in one launch, so that generator.run ->
+ * footholds -> prepare -> srbd_batch_step_device -> torques never leaves the GPU.
+ *   Controller state: d_stc is an array of num_envs srbd_stc structs (srbd_host.h, plain data) in device memory.  The
+ *   caller initialises them on the host with srbd_stc_init, uploads them, and may download and inspect them at any
+ *   time.  Step height, swing period, gains, generator and the two switches are per environment, read from the
+ *   struct; dt and apex_interval are shared.
+ *   Inputs are the simulator's: jac, jac_dot and mass_matrix are each leg's 3 x 3 block (row-major, already sliced to
+ *   the leg's own three joint columns), q_dot, qfrc_passive and qfrc_bias the leg's three joints.  lift_off is given
+ *   either as an array or through frg, the device state of srbd_frg_step_device, whose lift_off table is read; exactly
+ *   one of the two.  contact is float32 as srbd_pgg_run_device writes it: a leg is in swing iff its flag == 0.0f.
+ *   Equivalence: for environment e the call does what the host call srbd_stc_step (srbd_host.h) does on a host srbd_stc
+ *   with the same bytes and the same inputs, the contacts widened to double.  Afterwards d_stc[e] holds exactly the
+ *   host struct's bytes and every output row the host's values, bit for bit, NaNs position for position; apex[e] and
+ *   full_stance[e] are the host's two words.  The arithmetic is float64 in the order of the host function, unfused --
+ *   both sides compile the same per-leg functions (csrc/srbd_stc.h).  Environments are independent: a NaN in one
+ *   changes nothing in another.  An environment whose struct the host call refuses (unknown generator, swing_period not
+ *   positive and finite) is left as found and its output rows are not written.  The deviations from the reference are
+ *   the host function's: Jinv is the 3 x 3 inverse by cofactors over the determinant where the reference calls
+ *   np.linalg.pinv, and the zero matrix for a singular Jacobian (determinant zero or not finite).
+ *   Enqueue contract (the producers' above, srbd_prepare_state_device's): exactly one launch on hip_stream, no
+ *   synchronising HIP call, no device memory touched from the host; the stream handle is read as
+ *   srbd_prepare_state_device reads it (NULL and hipStreamLegacy both select the legacy null stream); every pointer is
+ *   memory of the current device; no event and no ordering rule.  Arrays must not overlap.
+ *   SRBD_E_INVALID (before any HIP call): a NULL d_stc, io or required pointer (every pointer except lift_off, frg,
+ *   des_joint_vel, apex and full_stance); both or neither of lift_off and frg; num_envs outside 1..4096; a dt or
+ *   apex_interval that is not finite.  A failed launch: SRBD_E_HIP, or SRBD_E_NODEVICE where no device exists. */
+struct srbd_stc;
+typedef struct srbd_stc_batch_io {
+    /* inputs: device memory, float64 unless noted; E = num_envs */
+    const double* jac;                /* E x 4 x 3 x 3 */
+    const double* jac_dot;            /* E x 4 x 3 x 3 */
+    const double* mass_matrix;        /* E x 4 x 3 x 3 */
+    const double* q_dot;              /* E x 4 x 3 */
+    const double* foot_pos;           /* E x 4 x 3 */
+    const double* foot_vel;           /* E x 4 x 3 */
+    const double* qfrc_passive;       /* E x 4 x 3 */
+    const double* qfrc_bias;          /* E x 4 x 3 */
+    const double* grfs;               /* E x 4 x 3 */
+    const double* touch_down;         /* E x 4 x 3 */
+    const double* lift_off;           /* E x 4 x 3, or NULL when frg is given */
+    const struct srbd_frg* frg;       /* E, or NULL when lift_off is given; only lift_off is read */
+    const float* contact;             /* E x 4 float32, as srbd_pgg_run_device writes it */
+    double apex_interval;             /* shared */
+    /* outputs */
+    double* tau;                      /* E x 4 x 3 */
+    double* des_foot_pos;             /* E x 4 x 3 */
+    double* des_foot_vel;             /* E x 4 x 3 */
+    double* des_joint_vel;            /* E x 4 x 3, or NULL */
+    int32_t* apex;                    /* E, or NULL */
+    int32_t* full_stance;             /* E, or NULL */
+} srbd_stc_batch_io;
+int srbd_stc_step_device(struct srbd_stc* d_stc, int32_t num_envs, double dt, const srbd_stc_batch_io* io,
+                         void* hip_stream);
+
 /* Diagnostic: enable != 0 stamps the phases of the following TAMOLS calls; out_us[5] (may be NULL)
  * receives the last call's mean per-block durations of (patch, queries, scores, slice argmin + count)
  * and the span from the first block's start to the last leg's end, in us.  enable == 0 turns it off. */

@@ -4,6 +4,8 @@
 //   NMPC = quadruped_pympc/controllers/sampling/centroidal_nmpc_jax.py
 //   ROS  = ros2/run_controller.py
 //   FRG  = quadruped_pympc/helpers/foothold_reference_generator.py
+//   STC  = quadruped_pympc/helpers/swing_trajectory_controller.py
+//   WBI  = quadruped_pympc/interfaces/wb_interface.py
 // Built with -ffp-contract=off: every float64 operation rounds as NumPy's does.
 #include <math.h>
 #include <string.h>
@@ -12,6 +14,7 @@
 #include "../../include/srbd_mpc.h"
 #include "srbd_frg.h"
 #include "srbd_jaxrng.h"
+#include "srbd_stc.h"
 
 namespace {
 
@@ -219,6 +222,78 @@ extern "C" int srbd_frg_mean(const srbd_frg* g, double mean_out[2]) {
     srbd::frg_mean_with(g, full ? len : len - 1, newest, g->vel_hist[newest][0], g->vel_hist[newest][1], mean_out[0],
                         mean_out[1]);
     return SRBD_OK;
+}
+
+// ------------------------------------------------------------------ stance and swing leg controller (srbd_stc.h)
+extern "C" int srbd_stc_init(srbd_stc* g, double step_height, double swing_period, double position_gain_fb,
+                             double velocity_gain_fb, int32_t generator) {  // STC:5-33
+    if (!g || !(swing_period > 0.0) || !std::isfinite(swing_period)) return SRBD_E_INVALID;
+    if (generator != SRBD_SWING_BEZIER_REF && generator != SRBD_SWING_EXPLICIT) return SRBD_E_INVALID;
+    memset(g, 0, sizeof(*g));
+    g->step_height = step_height;
+    g->swing_period = swing_period;
+    g->position_gain_fb = position_gain_fb;
+    g->velocity_gain_fb = velocity_gain_fb;
+    g->generator = generator;
+    g->use_feedback_linearization = 1;
+    g->use_friction_compensation = 1;
+    return SRBD_OK;
+}
+
+extern "C" int srbd_stc_set_timing(srbd_stc* g, double step_height, double swing_period) {  // STC:35-46
+    if (!g || !(swing_period > 0.0) || !std::isfinite(swing_period)) return SRBD_E_INVALID;
+    g->step_height = step_height;
+    g->swing_period = swing_period;
+    return SRBD_OK;
+}
+
+extern "C" int srbd_stc_update_swing_time(srbd_stc* g, const double contact[4], double dt) {  // STC:120-127
+    if (!g || !contact || !std::isfinite(dt)) return SRBD_E_INVALID;
+    for (int l = 0; l < 4; ++l) g->swing_time[l] = srbd::stc_clock(g->swing_time[l], g->swing_period, contact[l], dt);
+    return SRBD_OK;
+}
+
+extern "C" int srbd_stc_reference(const srbd_stc* g, int32_t leg, const double lift_off[3], const double touch_down[3],
+                                  double pos[3], double vel[3], double acc[3]) {
+    if (!g || !lift_off || !touch_down || !pos || !vel || !acc || leg < 0 || leg > 3 || !srbd::stc_struct_ok(g))
+        return SRBD_E_INVALID;
+    srbd::stc_reference(g, g->swing_time[leg], lift_off, touch_down, pos, vel, acc);
+    return SRBD_OK;
+}
+
+// WBI:369-415, :435-465: the clock update, the four legs (friction compensation inside each: the same subtraction
+// the reference makes after its loop), then the two flags from the updated clocks.
+extern "C" int srbd_stc_step(srbd_stc* g, const srbd_stc_io* io, double dt) {
+    if (!g || !io || !std::isfinite(dt) || !std::isfinite(io->apex_interval) || !srbd::stc_struct_ok(g))
+        return SRBD_E_INVALID;
+    if (!io->jac || !io->jac_dot || !io->mass_matrix || !io->q_dot || !io->foot_pos || !io->foot_vel ||
+        !io->qfrc_passive || !io->qfrc_bias || !io->grfs || !io->lift_off || !io->touch_down || !io->contact ||
+        !io->tau || !io->des_foot_pos || !io->des_foot_vel)
+        return SRBD_E_INVALID;
+    for (int l = 0; l < 4; ++l)
+        g->swing_time[l] = srbd::stc_clock(g->swing_time[l], g->swing_period, io->contact[l], dt);
+    for (int l = 0; l < 4; ++l) {
+        const srbd::StcLeg x = {io->jac + 9 * l,         io->jac_dot + 9 * l,      io->mass_matrix + 9 * l,
+                                io->q_dot + 3 * l,       io->foot_pos + 3 * l,     io->foot_vel + 3 * l,
+                                io->qfrc_passive + 3 * l, io->qfrc_bias + 3 * l,   io->grfs + 3 * l,
+                                io->lift_off + 3 * l,    io->touch_down + 3 * l,   io->tau + 3 * l,
+                                io->des_foot_pos + 3 * l, io->des_foot_vel + 3 * l,
+                                io->des_joint_vel ? io->des_joint_vel + 3 * l : nullptr};
+        srbd::stc_leg(g, g->swing_time[l], io->contact[l], x);
+    }
+    if (io->apex) *io->apex = srbd::stc_apex(g->swing_time, g->swing_period, io->contact, io->apex_interval);
+    if (io->full_stance) *io->full_stance = srbd::stc_full_stance(io->contact);
+    return SRBD_OK;
+}
+
+extern "C" int srbd_stc_apex(const srbd_stc* g, const double contact[4], double interval) {  // STC:129-138
+    if (!g || !contact || !std::isfinite(interval)) return SRBD_E_INVALID;
+    return srbd::stc_apex(g->swing_time, g->swing_period, contact, interval);
+}
+
+extern "C" int srbd_stc_full_stance(const double contact[4]) {  // STC:140-146
+    if (!contact) return SRBD_E_INVALID;
+    return srbd::stc_full_stance(contact);
 }
 
 // srbd_api.hip: the chained form (TAMOLS writes the step's device input; one host wait), 1 when not taken.

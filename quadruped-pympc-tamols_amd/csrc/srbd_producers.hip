@@ -16,6 +16,10 @@
 // through the per-leg functions both sides share (srbd_frg.h; FRG = quadruped_pympc/helpers/
 // foothold_reference_generator.py:53-199).  Its one piece of cross-lane traffic is a quad broadcast of the velocity
 // ring's length and head (see the kernel).
+// stc_step_kernel (srbd_stc_step_device) is the loop's last stage, the stance and swing leg torques, one lane per
+// (environment, leg) as well: srbd_stc_step of srbd_host.cpp through the per-leg functions of srbd_stc.h (STC =
+// quadruped_pympc/helpers/swing_trajectory_controller.py, quadruped_pympc/interfaces/wb_interface.py:369-465).  No
+// cross-lane traffic.
 // srbd_tamols_batch_device, the loop's foothold search, is validated and enqueued here too; its kernel lives with the
 // single-environment one (tamols_kernel.hip tamols_batch_kernel), whose device functions it runs.
 #include <hip/hip_runtime.h>
@@ -25,6 +29,7 @@
 #include "../../include/srbd_mpc.h"
 #include "srbd_frg.h"
 #include "srbd_launch.h"
+#include "srbd_stc.h"
 #include "yaw_sincos.h"
 
 namespace srbd {
@@ -210,6 +215,66 @@ __global__ void __launch_bounds__(PROD_BLOCK) frg_step_kernel(srbd_frg* __restri
     }
 }
 
+// The arrays of one srbd_stc_step_device call (srbd_stc_batch_io).
+struct StcJob {
+    const double *jac, *jac_dot, *mass_matrix, *q_dot, *foot_pos, *foot_vel, *passive, *bias, *grfs, *lift_off,
+        *touch_down;
+    const srbd_frg* frg;
+    const float* contact;
+    double dt, apex_interval;
+    double *tau, *des_foot_pos, *des_foot_vel, *des_joint_vel;
+    int32_t *apex, *full_stance;
+};
+
+// srbd_stc_step of srbd_host.cpp per environment, through the per-leg functions both sides share (srbd_stc.h).  Lane
+// (e, l) owns clock l of environment e and row (e, l) of the outputs and writes nothing else, lane (e, 0) the two
+// flag words besides.  The apex flag needs all four updated clocks: every lane loads the four old clocks and the four
+// contacts first, and lane 0 recomputes its neighbours' clocks from them (stc_clock, the operation they perform), so
+// there is no cross-lane exchange.  The old clocks are loaded before any lane of the quad stores its new one: a quad
+// lies inside one wave, which runs the loads and then the stores in program order, and the fence keeps the compiler
+// from moving a store above them.  An environment whose struct srbd_stc_step would refuse is left as found, its
+// output rows unwritten, as on the host.
+__global__ void __launch_bounds__(PROD_BLOCK) stc_step_kernel(srbd_stc* __restrict__ stc, int E, const StcJob j) {
+#pragma clang fp contract(off)
+    const int t = blockIdx.x * PROD_BLOCK + threadIdx.x;
+    if (t >= 4 * E) return;
+    const int e = t >> 2, l = t & 3;
+    srbd_stc* g = stc + e;
+    if (!stc_struct_ok(g)) return;
+    double clocks[4], contact[4];
+    for (int k = 0; k < 4; ++k) {
+        clocks[k] = g->swing_time[k];
+        contact[k] = (double)j.contact[4 * (size_t)e + k];
+    }
+    __atomic_signal_fence(__ATOMIC_SEQ_CST);
+    const double period = g->swing_period;
+    const double now = stc_clock(clocks[l], period, contact[l], j.dt);
+    const size_t v = 3 * (size_t)t, m = 9 * (size_t)t;
+    const StcLeg x = {j.jac + m,
+                      j.jac_dot + m,
+                      j.mass_matrix + m,
+                      j.q_dot + v,
+                      j.foot_pos + v,
+                      j.foot_vel + v,
+                      j.passive + v,
+                      j.bias + v,
+                      j.grfs + v,
+                      j.frg ? j.frg[e].lift_off[l] : j.lift_off + v,
+                      j.touch_down + v,
+                      j.tau + v,
+                      j.des_foot_pos + v,
+                      j.des_foot_vel + v,
+                      j.des_joint_vel ? j.des_joint_vel + v : nullptr};
+    stc_leg(g, now, contact[l], x);
+    g->swing_time[l] = now;
+    if (l == 0) {
+        clocks[0] = now;
+        for (int k = 1; k < 4; ++k) clocks[k] = stc_clock(clocks[k], period, contact[k], j.dt);
+        if (j.apex) j.apex[e] = stc_apex(clocks, period, contact, j.apex_interval);
+        if (j.full_stance) j.full_stance[e] = stc_full_stance(contact);
+    }
+}
+
 }  // namespace srbd
 
 using namespace srbd;
@@ -302,6 +367,42 @@ extern "C" int srbd_frg_step_device(srbd_frg* d_frg, int32_t num_envs, const srb
     j.seeds = io->seeds;
     j.ref = io->ref;
     hipLaunchKernelGGL(frg_step_kernel, dim3(blocks_of(num_envs)), dim3(PROD_BLOCK), 0, stream_of(hip_stream), d_frg,
+                       num_envs, j);
+    return launch_status();
+}
+
+extern "C" int srbd_stc_step_device(srbd_stc* d_stc, int32_t num_envs, double dt, const srbd_stc_batch_io* io,
+                                    void* hip_stream) {
+    if (!d_stc || !io || !envs_ok(num_envs) || !std::isfinite(dt) || !std::isfinite(io->apex_interval))
+        return SRBD_E_INVALID;
+    if (!io->jac || !io->jac_dot || !io->mass_matrix || !io->q_dot || !io->foot_pos || !io->foot_vel ||
+        !io->qfrc_passive || !io->qfrc_bias || !io->grfs || !io->touch_down || !io->contact || !io->tau ||
+        !io->des_foot_pos || !io->des_foot_vel)
+        return SRBD_E_INVALID;
+    if ((io->lift_off != nullptr) == (io->frg != nullptr)) return SRBD_E_INVALID;  // exactly one of the two
+    StcJob j = {};
+    j.jac = io->jac;
+    j.jac_dot = io->jac_dot;
+    j.mass_matrix = io->mass_matrix;
+    j.q_dot = io->q_dot;
+    j.foot_pos = io->foot_pos;
+    j.foot_vel = io->foot_vel;
+    j.passive = io->qfrc_passive;
+    j.bias = io->qfrc_bias;
+    j.grfs = io->grfs;
+    j.lift_off = io->lift_off;
+    j.touch_down = io->touch_down;
+    j.frg = io->frg;
+    j.contact = io->contact;
+    j.dt = dt;
+    j.apex_interval = io->apex_interval;
+    j.tau = io->tau;
+    j.des_foot_pos = io->des_foot_pos;
+    j.des_foot_vel = io->des_foot_vel;
+    j.des_joint_vel = io->des_joint_vel;
+    j.apex = io->apex;
+    j.full_stance = io->full_stance;
+    hipLaunchKernelGGL(stc_step_kernel, dim3(blocks_of(num_envs)), dim3(PROD_BLOCK), 0, stream_of(hip_stream), d_stc,
                        num_envs, j);
     return launch_status();
 }

@@ -183,6 +183,39 @@ class SrbdFrgBatchIo(C.Structure):
     ]
 
 
+SWING_BEZIER_REF, SWING_EXPLICIT = 0, 1
+SWING_CODES = {"bezier_ref": SWING_BEZIER_REF, "explicit": SWING_EXPLICIT}
+
+
+class SrbdStc(C.Structure):
+    """srbd_stc (include/srbd_host.h): SwingTrajectoryController state."""
+    _fields_ = [("step_height", _D), ("swing_period", _D), ("position_gain_fb", _D), ("velocity_gain_fb", _D),
+                ("generator", _I), ("use_feedback_linearization", _I), ("use_friction_compensation", _I),
+                ("reserved", _I), ("swing_time", _D * 4)]
+
+
+class SrbdStcIo(C.Structure):
+    """srbd_stc_io (include/srbd_host.h): one environment's srbd_stc_step arrays (host pointers)."""
+    _fields_ = [
+        ("jac", _DP), ("jac_dot", _DP), ("mass_matrix", _DP), ("q_dot", _DP), ("foot_pos", _DP), ("foot_vel", _DP),
+        ("qfrc_passive", _DP), ("qfrc_bias", _DP), ("grfs", _DP), ("lift_off", _DP), ("touch_down", _DP),
+        ("contact", _DP), ("apex_interval", _D),
+        ("tau", _DP), ("des_foot_pos", _DP), ("des_foot_vel", _DP), ("des_joint_vel", _DP), ("apex", _IP),
+        ("full_stance", _IP),
+    ]
+
+
+class SrbdStcBatchIo(C.Structure):
+    """srbd_stc_batch_io (include/srbd_mpc.h): the device arrays of one srbd_stc_step_device call."""
+    _fields_ = [
+        ("jac", _P), ("jac_dot", _P), ("mass_matrix", _P), ("q_dot", _P), ("foot_pos", _P), ("foot_vel", _P),
+        ("qfrc_passive", _P), ("qfrc_bias", _P), ("grfs", _P), ("touch_down", _P), ("lift_off", _P), ("frg", _P),
+        ("contact", _P), ("apex_interval", _D),
+        ("tau", _P), ("des_foot_pos", _P), ("des_foot_vel", _P), ("des_joint_vel", _P), ("apex", _P),
+        ("full_stance", _P),
+    ]
+
+
 SHM_DOUBLES = 75
 
 
@@ -212,6 +245,13 @@ SIGNATURES.update({
     "srbd_frg_update_touch_down": (_I, [C.POINTER(SrbdFrg), _DP, _DP, _DP, _I, _DP, _D]),
     "srbd_frg_compute": (_I, [C.POINTER(SrbdFrg), _DP, _D, _DP, _DP, _DP, _D, _D, _DP, _DP]),
     "srbd_frg_mean": (_I, [C.POINTER(SrbdFrg), _DP]),
+    "srbd_stc_init": (_I, [C.POINTER(SrbdStc), _D, _D, _D, _D, _I]),
+    "srbd_stc_set_timing": (_I, [C.POINTER(SrbdStc), _D, _D]),
+    "srbd_stc_update_swing_time": (_I, [C.POINTER(SrbdStc), _DP, _D]),
+    "srbd_stc_reference": (_I, [C.POINTER(SrbdStc), _I, _DP, _DP, _DP, _DP, _DP]),
+    "srbd_stc_step": (_I, [C.POINTER(SrbdStc), C.POINTER(SrbdStcIo), _D]),
+    "srbd_stc_apex": (_I, [C.POINTER(SrbdStc), _DP, _D]),
+    "srbd_stc_full_stance": (_I, [_DP]),
     "srbd_shm_publish": (_I, [_P, _P, C.POINTER(ShmMsg)]),
     "srbd_shm_read": (_I, [_P, _P, C.POINTER(ShmMsg), _U64P]),
     "srbd_terrain_create": (_I, [_I, C.POINTER(TerrainPrim), _I, _I, _D, _DP, _I, _I, _D, _D, _D, _D, _D,
@@ -251,6 +291,7 @@ SIGNATURES.update({
     "srbd_tamols_batch_device": (_I, [_P, C.POINTER(TamolsParams), _I, C.POINTER(TamolsBatchIO), _P]),
     "srbd_selftest_yaw_sincos": (_I, [_P, _I, _P]),
     "srbd_frg_step_device": (_I, [_P, _I, C.POINTER(SrbdFrgBatchIo), _P]),
+    "srbd_stc_step_device": (_I, [_P, _I, _D, C.POINTER(SrbdStcBatchIo), _P]),
 })
 
 # srbd_time_launch kinds (include/srbd_mpc.h)
@@ -1171,3 +1212,78 @@ def frg_step_device(frg, base_pos, yaws, base_lin_vel, ref_lin_vel, hips, feet, 
 
     return _enqueue(dev, stream, lambda: torch.empty((E, 4, 3), dtype=torch.float64, device=dev) if out is None
                     else out, call, "srbd_frg_step_device")
+
+
+STC_BYTES = C.sizeof(SrbdStc)
+STC_OUTPUTS = {"tau": ((4, 3), "float64"), "des_foot_pos": ((4, 3), "float64"), "des_foot_vel": ((4, 3), "float64"),
+               "des_joint_vel": ((4, 3), "float64"), "apex": ((), "int32"), "full_stance": ((), "int32")}
+
+
+def stc_step_device(stc, dt: float, jac, jac_dot, q_dot, foot_pos, foot_vel, qfrc_passive, qfrc_bias, mass_matrix,
+                    grfs, touch_down, contact, *, lift_off=None, frg=None, apex_interval: float = 0.01, out=None,
+                    want_joint_vel=True, want_flags=True, stream=None):
+    """srbd_stc_step_device: the swing clocks and the stance and swing torques of every environment, one launch
+    enqueued on ``stream`` (None: torch's current stream) without a host synchronisation.
+    stc (E, STC_BYTES) uint8: the srbd_stc structs, advanced in place.  jac / jac_dot / mass_matrix (E, 4, 3, 3), q_dot /
+    foot_pos / foot_vel / qfrc_passive / qfrc_bias / grfs / touch_down (E, 4, 3) float64; contact (E, 4) float32.
+    Exactly one of lift_off (E, 4, 3) float64 and frg (E, FRG_BYTES) uint8, the foothold reference generator's state.
+    ``out``: a dict of preallocated outputs (any of tau, des_foot_pos, des_foot_vel, des_joint_vel (E, 4, 3) float64,
+    apex, full_stance (E,) int32); absent tau / des_foot_pos / des_foot_vel are allocated, des_joint_vel and the two
+    flags only when asked for by ``want_joint_vel`` / ``want_flags`` (else they are NULL in the call).  Returns the
+    dict of the tensors written."""
+    import math
+
+    import torch
+
+    E = int(stc.shape[0]) if isinstance(stc, torch.Tensor) and stc.dim() == 2 else 0
+    if not 1 <= E <= MAX_ENVS:
+        raise ValueError(f"the controller state must be (1..{MAX_ENVS}, {STC_BYTES}) uint8, got "
+                         f"{tuple(getattr(stc, 'shape', ()))}")
+    dt, interval = float(dt), float(apex_interval)
+    if not (math.isfinite(dt) and math.isfinite(interval)):
+        raise ValueError(f"dt and apex_interval must be finite, got {dt}, {interval}")
+    if (lift_off is None) == (frg is None):
+        raise ValueError("give exactly one of lift_off and frg")
+    f64, f32, u8 = (torch.float64,), (torch.float32,), (torch.uint8,)
+    specs = [("stc", stc, (E, STC_BYTES), u8), ("jac", jac, (E, 4, 3, 3), f64), ("jac_dot", jac_dot, (E, 4, 3, 3), f64),
+             ("q_dot", q_dot, (E, 4, 3), f64), ("foot_pos", foot_pos, (E, 4, 3), f64),
+             ("foot_vel", foot_vel, (E, 4, 3), f64), ("qfrc_passive", qfrc_passive, (E, 4, 3), f64),
+             ("qfrc_bias", qfrc_bias, (E, 4, 3), f64), ("mass_matrix", mass_matrix, (E, 4, 3, 3), f64),
+             ("grfs", grfs, (E, 4, 3), f64), ("touch_down", touch_down, (E, 4, 3), f64),
+             ("contact", contact, (E, 4), f32)]
+    if lift_off is not None:
+        specs.append(("lift_off", lift_off, (E, 4, 3), f64))
+    else:
+        specs.append(("frg", frg, (E, FRG_BYTES), u8))
+    given = dict(out or {})
+    for name, t in given.items():
+        if name not in STC_OUTPUTS:
+            raise ValueError(f"unknown output {name!r}")
+        tail, dtype = STC_OUTPUTS[name]
+        specs.append((f"out[{name!r}]", t, (E,) + tail, (getattr(torch, dtype),)))
+    dev = _device_tensors(specs)
+    wanted = (["tau", "des_foot_pos", "des_foot_vel"] + (["des_joint_vel"] if want_joint_vel else []) +
+              (["apex", "full_stance"] if want_flags else []))
+
+    def alloc():
+        o = dict(given)
+        for n in wanted:
+            if n not in o:
+                tail, dtype = STC_OUTPUTS[n]
+                o[n] = torch.empty((E,) + tail, dtype=getattr(torch, dtype), device=dev)
+        return o
+
+    def ptr(t):
+        return None if t is None else t.data_ptr()
+
+    def call(o, s):
+        io = SrbdStcBatchIo(jac=ptr(jac), jac_dot=ptr(jac_dot), mass_matrix=ptr(mass_matrix), q_dot=ptr(q_dot),
+                            foot_pos=ptr(foot_pos), foot_vel=ptr(foot_vel), qfrc_passive=ptr(qfrc_passive),
+                            qfrc_bias=ptr(qfrc_bias), grfs=ptr(grfs), touch_down=ptr(touch_down),
+                            lift_off=ptr(lift_off), frg=ptr(frg), contact=ptr(contact), apex_interval=interval,
+                            tau=ptr(o["tau"]), des_foot_pos=ptr(o["des_foot_pos"]),
+                            des_foot_vel=ptr(o["des_foot_vel"]), des_joint_vel=ptr(o.get("des_joint_vel")),
+                            apex=ptr(o.get("apex")), full_stance=ptr(o.get("full_stance")))
+        return lib.srbd_stc_step_device(stc.data_ptr(), E, dt, C.byref(io), s)
+
+    return _enqueue(dev, stream, alloc, call, "srbd_stc_step_device")

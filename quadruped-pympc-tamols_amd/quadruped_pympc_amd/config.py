@@ -92,6 +92,10 @@ mpc_params = {
 }
 
 simulation_params = {
+    # config.py:196-198
+    "swing_generator": "bezier_ref",  # 'explicit', 'bezier_ref' ('scipy' is not available)
+    "swing_position_gain_fb": 500,
+    "swing_velocity_gain_fb": 10,
     "step_height": 0.3 * hip_height,
     "visual_foothold_adaptation": "tamols",
     # config.py:209-243
