@@ -17,6 +17,12 @@
  *                                       WBInterface.compute_stance_and_swing_torque
  *                                       quadruped_pympc/helpers/swing_trajectory_controller.py:5-146
  *                                       quadruped_pympc/interfaces/wb_interface.py:369-415, :435-465
+ *   srbd_vm_modulate / srbd_terrain_est_init / srbd_terrain_estimate / srbd_reference_assemble
+ *                                    <- VelocityModulator, TerrainEstimator and the reference row of
+ *                                       WBInterface.update_state_and_reference
+ *                                       quadruped_pympc/helpers/velocity_modulator.py:19-46
+ *                                       quadruped_pympc/helpers/terrain_estimator.py:5-106
+ *                                       quadruped_pympc/interfaces/wb_interface.py:168-172, :250-291
  *   srbd_shm_publish / srbd_shm_read <- the MPC -> WBC shared-memory seqlock of ros2/run_controller.py
  *                                       (payload layout :50-83, writer :343-358, reader :565-580)
  *
@@ -224,6 +230,60 @@ int srbd_stc_step(srbd_stc* g, const srbd_stc_io* io, double dt);
 int srbd_stc_apex(const srbd_stc* g, const double contact[4], double interval);
 /* 1 if no contact equals 0, else 0; negative: NULL. */
 int srbd_stc_full_stance(const double contact[4]);
+
+/* ---- Velocity modulator, terrain estimator and the reference row's first twelve entries: what
+ * WBInterface.update_state_and_reference builds every control step from the velocity command, before and after the
+ * foothold reference generator (quadruped_pympc/interfaces/wb_interface.py:168-172 and :250-291).
+ *   srbd_vm_modulate        <- VelocityModulator.modulate_velocities   quadruped_pympc/helpers/velocity_modulator.py:19-46
+ *   srbd_terrain_est_init   <- TerrainEstimator.__init__               quadruped_pympc/helpers/terrain_estimator.py:5-11
+ *   srbd_terrain_estimate   <- TerrainEstimator.compute_terrain_estimation                                  :13-106
+ *   srbd_reference_assemble <- wb_interface.py:258-291: ref_position, the command rotated into the terrain frame with
+ *                              its two pitch quirks, ref_orientation, ref_angular_velocity
+ * The struct is named srbd_terrain_est because srbd_terrain is the ray-cast terrain handle of srbd_mpc.h.
+ * State (plain data, sizeof 32: the caller may copy, inspect or persist it, and an array of them in device memory keeps
+ * every double aligned).  The arithmetic is float64 in the fixed order csrc/srbd_terrain.h writes out, which the device
+ * forms (srbd_vm_modulate_device, srbd_terrain_ref_step_device, srbd_mpc.h) compile too.  The modulator and the height
+ * filter are IEEE operations only and equal the reference bit for bit.  Roll, pitch and the rotated command agree with
+ * the reference to rounding: cos / sin are the correctly rounded values of csrc/yaw_sincos.h, the arctangent is the
+ * header's own (within 1 ulp of the true value; srbd_selftest_atan shows it), the yaw rotation is written out where the
+ * reference calls a BLAS product, and the terrain rotation is Ry(pitch) Rx(roll) written out where the reference goes
+ * through scipy's quaternion.
+ * Out of scope: update_start_and_stop, the early-stance detector, inverse kinematics and the kinodynamic branch. */
+typedef struct srbd_terrain_est {
+    double roll, pitch, height;               /* the three filtered values, 0 after init */
+    int32_t roll_activated, pitch_activated;  /* 0 and 1 after init; a switched-off angle is set to 0.0 every step */
+} srbd_terrain_est;
+
+/* If lin[0] < 0.01 and lin[1] < 0.01 (no abs: a negative command counts as standing, a NaN as moving) the command is
+ * returned as it is.  Otherwise, if sqrt(square(dx) + square(dy)) of foot minus hip is strictly above max_distance
+ * for any leg, lin_out = lin * 0.0 and ang_out = ang * 0.0 -- products, so a negative entry becomes -0.0 and a NaN
+ * stays; a NaN distance fails the comparison.  The reference's max_distance is 0.2 for every robot.  feet and hips
+ * are 4 x 3 (z unused).  SRBD_E_INVALID: a NULL pointer.  Nothing else is refused. */
+int srbd_vm_modulate(double max_distance, const double lin[3], const double ang[3], const double* feet /* 4 x 3 */,
+                     const double* hips /* 4 x 3 */, double lin_out[3], double ang_out[3]);
+/* roll = pitch = height = 0, roll_activated = 0, pitch_activated = 1.  SRBD_E_INVALID: NULL. */
+int srbd_terrain_est_init(srbd_terrain_est* g);
+/* One step of the estimator.  feet (4 x 3, FL FR RL RR) are the positions the reference passes: the foothold
+ * generator's lift-off table.  The four R_W2H @ (foot - base_pos) are formed first (each row's products summed left to
+ * right, the zero products included, so a NaN coordinate spreads as in NumPy), then front = FL - FR, back = RL - RR,
+ * left = FL - RL, right = FR - RR; pitch = (arctan(|left z| / |left x + 0.001|) + arctan(|right z| / |right x +
+ * 0.001|)) * 0.5, roll the same from front and back over y; roll is negated if front z * 0.5 + back z * 0.5 < 0, pitch
+ * if left z * 0.5 + right z * 0.5 > 0; the filters are value * 0.99 + new * 0.01 for an activated angle (0.0 for one
+ * switched off) and height * 0.2 + ((z0 + z1 + z2 + z3) / 4) * 0.8.  A zero denominator gives inf and the angle pi / 2;
+ * 0 / 0 gives NaN, which stays in the filter.  The reference's current_contact argument is unused there and absent
+ * here.  out (3, or NULL) receives roll, pitch, height.  SRBD_E_INVALID: a NULL g, base_pos or feet. */
+int srbd_terrain_estimate(srbd_terrain_est* g, const double base_pos[3], double yaw, const double* feet /* 4 x 3 */,
+                          double out[3]);
+/* Entries 0..11 of the 24-entry reference row srbd_prepare_state reads, from the estimator's state and the (modulated)
+ * command: ref_position = (0, 0, (ref_z + height) - (base_z - (com_z + com_off_z))); ref_linear_velocity = R @ lin with
+ * R = [[cp, sp sr, sp cr], [0, cr, -sr], [-sp, cp sr, cp cr]], each row summed left to right, then z negated if pitch >
+ * 0, then x / 2 and z * 2 if |pitch| > 0.2; ref_orientation = (roll, pitch, 0.0); ref_angular_velocity = ang.
+ * SRBD_E_INVALID: a NULL pointer.  NaN inputs flow through. */
+int srbd_reference_assemble(const srbd_terrain_est* g, double ref_z, double base_z, double com_z, double com_off_z,
+                            const double lin[3], const double ang[3], double ref_out[12]);
+/* Self-test: out[i] = the arctangent both sides use, of x[i] >= 0 (+inf and NaN included), evaluated on the host by
+ * the function the device kernel compiles (plain float64 add, multiply and divide: the same bits on both sides). */
+int srbd_selftest_atan(const double* x, int32_t n, double* out);
 
 /* ---- MPC -> WBC shared-memory seqlock (single writer, any number of readers) ---- */
 #define SRBD_SHM_DOUBLES 75

@@ -790,6 +790,64 @@ typedef struct srbd_stc_batch_io {
 int srbd_stc_step_device(struct srbd_stc* d_stc, int32_t num_envs, double dt, const srbd_stc_batch_io* io,
                          void* hip_stream);
 
+/* The velocity modulator and the terrain estimate with the reference row of the device-resident loop: what
+ * WBInterface.update_state_and_reference builds from the velocity command before and after the foothold reference
+ * generator (wb_interface.py:168-172 with velocity_modulator.py:19-46; wb_interface.py:250-291 with
+ * terrain_estimator.py:13-106), for num_envs environments in one launch each, so that the loop needs only measurements
+ * and a velocity command from the simulator: modulate -> srbd_frg_step_device -> terrain / reference ->
+ * srbd_prepare_state_device.
+ *   srbd_vm_modulate_device: lin_out[e], ang_out[e] are what the host call srbd_vm_modulate (srbd_host.h) returns for
+ *   lin[e], ang[e], feet[e], hips[e] and the shared max_distance, bit for bit.  lin_out is what srbd_frg_step_device
+ *   then reads as ref_lin_vel.  The modulator has no state.
+ *   srbd_terrain_ref_step_device: estimator state d_terrain is an array of num_envs srbd_terrain_est structs
+ *   (srbd_host.h, plain data) in device memory, initialised on the host with srbd_terrain_est_init and uploaded.  The
+ *   feet are given either as an array or through frg, the device state of srbd_frg_step_device, whose lift_off table
+ *   is read (the positions the reference passes); exactly one of the two.
+ *   Equivalence: for environment e the call does what these two host calls do in order on a host struct with the same
+ *   bytes: srbd_terrain_estimate(g, base_pos[e], yaws[e], feet[e], terrain[e]) and srbd_reference_assemble(g, ref_z,
+ *   base_pos[e][2], com_pos[e][2], com_pos_offset_w ? com_pos_offset_w[e][2] : 0.0, lin[e], ang[e], ref[e][0:12]).
+ *   Afterwards d_terrain[e] holds exactly the host struct's bytes and entries 0..11 of row e of ref the host's values,
+ *   bit for bit, NaNs position for position; entries 12..23 are not written.  Both sides compile the same functions
+ *   (csrc/srbd_terrain.h, csrc/yaw_sincos.h), none of which calls libm or the device library for cos, sin or arctan.
+ *   Environments are independent: a NaN in one changes nothing in another.
+ *   Enqueue contract (the producers' above): exactly one launch on hip_stream, no synchronising HIP call, no device
+ *   memory touched from the host; NULL and hipStreamLegacy both select the legacy null stream; every pointer is memory
+ *   of the current device.  Arrays must not overlap.
+ *   SRBD_E_INVALID (before any HIP call): a NULL io or required pointer (every pointer except com_pos_offset_w, feet,
+ *   frg and terrain; d_terrain too); both or neither of feet and frg; a ref_z that is not finite; a max_distance that
+ *   is NaN; num_envs outside 1..4096.  A failed launch: SRBD_E_HIP, or SRBD_E_NODEVICE where no device exists. */
+typedef struct srbd_vm_batch_io {
+    /* inputs: device memory, float64; E = num_envs */
+    const double* lin;                /* E x 3: ref_base_lin_vel, the command */
+    const double* ang;                /* E x 3: ref_base_ang_vel */
+    const double* feet;               /* E x 4 x 3 */
+    const double* hips;               /* E x 4 x 3 */
+    double max_distance;              /* shared; the reference's value is 0.2 */
+    /* outputs */
+    double* lin_out;                  /* E x 3 */
+    double* ang_out;                  /* E x 3 */
+} srbd_vm_batch_io;
+int srbd_vm_modulate_device(int32_t num_envs, const srbd_vm_batch_io* io, void* hip_stream);
+
+struct srbd_terrain_est;
+typedef struct srbd_terrain_ref_batch_io {
+    /* inputs: device memory, float64; E = num_envs */
+    const double* base_pos;           /* E x 3 */
+    const double* com_pos;            /* E x 3, z used */
+    const double* com_pos_offset_w;   /* E x 3, z used, or NULL (+0.0) */
+    const double* yaws;               /* E */
+    const double* lin;                /* E x 3: the modulated ref_base_lin_vel */
+    const double* ang;                /* E x 3: the modulated ref_base_ang_vel */
+    const double* feet;               /* E x 4 x 3, or NULL when frg is given */
+    const struct srbd_frg* frg;       /* E, or NULL when feet is given; only lift_off is read */
+    double ref_z;                     /* shared */
+    /* outputs */
+    double* ref;                      /* E x 24: entries 0..11 of row e are written */
+    double* terrain;                  /* E x 3 or NULL: roll, pitch, height */
+} srbd_terrain_ref_batch_io;
+int srbd_terrain_ref_step_device(struct srbd_terrain_est* d_terrain, int32_t num_envs,
+                                 const srbd_terrain_ref_batch_io* io, void* hip_stream);
+
 /* Diagnostic: enable != 0 stamps the phases of the following TAMOLS calls; out_us[5] (may be NULL)
  * receives the last call's mean per-block durations of (patch, queries, scores, slice argmin + count)
  * and the span from the first block's start to the last leg's end, in us.  enable == 0 turns it off. */

@@ -6,6 +6,8 @@
 //   FRG  = quadruped_pympc/helpers/foothold_reference_generator.py
 //   STC  = quadruped_pympc/helpers/swing_trajectory_controller.py
 //   WBI  = quadruped_pympc/interfaces/wb_interface.py
+//   VM   = quadruped_pympc/helpers/velocity_modulator.py
+//   TE   = quadruped_pympc/helpers/terrain_estimator.py
 // Built with -ffp-contract=off: every float64 operation rounds as NumPy's does.
 #include <math.h>
 #include <string.h>
@@ -15,6 +17,7 @@
 #include "srbd_frg.h"
 #include "srbd_jaxrng.h"
 #include "srbd_stc.h"
+#include "srbd_terrain.h"
 
 namespace {
 
@@ -294,6 +297,65 @@ extern "C" int srbd_stc_apex(const srbd_stc* g, const double contact[4], double 
 extern "C" int srbd_stc_full_stance(const double contact[4]) {  // STC:140-146
     if (!contact) return SRBD_E_INVALID;
     return srbd::stc_full_stance(contact);
+}
+
+// ------------------------------------------- velocity modulator, terrain estimator, reference row (srbd_terrain.h)
+extern "C" int srbd_vm_modulate(double max_distance, const double lin[3], const double ang[3], const double* feet,
+                                const double* hips, double lin_out[3], double ang_out[3]) {  // VM:19-46
+    if (!lin || !ang || !feet || !hips || !lin_out || !ang_out) return SRBD_E_INVALID;
+    bool beyond = false;
+    for (int l = 0; l < 4; ++l) beyond = beyond || srbd::vm_distance(feet + 3 * l, hips + 3 * l) > max_distance;
+    const bool standing = srbd::vm_standing(lin);
+    for (int k = 0; k < 3; ++k) {
+        lin_out[k] = srbd::vm_entry(lin[k], standing, beyond);
+        ang_out[k] = srbd::vm_entry(ang[k], standing, beyond);
+    }
+    return SRBD_OK;
+}
+
+extern "C" int srbd_terrain_est_init(srbd_terrain_est* g) {  // TE:5-11
+    if (!g) return SRBD_E_INVALID;
+    memset(g, 0, sizeof(*g));
+    g->pitch_activated = 1;
+    return SRBD_OK;
+}
+
+// TE:13-106 through the pieces the device kernel spreads over a quad: four rotations, four slopes, one filter.
+extern "C" int srbd_terrain_estimate(srbd_terrain_est* g, const double base_pos[3], double yaw, const double* feet,
+                                     double out[3]) {
+    if (!g || !base_pos || !feet) return SRBD_E_INVALID;
+    double c, s, r[4][3], angle[4], dz[4], foot_z[4];
+    srbd::yaw_sincos(yaw, c, s);
+    for (int l = 0; l < 4; ++l) {
+        srbd::terr_rotate(feet + 3 * l, base_pos, c, s, r[l]);
+        foot_z[l] = feet[3 * l + 2];
+    }
+    for (int k = 0; k < 4; ++k) {
+        int a, b;
+        srbd::terr_pair(k, a, b);
+        angle[k] = srbd::terr_slope(k, r[a], r[b], dz[k]);
+    }
+    srbd::terr_filter(g, angle, dz, foot_z);
+    if (out) out[0] = g->roll, out[1] = g->pitch, out[2] = g->height;
+    return SRBD_OK;
+}
+
+extern "C" int srbd_reference_assemble(const srbd_terrain_est* g, double ref_z, double base_z, double com_z,
+                                       double com_off_z, const double lin[3], const double ang[3],
+                                       double ref_out[12]) {  // WBI:258-291
+    if (!g || !lin || !ang || !ref_out) return SRBD_E_INVALID;
+    double cr, sr, cp, sp;
+    srbd::yaw_sincos(g->roll, cr, sr);
+    srbd::yaw_sincos(g->pitch, cp, sp);
+    srbd::terr_assemble(g->roll, g->pitch, g->height, cr, sr, cp, sp, ref_z, base_z, com_z, com_off_z, lin, ang,
+                        ref_out);
+    return SRBD_OK;
+}
+
+extern "C" int srbd_selftest_atan(const double* x, int32_t n, double* out) {
+    if (!x || !out || n < 0) return SRBD_E_INVALID;
+    for (int32_t i = 0; i < n; ++i) out[i] = srbd::terr_atan(x[i]);
+    return SRBD_OK;
 }
 
 // srbd_api.hip: the chained form (TAMOLS writes the step's device input; one host wait), 1 when not taken.

@@ -20,6 +20,11 @@
 // (environment, leg) as well: srbd_stc_step of srbd_host.cpp through the per-leg functions of srbd_stc.h (STC =
 // quadruped_pympc/helpers/swing_trajectory_controller.py, quadruped_pympc/interfaces/wb_interface.py:369-465).  No
 // cross-lane traffic.
+// vm_modulate_kernel (srbd_vm_modulate_device) and terrain_ref_step_kernel (srbd_terrain_ref_step_device) build what
+// the reference derives from the velocity command before and after the foothold generator: the modulated command, the
+// terrain estimate and entries 0..11 of the reference row (srbd_terrain.h; quadruped_pympc/helpers/
+// velocity_modulator.py, terrain_estimator.py, wb_interface.py:168-172, :250-291).  Both spread an environment over
+// its quad and exchange values by shuffles (see the kernels).
 // srbd_tamols_batch_device, the loop's foothold search, is validated and enqueued here too; its kernel lives with the
 // single-environment one (tamols_kernel.hip tamols_batch_kernel), whose device functions it runs.
 #include <hip/hip_runtime.h>
@@ -30,6 +35,7 @@
 #include "srbd_frg.h"
 #include "srbd_launch.h"
 #include "srbd_stc.h"
+#include "srbd_terrain.h"
 #include "yaw_sincos.h"
 
 namespace srbd {
@@ -275,6 +281,111 @@ __global__ void __launch_bounds__(PROD_BLOCK) stc_step_kernel(srbd_stc* __restri
     }
 }
 
+// The arrays of one srbd_vm_modulate_device call (srbd_vm_batch_io).
+struct VmJob {
+    const double *lin, *ang, *feet, *hips;
+    double max_distance;
+    double *lin_out, *ang_out;
+};
+
+// srbd_vm_modulate of srbd_host.cpp per environment (srbd_terrain.h).  Lane (e, l) forms leg l's distance and its
+// comparison; the four comparisons are or-ed across the quad (all four lanes of a live quad are live), and lanes 0..2
+// write entry l of the two outputs.  No state.
+__global__ void __launch_bounds__(PROD_BLOCK) vm_modulate_kernel(int E, const VmJob j) {
+#pragma clang fp contract(off)
+    const int t = blockIdx.x * PROD_BLOCK + threadIdx.x;
+    if (t >= 4 * E) return;
+    const int e = t >> 2, l = t & 3;
+    int beyond = vm_distance(j.feet + 3 * (size_t)t, j.hips + 3 * (size_t)t) > j.max_distance ? 1 : 0;
+    beyond |= __shfl_xor(beyond, 1, 4);
+    beyond |= __shfl_xor(beyond, 2, 4);
+    if (l == 3) return;
+    const double* lin = j.lin + 3 * (size_t)e;
+    const bool standing = vm_standing(lin);
+    j.lin_out[3 * (size_t)e + l] = vm_entry(lin[l], standing, beyond != 0);
+    j.ang_out[3 * (size_t)e + l] = vm_entry(j.ang[3 * (size_t)e + l], standing, beyond != 0);
+}
+
+// The arrays of one srbd_terrain_ref_step_device call (srbd_terrain_ref_batch_io).
+struct TerrJob {
+    const double *base_pos, *com_pos, *com_off, *yaws, *lin, *ang, *feet;
+    const srbd_frg* frg;
+    double ref_z;
+    double *ref, *terrain;
+};
+
+// cos and sin of x on the lanes of a pair: the reduction on both, the sine series on the even lane and the cosine
+// series on the odd one side by side, exchanged by one shuffle; yaw_sincos's functions, so its bits.
+__device__ inline void pair_sincos(double x, int l, double& c, double& s) {
+    DD r;
+    const int q = yaw_reduce(x, r);
+    const bool cosine = (l & 1) != 0;
+    const double mine = yaw_series_value(r, cosine);
+    const double other = __shfl_xor(mine, 1, 4);
+    yaw_finish(x, q, cosine ? other : mine, cosine ? mine : other, c, s);
+}
+
+// srbd_terrain_estimate and srbd_reference_assemble of srbd_host.cpp per environment, through the pieces both sides
+// share (srbd_terrain.h), an environment spread over its quad: lane l rotates foot l, forms difference l with its
+// arctangent (l = 0, 1 the pitch pair, 2, 3 the roll pair), and evaluates one of the four series of cos / sin of roll
+// and pitch; the values move inside the quad by shuffles (4 E lanes are live and a quad is one environment, so every
+// source lane is live).  Lane 0 alone loads the state, runs the filter and stores the three filtered words, and hands
+// them to its neighbours with a quad broadcast: no lane reads a word another lane of the launch writes.  Lane l
+// stores entries 3 l .. 3 l + 2 of the reference row.
+__global__ void __launch_bounds__(PROD_BLOCK) terrain_ref_step_kernel(srbd_terrain_est* __restrict__ terr, int E,
+                                                                      const TerrJob j) {
+#pragma clang fp contract(off)
+    const int t = blockIdx.x * PROD_BLOCK + threadIdx.x;
+    if (t >= 4 * E) return;
+    const int e = t >> 2, l = t & 3;
+    const double base[3] = {j.base_pos[3 * (size_t)e], j.base_pos[3 * (size_t)e + 1], j.base_pos[3 * (size_t)e + 2]};
+    const double* fp = j.frg ? j.frg[e].lift_off[l] : j.feet + 3 * (size_t)t;
+    const double foot[3] = {fp[0], fp[1], fp[2]};
+    const double yaw = j.yaws[e];
+    double c, s, rot[3];
+    pair_sincos(yaw, l, c, s);
+    terr_rotate(foot, base, c, s, rot);
+    int a, b;
+    terr_pair(l, a, b);
+    double ra[3], rb[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        ra[k] = __shfl(rot[k], a, 4);
+        rb[k] = __shfl(rot[k], b, 4);
+    }
+    double dz_l;
+    const double angle_l = terr_slope(l, ra, rb, dz_l);
+    double angle[4], dz[4], foot_z[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        angle[k] = __shfl(angle_l, k, 4);
+        dz[k] = __shfl(dz_l, k, 4);
+        foot_z[k] = __shfl(foot[2], k, 4);
+    }
+    srbd_terrain_est g = {};
+    if (l == 0) {
+        g = terr[e];
+        terr_filter(&g, angle, dz, foot_z);
+        terr[e].roll = g.roll;
+        terr[e].pitch = g.pitch;
+        terr[e].height = g.height;
+        if (j.terrain) {
+            double* __restrict__ o = j.terrain + 3 * (size_t)e;
+            o[0] = g.roll, o[1] = g.pitch, o[2] = g.height;
+        }
+    }
+    const double roll = __shfl(g.roll, 0, 4), pitch = __shfl(g.pitch, 0, 4), height = __shfl(g.height, 0, 4);
+    double cc, ss;  // lanes 0, 1: of the roll; lanes 2, 3: of the pitch
+    pair_sincos(l < 2 ? roll : pitch, l, cc, ss);
+    const double cr = __shfl(cc, 0, 4), sr = __shfl(ss, 0, 4), cp = __shfl(cc, 2, 4), sp = __shfl(ss, 2, 4);
+    double out[12];
+    terr_assemble(roll, pitch, height, cr, sr, cp, sp, j.ref_z, base[2], j.com_pos[3 * (size_t)e + 2],
+                  j.com_off ? j.com_off[3 * (size_t)e + 2] : 0.0, j.lin + 3 * (size_t)e, j.ang + 3 * (size_t)e, out);
+    double* __restrict__ row = j.ref + 24 * (size_t)e + 3 * l;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) row[k] = l == 0 ? out[k] : l == 1 ? out[3 + k] : l == 2 ? out[6 + k] : out[9 + k];
+}
+
 }  // namespace srbd
 
 using namespace srbd;
@@ -404,6 +515,45 @@ extern "C" int srbd_stc_step_device(srbd_stc* d_stc, int32_t num_envs, double dt
     j.full_stance = io->full_stance;
     hipLaunchKernelGGL(stc_step_kernel, dim3(blocks_of(num_envs)), dim3(PROD_BLOCK), 0, stream_of(hip_stream), d_stc,
                        num_envs, j);
+    return launch_status();
+}
+
+extern "C" int srbd_vm_modulate_device(int32_t num_envs, const srbd_vm_batch_io* io, void* hip_stream) {
+    if (!io || !envs_ok(num_envs)) return SRBD_E_INVALID;
+    if (!io->lin || !io->ang || !io->feet || !io->hips || !io->lin_out || !io->ang_out) return SRBD_E_INVALID;
+    if (io->max_distance != io->max_distance) return SRBD_E_INVALID;
+    VmJob j = {};
+    j.lin = io->lin;
+    j.ang = io->ang;
+    j.feet = io->feet;
+    j.hips = io->hips;
+    j.max_distance = io->max_distance;
+    j.lin_out = io->lin_out;
+    j.ang_out = io->ang_out;
+    hipLaunchKernelGGL(vm_modulate_kernel, dim3(blocks_of(num_envs)), dim3(PROD_BLOCK), 0, stream_of(hip_stream),
+                       num_envs, j);
+    return launch_status();
+}
+
+extern "C" int srbd_terrain_ref_step_device(srbd_terrain_est* d_terrain, int32_t num_envs,
+                                            const srbd_terrain_ref_batch_io* io, void* hip_stream) {
+    if (!d_terrain || !io || !envs_ok(num_envs) || !std::isfinite(io->ref_z)) return SRBD_E_INVALID;
+    if (!io->base_pos || !io->com_pos || !io->yaws || !io->lin || !io->ang || !io->ref) return SRBD_E_INVALID;
+    if ((io->feet != nullptr) == (io->frg != nullptr)) return SRBD_E_INVALID;  // exactly one of the two
+    TerrJob j = {};
+    j.base_pos = io->base_pos;
+    j.com_pos = io->com_pos;
+    j.com_off = io->com_pos_offset_w;
+    j.yaws = io->yaws;
+    j.lin = io->lin;
+    j.ang = io->ang;
+    j.feet = io->feet;
+    j.frg = io->frg;
+    j.ref_z = io->ref_z;
+    j.ref = io->ref;
+    j.terrain = io->terrain;
+    hipLaunchKernelGGL(terrain_ref_step_kernel, dim3(blocks_of(num_envs)), dim3(PROD_BLOCK), 0, stream_of(hip_stream),
+                       d_terrain, num_envs, j);
     return launch_status();
 }
 

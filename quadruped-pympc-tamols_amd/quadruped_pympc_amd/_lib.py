@@ -216,6 +216,23 @@ class SrbdStcBatchIo(C.Structure):
     ]
 
 
+class SrbdTerrainEst(C.Structure):
+    """srbd_terrain_est (include/srbd_host.h): TerrainEstimator state."""
+    _fields_ = [("roll", _D), ("pitch", _D), ("height", _D), ("roll_activated", _I), ("pitch_activated", _I)]
+
+
+class SrbdVmBatchIo(C.Structure):
+    """srbd_vm_batch_io (include/srbd_mpc.h): the device arrays of one srbd_vm_modulate_device call."""
+    _fields_ = [("lin", _P), ("ang", _P), ("feet", _P), ("hips", _P), ("max_distance", _D), ("lin_out", _P),
+                ("ang_out", _P)]
+
+
+class SrbdTerrainRefBatchIo(C.Structure):
+    """srbd_terrain_ref_batch_io (include/srbd_mpc.h): the device arrays of one srbd_terrain_ref_step_device call."""
+    _fields_ = [("base_pos", _P), ("com_pos", _P), ("com_pos_offset_w", _P), ("yaws", _P), ("lin", _P), ("ang", _P),
+                ("feet", _P), ("frg", _P), ("ref_z", _D), ("ref", _P), ("terrain", _P)]
+
+
 SHM_DOUBLES = 75
 
 
@@ -252,6 +269,11 @@ SIGNATURES.update({
     "srbd_stc_step": (_I, [C.POINTER(SrbdStc), C.POINTER(SrbdStcIo), _D]),
     "srbd_stc_apex": (_I, [C.POINTER(SrbdStc), _DP, _D]),
     "srbd_stc_full_stance": (_I, [_DP]),
+    "srbd_vm_modulate": (_I, [_D, _DP, _DP, _DP, _DP, _DP, _DP]),
+    "srbd_terrain_est_init": (_I, [C.POINTER(SrbdTerrainEst)]),
+    "srbd_terrain_estimate": (_I, [C.POINTER(SrbdTerrainEst), _DP, _D, _DP, _DP]),
+    "srbd_reference_assemble": (_I, [C.POINTER(SrbdTerrainEst), _D, _D, _D, _D, _DP, _DP, _DP]),
+    "srbd_selftest_atan": (_I, [_P, _I, _P]),
     "srbd_shm_publish": (_I, [_P, _P, C.POINTER(ShmMsg)]),
     "srbd_shm_read": (_I, [_P, _P, C.POINTER(ShmMsg), _U64P]),
     "srbd_terrain_create": (_I, [_I, C.POINTER(TerrainPrim), _I, _I, _D, _DP, _I, _I, _D, _D, _D, _D, _D,
@@ -292,6 +314,8 @@ SIGNATURES.update({
     "srbd_selftest_yaw_sincos": (_I, [_P, _I, _P]),
     "srbd_frg_step_device": (_I, [_P, _I, C.POINTER(SrbdFrgBatchIo), _P]),
     "srbd_stc_step_device": (_I, [_P, _I, _D, C.POINTER(SrbdStcBatchIo), _P]),
+    "srbd_vm_modulate_device": (_I, [_I, C.POINTER(SrbdVmBatchIo), _P]),
+    "srbd_terrain_ref_step_device": (_I, [_P, _I, C.POINTER(SrbdTerrainRefBatchIo), _P]),
 })
 
 # srbd_time_launch kinds (include/srbd_mpc.h)
@@ -1287,3 +1311,91 @@ def stc_step_device(stc, dt: float, jac, jac_dot, q_dot, foot_pos, foot_vel, qfr
         return lib.srbd_stc_step_device(stc.data_ptr(), E, dt, C.byref(io), s)
 
     return _enqueue(dev, stream, alloc, call, "srbd_stc_step_device")
+
+
+def vm_modulate_device(lin, ang, feet, hips, max_distance: float = 0.2, *, out=None, stream=None):
+    """srbd_vm_modulate_device: the velocity modulator of every environment, one launch enqueued on ``stream`` (None:
+    torch's current stream) without a host synchronisation.  lin / ang (E, 3), feet / hips (E, 4, 3) float64.
+    ``out``: None (allocated) or a pair of (E, 3) float64 tensors.  Returns (lin_out, ang_out); lin_out is what
+    ``frg_step_device`` then takes as ref_lin_vel."""
+    import math
+
+    import torch
+
+    E = int(lin.shape[0]) if isinstance(lin, torch.Tensor) and lin.dim() == 2 else 0
+    if not 1 <= E <= MAX_ENVS:
+        raise ValueError(f"lin must be a torch tensor of shape (1..{MAX_ENVS}, 3), got "
+                         f"{tuple(getattr(lin, 'shape', ()))}")
+    limit = float(max_distance)
+    if math.isnan(limit):
+        raise ValueError("max_distance must not be NaN")
+    f64 = (torch.float64,)
+    specs = [("lin", lin, (E, 3), f64), ("ang", ang, (E, 3), f64), ("feet", feet, (E, 4, 3), f64),
+             ("hips", hips, (E, 4, 3), f64)]
+    if out is not None:
+        if len(out) != 2:
+            raise ValueError("out must be a pair (lin_out, ang_out)")
+        specs += [("out[0]", out[0], (E, 3), f64), ("out[1]", out[1], (E, 3), f64)]
+    dev = _device_tensors(specs)
+
+    def alloc():
+        return tuple(out) if out is not None else (torch.empty((E, 3), dtype=torch.float64, device=dev),
+                                                   torch.empty((E, 3), dtype=torch.float64, device=dev))
+
+    def call(o, s):
+        io = SrbdVmBatchIo(lin=lin.data_ptr(), ang=ang.data_ptr(), feet=feet.data_ptr(), hips=hips.data_ptr(),
+                           max_distance=limit, lin_out=o[0].data_ptr(), ang_out=o[1].data_ptr())
+        return lib.srbd_vm_modulate_device(E, C.byref(io), s)
+
+    return _enqueue(dev, stream, alloc, call, "srbd_vm_modulate_device")
+
+
+TERRAIN_EST_BYTES = C.sizeof(SrbdTerrainEst)
+
+
+def terrain_ref_step_device(terrain, base_pos, com_pos, yaws, lin, ang, ref, ref_z: float, *, lift_off=None, frg=None,
+                            com_pos_offset_w=None, out=None, stream=None):
+    """srbd_terrain_ref_step_device: the terrain estimate and entries 0..11 of the reference row of every environment,
+    one launch enqueued on ``stream`` (None: torch's current stream) without a host synchronisation.
+    terrain (E, TERRAIN_EST_BYTES) uint8: the srbd_terrain_est structs, advanced in place.  base_pos / com_pos / lin /
+    ang (E, 3), yaws (E,) float64; lin and ang are the modulated command.  Exactly one of lift_off (E, 4, 3) float64 and
+    frg (E, FRG_BYTES) uint8, the foothold reference generator's state, whose lift-off table is read.  ref (E, 24)
+    float64, ``prepare_state_and_reference_device``'s ref_in: entries 0..11 of each row are written, 12..23 left alone.
+    Optional: com_pos_offset_w (E, 3) float64; out (E, 3) float64, which receives roll, pitch and height.  Returns
+    ``out`` (None when not given)."""
+    import math
+
+    import torch
+
+    E = int(terrain.shape[0]) if isinstance(terrain, torch.Tensor) and terrain.dim() == 2 else 0
+    if not 1 <= E <= MAX_ENVS:
+        raise ValueError(f"the estimator state must be (1..{MAX_ENVS}, {TERRAIN_EST_BYTES}) uint8, got "
+                         f"{tuple(getattr(terrain, 'shape', ()))}")
+    z = float(ref_z)
+    if not math.isfinite(z):
+        raise ValueError(f"ref_z must be finite, got {z}")
+    if (lift_off is None) == (frg is None):
+        raise ValueError("give exactly one of lift_off and frg")
+    f64, u8 = (torch.float64,), (torch.uint8,)
+    specs = [("terrain", terrain, (E, TERRAIN_EST_BYTES), u8), ("base_pos", base_pos, (E, 3), f64),
+             ("com_pos", com_pos, (E, 3), f64), ("yaws", yaws, (E,), f64), ("lin", lin, (E, 3), f64),
+             ("ang", ang, (E, 3), f64), ("ref", ref, (E, 24), f64)]
+    if lift_off is not None:
+        specs.append(("lift_off", lift_off, (E, 4, 3), f64))
+    else:
+        specs.append(("frg", frg, (E, FRG_BYTES), u8))
+    for name, t, shape in (("com_pos_offset_w", com_pos_offset_w, (E, 3)), ("out", out, (E, 3))):
+        if t is not None:
+            specs.append((name, t, shape, f64))
+    dev = _device_tensors(specs)
+
+    def ptr(t):
+        return None if t is None else t.data_ptr()
+
+    def call(o, s):
+        io = SrbdTerrainRefBatchIo(base_pos=ptr(base_pos), com_pos=ptr(com_pos),
+                                   com_pos_offset_w=ptr(com_pos_offset_w), yaws=ptr(yaws), lin=ptr(lin), ang=ptr(ang),
+                                   feet=ptr(lift_off), frg=ptr(frg), ref_z=z, ref=ptr(ref), terrain=ptr(o))
+        return lib.srbd_terrain_ref_step_device(terrain.data_ptr(), E, C.byref(io), s)
+
+    return _enqueue(dev, stream, lambda: out, call, "srbd_terrain_ref_step_device")

@@ -135,6 +135,7 @@ simulation_params = {
         "bound": {"step_freq": 1.8, "duty_factor": 0.65, "type": 2},
         "full_stance": {"step_freq": 2, "duty_factor": 0.65, "type": 7},
     },
+    "velocity_modulator": True,  # config.py:260
     "ref_z": hip_height,
     "mpc_frequency": 100,
     "use_inertia_recomputation": True,
