@@ -17,6 +17,11 @@
  *                                       WBInterface.compute_stance_and_swing_torque
  *                                       quadruped_pympc/helpers/swing_trajectory_controller.py:5-146
  *                                       quadruped_pympc/interfaces/wb_interface.py:369-415, :435-465
+ *   srbd_stc_touch_down / srbd_gait_apply_freq
+ *                                    <- SwingTrajectoryController.check_touch_down_condition and the step-frequency
+ *                                       write-back of WBInterface.compute_stance_and_swing_torque
+ *                                       quadruped_pympc/helpers/swing_trajectory_controller.py:148-165
+ *                                       quadruped_pympc/interfaces/wb_interface.py:354-358
  *   srbd_vm_modulate / srbd_terrain_est_init / srbd_terrain_estimate / srbd_reference_assemble
  *                                    <- VelocityModulator, TerrainEstimator and the reference row of
  *                                       WBInterface.update_state_and_reference
@@ -166,8 +171,9 @@ int srbd_frg_mean(const srbd_frg* g, double mean_out[2]);
  * feedback-linearisation term reduces to the bias force.
  * Out of scope: the early-stance detector (neither generator reads its hit moment or hit point, and
  * reflex_next_steps_height_enhancement is off by default: it changes no output of this path), inverse kinematics and
- * des_joints_pos, the kinodynamic branch, the 'scipy' generator, and the re-timing from optimize_swing /
- * best_sample_freq (wb_interface.py:354-358; srbd_stc_set_timing is the call it would make). */
+ * des_joints_pos, the kinodynamic branch and the 'scipy' generator.  The re-timing from optimize_swing /
+ * best_sample_freq (wb_interface.py:354-358) is not part of srbd_stc_step: srbd_stc_touch_down and srbd_gait_apply_freq
+ * below are its trigger and its write-back (srbd_stc_set_timing is the call it would make for the swing period). */
 enum { SRBD_SWING_BEZIER_REF = 0, SRBD_SWING_EXPLICIT = 1 };
 typedef struct srbd_stc {
     double step_height, swing_period, position_gain_fb, velocity_gain_fb;
@@ -230,6 +236,35 @@ int srbd_stc_step(srbd_stc* g, const srbd_stc_io* io, double dt);
 int srbd_stc_apex(const srbd_stc* g, const double contact[4], double interval);
 /* 1 if no contact equals 0, else 0; negative: NULL. */
 int srbd_stc_full_stance(const double contact[4]);
+
+/* ---- Gait adaptation (mpc_params['optimize_step_freq']): when to optimise the step frequency, and what the sampler's
+ * best frequency re-times (csrc/srbd_gait_adapt.h, which the device forms srbd_stc_touch_down_device and
+ * srbd_gait_apply_freq_device of srbd_mpc.h compile too).
+ *   srbd_stc_touch_down   <- SwingTrajectoryController.check_touch_down_condition
+ *                            quadruped_pympc/helpers/swing_trajectory_controller.py:148-165 (called wb_interface.py:298)
+ *   srbd_gait_apply_freq  <- WBInterface.compute_stance_and_swing_torque, quadruped_pympc/interfaces/wb_interface.py:354-358
+ * srbd_stc_touch_down, statement for statement: *rising_edge (the reference's rising_edge_detected, caller-owned, 0
+ * at start) is set when all four current_contact == 1 and not all four previous_contact == 1; stable = every entry of
+ * columns 0..lookahead-1 of the 4 x horizon contact sequence (row l at contact_sequence + l * contact_stride) == 1;
+ * next_lift = not every entry of column `lookahead` == 1; when the edge is set, stable and next_lift all hold the edge
+ * is cleared and 1 returned, else 0.  The comparisons are `== 1` as in the reference (a contact of 2.0 or NaN is not
+ * stance).  SRBD_E_INVALID (nothing written): a NULL pointer, contact_stride < horizon, lookahead outside
+ * 1..horizon-1 (where the reference raises IndexError; its default is 3).
+ * srbd_gait_apply_freq: with optimize != 1 nothing is written and 0 is returned.  Otherwise pgg->step_freq =
+ * best_freq, frg->stance_time = (1 / f) * duty and stc->swing_period = (1 - duty) * (1 / f) with duty =
+ * pgg->duty_factor, stc->step_height unchanged, and 1 is returned.  best_freq is the float32 scalar the sampler
+ * returns, and the two products are float32 products as the reference forms them under NumPy 2 (NEP 50: Python scalars
+ * do not widen a float32): inv = 1.0f / f, stance = inv * (float)duty, swing = (float)(1.0 - duty) * inv, each widened
+ * exactly to the struct's double -- the recorded reference values bit for bit.  frg and stc may each be NULL.  A
+ * best_freq that is zero, negative or not finite, or a duty factor that leaves a swing period srbd_stc_set_timing
+ * refuses, leaves all three structs untouched and returns 0 (the reference would divide and store the result).
+ * SRBD_E_INVALID: a NULL pgg.  Deviation: see csrc/srbd_gait_adapt.h on the reference's float32 phase increment after
+ * its first write-back; srbd_pgg_run is unchanged. */
+int srbd_stc_touch_down(int32_t* rising_edge, const double current_contact[4], const double previous_contact[4],
+                        const double* contact_sequence /* 4 x contact_stride */, int32_t contact_stride,
+                        int32_t horizon, int32_t lookahead);
+int srbd_gait_apply_freq(srbd_pgg* pgg, srbd_frg* frg /* or NULL */, srbd_stc* stc /* or NULL */, int32_t optimize,
+                         float best_freq);
 
 /* ---- Velocity modulator, terrain estimator and the reference row's first twelve entries: what
  * WBInterface.update_state_and_reference builds every control step from the velocity command, before and after the

@@ -848,6 +848,78 @@ typedef struct srbd_terrain_ref_batch_io {
 int srbd_terrain_ref_step_device(struct srbd_terrain_est* d_terrain, int32_t num_envs,
                                  const srbd_terrain_ref_batch_io* io, void* hip_stream);
 
+/* The gait adaptation loop of the device-resident step (mpc_params['optimize_step_freq']): the trigger that decides
+ * per environment and step whether to optimise the step frequency, the device form of srbd_batch_set_gait, and the
+ * write-back of the sampler's best frequency, so that run -> contact sequence -> trigger -> set gait ->
+ * srbd_batch_step_device -> write-back never leaves the GPU.  Reference lines restated per environment:
+ *   srbd_stc_touch_down_device  <- SwingTrajectoryController.check_touch_down_condition
+ *                                  swing_trajectory_controller.py:148-165 (called wb_interface.py:298)
+ *   srbd_batch_set_gait_device  <- the gait arguments of the gait-adaptive compute_control and its candidate set,
+ *                                  centroidal_nmpc_jax_gait_adaptive.py:687-692 (random sampling), :834-838 (MPPI)
+ *   srbd_gait_apply_freq_device <- wb_interface.py:354-358
+ *   srbd_stc_touch_down_device: d_rising_edge (num_envs int32, caller-owned state, zero at start) is the reference's
+ *   rising_edge_detected per environment; d_current, d_previous num_envs x 4 float32 as srbd_pgg_run_device writes
+ *   them; d_contacts num_envs x 4 x contact_stride float32 as srbd_pgg_contact_sequence_device writes them, the first
+ *   `horizon` columns read; d_optimize (num_envs int32) receives 0 or 1.  One lane per environment.
+ *   srbd_gait_apply_freq_device: d_pgg, d_frg, d_stc are the device state arrays of srbd_pgg_run_device,
+ *   srbd_frg_step_device and srbd_stc_step_device; d_frg and d_stc may each be NULL, for a caller that keeps only
+ *   some of the stages.  d_optimize is the trigger's output, d_best_freq (num_envs float32) the best_freq array of
+ *   srbd_batch_step_device.  One lane per environment.  An environment with d_optimize[e] != 1, or with a best
+ *   frequency that is zero, negative or not finite, is left untouched.
+ *   srbd_batch_set_gait_device is the device form of srbd_batch_set_gait: the gait fields of every environment's step
+ *   input are written by one launch from device arrays, and the next enqueued step runs the gait-adaptive rollout.
+ *   The leg phases come from exactly one of io->pgg (the device state of srbd_pgg_run_device: phase_signal[l] rounded
+ *   to float32, round to nearest, as np.asarray(timing, dtype=float32) rounds it) or io->timings (num_envs x 4
+ *   float32).  The nominal step frequency comes from io->nominal_freqs (num_envs float32) when given, else from
+ *   io->pgg's step_freq rounded to float32; io->timings without io->nominal_freqs is refused.  Environment e's
+ *   candidate set is formed as the reference forms it: MPPI takes available[0..n_freq); random sampling takes them
+ *   when optimize[e] != 0 and n_freq copies of the nominal frequency otherwise.  available, n_freq, pgg_dt and
+ *   duty_factor travel by value and are shared.  io->freq_rows (num_envs x N float32 device memory, or NULL) are
+ *   injected per-sample frequencies (the parity mode): the launch copies environment e's N rows into the batch's
+ *   frequency array.  That array is allocated on the first call that needs it; that first call may block (a
+ *   hipMalloc), every other call does not.
+ *   Equivalence: environment e after these calls holds, byte for byte, what the host calls leave: d_optimize[e] and
+ *   d_rising_edge[e] are srbd_stc_touch_down's (srbd_host.h) for the contacts widened to double; d_pgg[e], d_frg[e],
+ *   d_stc[e] hold the bytes srbd_gait_apply_freq leaves.  A srbd_batch_step_device after srbd_batch_set_gait_device
+ *   returns, bit for bit, what it returns after srbd_batch_set_gait with the same values (timings the float32 phases,
+ *   freq_sets[e] the set formed as above, the same freq_rows), best_freq included.
+ *   Enqueue contract: each call enqueues exactly one launch on hip_stream and returns; it makes no synchronising HIP
+ *   call and touches no device memory from the host (the first srbd_batch_set_gait_device with freq_rows excepted, as
+ *   said).  srbd_stc_touch_down_device and srbd_gait_apply_freq_device read the stream handle as
+ *   srbd_prepare_state_device reads it (NULL and hipStreamLegacy both select the legacy null stream), use none of a
+ *   batch's buffers and enter no ordering rule.  srbd_batch_set_gait_device reads it as srbd_batch_step_device does
+ *   (NULL: the batch's own stream; the legacy null stream by hipStreamLegacy) and joins the batch's event protocol as
+ *   a device step does: it makes its stream wait on the event of the last device call on another stream and records
+ *   the event behind its launch, so a set on stream A followed by srbd_batch_step_device on stream B is ordered
+ *   exactly as two device steps are.  It sets the batch's gait-adaptive mode on the host at once.
+ *   Stale staging: after srbd_batch_set_gait_device the host staging of the gait fields is stale.  Until
+ *   srbd_batch_set_gait or srbd_batch_clear_gait is called, srbd_batch_step (the host step) returns SRBD_E_INVALID
+ *   with a message naming those two calls, and changes nothing.  srbd_batch_step_device is not affected.
+ *   SRBD_E_INVALID (before any HIP call): a NULL required pointer (d_frg, d_stc, io->freq_rows and one of io->pgg /
+ *   io->timings excepted); num_envs outside 1..4096; horizon outside 2..SRBD_MAX_HORIZON; contact_stride < horizon;
+ *   lookahead outside 1..horizon-1; both or neither of io->pgg and io->timings; io->timings without
+ *   io->nominal_freqs; and srbd_batch_set_gait's refusals: n_freq outside 1..SRBD_MAX_FREQS, num_splines + 1 > 33,
+ *   the opt-in cost terms active.  A failed launch: SRBD_E_HIP, or SRBD_E_NODEVICE where no device exists. */
+struct srbd_stc;
+typedef struct srbd_batch_gait_io {
+    const struct srbd_pgg* pgg;        /* E device structs, or NULL when timings is given */
+    const float* timings;              /* E x 4 leg phases, or NULL when pgg is given */
+    const float* nominal_freqs;        /* E, or NULL: pgg's step_freq rounded to float32 */
+    const int32_t* optimize;           /* E: the trigger's flags */
+    const float* freq_rows;            /* E x N injected frequencies, or NULL: device draws */
+    float available[SRBD_MAX_FREQS];   /* the configured candidates, n_freq used */
+    int32_t n_freq;
+    float pgg_dt, duty_factor;
+    int32_t pad;
+} srbd_batch_gait_io;
+int srbd_stc_touch_down_device(int32_t* d_rising_edge, int32_t num_envs, const float* d_current,
+                               const float* d_previous, const float* d_contacts, int32_t contact_stride,
+                               int32_t horizon, int32_t lookahead, int32_t* d_optimize, void* hip_stream);
+int srbd_batch_set_gait_device(srbd_batch* b, const srbd_batch_gait_io* io, void* hip_stream);
+int srbd_gait_apply_freq_device(struct srbd_pgg* d_pgg, struct srbd_frg* d_frg, struct srbd_stc* d_stc,
+                                int32_t num_envs, const int32_t* d_optimize, const float* d_best_freq,
+                                void* hip_stream);
+
 /* Diagnostic: enable != 0 stamps the phases of the following TAMOLS calls; out_us[5] (may be NULL)
  * receives the last call's mean per-block durations of (patch, queries, scores, slice argmin + count)
  * and the span from the first block's start to the last leg's end, in us.  enable == 0 turns it off. */

@@ -19,6 +19,7 @@
 
 #include <rccl/rccl.h>  // types only: RCCL is dlopen'ed (the caller's copy, e.g. torch's)
 
+#include "srbd_gait_adapt.h"
 #include "srbd_jaxrng.h"
 #include "srbd_launch.h"
 
@@ -1130,22 +1131,23 @@ static void drop_graphs(srbd_ctx* c) {
     xg_drop_graphs(c);
 }
 
-// The gait fields of one StepInput (srbd_set_gait, srbd_batch_set_gait); fill_input leaves them as they are.
-static void fill_gait(const ModelConst& mc, StepInput* in, const float* timing, float pgg_dt, float duty_factor,
-                      const float* freq_set, int n_freq, bool explicit_rows) {
-    for (int l = 0; l < 4; ++l) in->ga_timing[l] = timing[l];
-    in->ga_dt = pgg_dt;
-    in->ga_duty = duty_factor;
-    in->ga_nfreq = n_freq;
-    for (int i = 0; i < SRBD_MAX_FREQS; ++i) in->ga_freqs[i] = i < n_freq ? freq_set[i] : 0.0f;
-    // chunk boundaries float32(linspace(0, H, S+1)) as spline_coef forms them; integer steps compare
-    // >= a boundary exactly when they are >= its ceiling
+// Chunk boundaries float32(linspace(0, H, S+1)) as spline_coef forms them; integer steps compare >= a boundary exactly
+// when they are >= its ceiling.
+static void ga_chunk_bounds(const ModelConst& mc, int32_t* cb /* GA_MAXCB */) {
     for (int i = 0; i < GA_MAXCB; ++i) {
         const int S = mc.S > 0 ? mc.S : 1;
-        const float cb = (float)((double)mc.H * (double)i / (double)S);
-        in->ga_cb[i] = i <= S ? (int)ceilf(cb) : 1 << 30;
+        const float b = (float)((double)mc.H * (double)i / (double)S);
+        cb[i] = i <= S ? (int)ceilf(b) : 1 << 30;
     }
-    in->ga_explicit = explicit_rows ? 1 : 0;
+}
+
+// The gait fields of one StepInput (srbd_set_gait, srbd_batch_set_gait); fill_input leaves them as they are.  The
+// stores are srbd_gait_adapt.h's, which batch_set_gait_kernel compiles too.
+static void fill_gait(const ModelConst& mc, StepInput* in, const float* timing, float pgg_dt, float duty_factor,
+                      const float* freq_set, int n_freq, bool explicit_rows) {
+    int32_t cb[GA_MAXCB];
+    ga_chunk_bounds(mc, cb);
+    ga_write_fields(in, timing, pgg_dt, duty_factor, freq_set, n_freq, cb, GA_MAXCB, explicit_rows);
 }
 
 extern "C" int srbd_set_gait(srbd_ctx* c, const float* timing, float pgg_dt, float duty_factor, const float* freq_set,
@@ -2660,6 +2662,9 @@ struct srbd_batch {
     hipEvent_t dev_done = nullptr;
     hipStream_t dev_stream = nullptr;
     bool dev_pending = false;
+    // srbd_batch_set_gait_device wrote d_in's gait fields past the staging: the host step, which copies the staging
+    // over them, is refused until srbd_batch_set_gait or srbd_batch_clear_gait
+    bool ga_staging_stale = false;
 };
 
 // The internal buffers (d_in, d_noise, d_rec, d_costs, d_count, d_ga_freq) are shared by the host path and the device
@@ -2838,6 +2843,62 @@ extern "C" int srbd_batch_set_gait(srbd_batch* b, const float* timings, float pg
     HIP_TRY(c, hipMemcpy2D((char*)b->d_in + G0, sizeof(StepInput), (const char*)b->h_in + G0, sizeof(StepInput),
                            G1 - G0, E, hipMemcpyHostToDevice));
     mc.ga = 1;
+    b->ga_staging_stale = false;
+    return SRBD_OK;
+}
+
+// srbd_batch_set_gait with every per-environment value in the caller's device memory, enqueued on the caller's stream:
+// batch_set_gait_kernel writes d_in[e]'s gait fields as fill_gait writes the staging's (the same stores,
+// srbd_gait_adapt.h) and copies the injected rows.  No synchronising call: the launch joins the device steps' event
+// protocol, so it follows the last device step's reads of d_in and d_ga_freq and the next device step follows it.
+extern "C" int srbd_batch_set_gait_device(srbd_batch* b, const srbd_batch_gait_io* io, void* hip_stream) {
+    srbd_ctx* c = b ? &b->c : nullptr;
+    if (!io) return fail(c, SRBD_E_INVALID, "srbd_batch_set_gait_device: null io");
+    if (!io->optimize) return fail(c, SRBD_E_INVALID, "srbd_batch_set_gait_device: null required pointer: optimize");
+    if ((io->pgg != nullptr) == (io->timings != nullptr))
+        return fail(c, SRBD_E_INVALID, "srbd_batch_set_gait_device: exactly one of pgg and timings must be given");
+    if (!io->pgg && !io->nominal_freqs)
+        return fail(c, SRBD_E_INVALID, "srbd_batch_set_gait_device: timings need nominal_freqs");
+    if (io->n_freq < 1 || io->n_freq > SRBD_MAX_FREQS)
+        return fail(c, SRBD_E_INVALID, "n_freq must be in [1, " + std::to_string(SRBD_MAX_FREQS) + "]");
+    if (!b) return fail(nullptr, SRBD_E_INVALID, "srbd_batch_set_gait_device: null batch");
+    ModelConst& mc = c->mc;
+    if (mc.kind != SRBD_ZERO_ORDER && mc.S + 1 > GA_MAXCB) return fail(c, SRBD_E_INVALID, "num_splines > 32");
+    if (mc.cost_on)
+        return fail(c, SRBD_E_INVALID,
+                    "gait-adaptive sampling with the opt-in cost terms has no batch form (one context runs it on its "
+                    "thread-per-sample kernel): clear the cost weights first, or use separate contexts");
+    HIP_TRY(c, hipSetDevice(c->cfg.device_id));
+    hipStream_t s = (hipStream_t)hip_stream;  // as srbd_batch_step_device reads it
+    if (!s) s = c->stream;
+    else if (s == hipStreamLegacy) s = nullptr;
+    const size_t E = (size_t)b->E, ldn = (size_t)mc.ldn;
+    // the previous device call on another stream still reads d_in and d_ga_freq
+    if (b->dev_pending && b->dev_stream != s) HIP_TRY(c, hipStreamWaitEvent(s, b->dev_done, 0));
+    if (io->freq_rows && !b->d_ga_freq) {  // the one call that may block: the allocation
+        float* d = nullptr;
+        hipError_t e = hipMalloc((void**)&d, sizeof(float) * E * ldn);
+        if (e == hipSuccess && (e = hipMemsetAsync(d, 0, sizeof(float) * E * ldn, s)) != hipSuccess) (void)hipFree(d);
+        if (e != hipSuccess)
+            return fail(c, e == hipErrorOutOfMemory ? SRBD_E_NOMEM : SRBD_E_HIP,
+                        std::string("hipMalloc: ") + hipGetErrorString(e));
+        b->d_ga_freq = d;
+    }
+    BatchGaitJob j = {};
+    j.io = *io;
+    ga_chunk_bounds(mc, j.cb);
+    j.random_sampling = mc.method == SRBD_RANDOM_SAMPLING;
+    j.N = mc.n_local;
+    j.ldn = mc.ldn;
+    launch_batch_set_gait(j, b->d_in, b->d_ga_freq, b->E, s);
+    const hipError_t le = hipGetLastError();
+    const hipError_t re = hipEventRecord(b->dev_done, s);
+    b->dev_stream = s;
+    b->dev_pending = re == hipSuccess;
+    HIP_TRY(c, le);
+    HIP_TRY(c, re);
+    mc.ga = 1;
+    b->ga_staging_stale = true;
     return SRBD_OK;
 }
 
@@ -2850,6 +2911,7 @@ extern "C" int srbd_batch_clear_gait(srbd_batch* b) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         c->mc.ga = 0;
     }
+    b->ga_staging_stale = false;  // the gait fields are not read again until a set call rewrites them
     return SRBD_OK;
 }
 
@@ -2899,6 +2961,11 @@ extern "C" int srbd_batch_step(srbd_batch* b, const float* states, const float* 
     const ModelConst& mc = c->mc;
     if (!states || !refs || !contacts || !best_params || !seeds || !counters || !out || contact_stride < mc.H)
         return fail(c, SRBD_E_INVALID, "invalid step arguments");
+    if (b->ga_staging_stale)
+        return fail(c, SRBD_E_INVALID,
+                    "srbd_batch_step: the gait fields were last set on the device (srbd_batch_set_gait_device) and the "
+                    "host staging is stale: call srbd_batch_set_gait or srbd_batch_clear_gait first, or step with "
+                    "srbd_batch_step_device");
     HIP_TRY(c, hipSetDevice(c->cfg.device_id));
     if (b->dev_pending) {  // a device step in flight on another stream: this step's launches follow it
         HIP_TRY(c, hipStreamWaitEvent(c->stream, b->dev_done, 0));

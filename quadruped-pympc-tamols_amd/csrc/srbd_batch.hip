@@ -17,9 +17,13 @@
 // The device-resident step (srbd_batch_step_device) replaces the input copy and the host's read of out[e]:
 //   batch_pack_kernel       in[e] from the caller's device arrays, as fill_input (srbd_api.hip) builds it on the host
 //   batch_unpack_kernel     out[e] (device memory on this path) and the costs row -> the caller's device arrays
+// The device form of srbd_batch_set_gait (srbd_batch_set_gait_device):
+//   batch_set_gait_kernel   the gait fields of in[e] from the caller's device arrays, as fill_gait (srbd_api.hip)
+//                           writes them on the host, and the injected frequency rows into the batch's array
 #include <algorithm>
 
 #include "srbd_device.h"
+#include "srbd_gait_adapt.h"
 #include "srbd_merge.h"
 #include "srbd_quad.h"
 
@@ -117,6 +121,28 @@ __global__ void __launch_bounds__(256) batch_unpack_kernel(const srbd_batch_devi
     }
     if (io.costs)
         for (int i = tid; i < N; i += 256) io.costs[(size_t)e * N + i] = costs_arr[(size_t)e * ldn + i];
+}
+
+// fill_gait (srbd_api.hip) on the device, one block per environment: thread 0 forms environment e's candidate set
+// (ga_freq_set) and writes the gait fields of in[e] through the function the host compiles (ga_write_fields), so they
+// are the host path's bytes; nothing else of in[e] is written.  With injected frequencies every thread copies rows
+// k = tid, tid + blockDim.x, ... < N of freq_rows[e] to ga_freq[e ldn + k]; the padding rows N .. ldn stay zero.
+__global__ void __launch_bounds__(256) batch_set_gait_kernel(const BatchGaitJob j, StepInput* __restrict__ in_arr,
+                                                             float* __restrict__ ga_freq) {
+    const int e = blockIdx.x, tid = threadIdx.x;
+    if (tid == 0) {
+        float timing[4], set[SRBD_MAX_FREQS];
+#pragma unroll
+        for (int l = 0; l < 4; ++l)
+            timing[l] = j.io.pgg ? (float)j.io.pgg[e].phase_signal[l] : j.io.timings[4 * (size_t)e + l];
+        const float nominal = j.io.nominal_freqs ? j.io.nominal_freqs[e] : (float)j.io.pgg[e].step_freq;
+        ga_freq_set(j.random_sampling, j.io.optimize[e], nominal, j.io.available, j.io.n_freq, set);
+        ga_write_fields(in_arr + e, timing, j.io.pgg_dt, j.io.duty_factor, set, j.io.n_freq, j.cb, GA_MAXCB,
+                        j.io.freq_rows != nullptr);
+    }
+    if (j.io.freq_rows)
+        for (int k = tid; k < j.N; k += blockDim.x)
+            ga_freq[(size_t)e * j.ldn + k] = j.io.freq_rows[(size_t)e * j.N + k];
 }
 
 __global__ void __launch_bounds__(256) batch_rng_kernel(const ModelConst mc, const StepInput* __restrict__ in,
@@ -588,6 +614,11 @@ void launch_batch_unpack(const ModelConst& mc, const srbd_batch_device_io& io, c
                          const float* costs, int E, hipStream_t s) {
     const int vec = aligned16(io.best_params) && aligned16(io.grf) && aligned16(io.predicted_state);
     hipLaunchKernelGGL(batch_unpack_kernel, dim3(E), dim3(256), 0, s, io, out, costs, mc.P, mc.n_local, mc.ldn, vec);
+}
+
+void launch_batch_set_gait(const BatchGaitJob& j, StepInput* in, float* ga_freq, int E, hipStream_t s) {
+    // one wave per environment for the fields alone; four when N rows are copied besides
+    hipLaunchKernelGGL(batch_set_gait_kernel, dim3(E), dim3(j.io.freq_rows ? 256 : 64), 0, s, j, in, ga_freq);
 }
 
 void launch_batch_rng(const ModelConst& mc, const StepInput* in, float* noise, int E, hipStream_t s) {

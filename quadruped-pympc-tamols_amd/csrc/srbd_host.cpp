@@ -15,6 +15,7 @@
 #include "../../include/srbd_host.h"
 #include "../../include/srbd_mpc.h"
 #include "srbd_frg.h"
+#include "srbd_gait_adapt.h"
 #include "srbd_jaxrng.h"
 #include "srbd_stc.h"
 #include "srbd_terrain.h"
@@ -297,6 +298,22 @@ extern "C" int srbd_stc_apex(const srbd_stc* g, const double contact[4], double 
 extern "C" int srbd_stc_full_stance(const double contact[4]) {  // STC:140-146
     if (!contact) return SRBD_E_INVALID;
     return srbd::stc_full_stance(contact);
+}
+
+// ------------------------------------------- gait adaptation: trigger and frequency write-back (srbd_gait_adapt.h)
+extern "C" int srbd_stc_touch_down(int32_t* rising_edge, const double current_contact[4],
+                                   const double previous_contact[4], const double* contact_sequence,
+                                   int32_t contact_stride, int32_t horizon, int32_t lookahead) {  // STC:148-165
+    if (!rising_edge || !current_contact || !previous_contact || !contact_sequence) return SRBD_E_INVALID;
+    if (horizon < 2 || contact_stride < horizon || lookahead < 1 || lookahead > horizon - 1) return SRBD_E_INVALID;
+    return srbd::ga_touch_down(rising_edge, current_contact, previous_contact, contact_sequence, contact_stride,
+                               lookahead);
+}
+
+extern "C" int srbd_gait_apply_freq(srbd_pgg* pgg, srbd_frg* frg, srbd_stc* stc, int32_t optimize,
+                                    float best_freq) {  // WBI:354-358
+    if (!pgg) return SRBD_E_INVALID;
+    return srbd::ga_apply_freq(pgg, frg, stc, optimize, best_freq);
 }
 
 // ------------------------------------------- velocity modulator, terrain estimator, reference row (srbd_terrain.h)

@@ -174,6 +174,14 @@ void launch_batch_pack(const ModelConst& mc, const float* q_feet, const srbd_bat
                        hipStream_t s);
 void launch_batch_unpack(const ModelConst& mc, const srbd_batch_device_io& io, const StepOutput* out,
                          const float* costs, int E, hipStream_t s);
+// srbd_batch_set_gait_device: the caller's io by value, the chunk boundaries ga_chunk_bounds formed on the host and the
+// shapes; in[e]'s gait fields, and with io.freq_rows environment e's N rows into ga_freq at stride ldn
+struct BatchGaitJob {
+    srbd_batch_gait_io io;
+    int32_t cb[GA_MAXCB];
+    int32_t random_sampling, N, ldn;
+};
+void launch_batch_set_gait(const BatchGaitJob& j, StepInput* in, float* ga_freq, int E, hipStream_t s);
 // environment e's draws keyed by in[e]'s seed and counter (rng_items)
 void launch_batch_rng(const ModelConst& mc, const StepInput* in, float* noise, int E, hipStream_t s);
 // injected noise, E x n_local x P row-major -> SoA per environment

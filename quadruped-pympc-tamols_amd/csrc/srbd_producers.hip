@@ -25,6 +25,10 @@
 // terrain estimate and entries 0..11 of the reference row (srbd_terrain.h; quadruped_pympc/helpers/
 // velocity_modulator.py, terrain_estimator.py, wb_interface.py:168-172, :250-291).  Both spread an environment over
 // its quad and exchange values by shuffles (see the kernels).
+// touch_down_kernel (srbd_stc_touch_down_device) and gait_apply_freq_kernel (srbd_gait_apply_freq_device) close the gait
+// adaptation loop around the step: the trigger that decides whether to optimise the step frequency and the write-back
+// of the sampler's best frequency (srbd_gait_adapt.h; STC:148-165, wb_interface.py:354-358).  One lane per
+// environment, no cross-lane traffic.
 // srbd_tamols_batch_device, the loop's foothold search, is validated and enqueued here too; its kernel lives with the
 // single-environment one (tamols_kernel.hip tamols_batch_kernel), whose device functions it runs.
 #include <hip/hip_runtime.h>
@@ -33,6 +37,7 @@
 #include "../../include/srbd_host.h"
 #include "../../include/srbd_mpc.h"
 #include "srbd_frg.h"
+#include "srbd_gait_adapt.h"
 #include "srbd_launch.h"
 #include "srbd_stc.h"
 #include "srbd_terrain.h"
@@ -386,6 +391,34 @@ __global__ void __launch_bounds__(PROD_BLOCK) terrain_ref_step_kernel(srbd_terra
     for (int k = 0; k < 3; ++k) row[k] = l == 0 ? out[k] : l == 1 ? out[3 + k] : l == 2 ? out[6 + k] : out[9 + k];
 }
 
+// srbd_stc_touch_down of srbd_host.cpp per environment (srbd_gait_adapt.h ga_touch_down): lane e owns rising_edge[e]
+// and optimize[e] and reads its own 4 + 4 + 4 x (lookahead + 1) contact flags.
+__global__ void __launch_bounds__(PROD_BLOCK) touch_down_kernel(int32_t* __restrict__ rising_edge, int E,
+                                                                const float* __restrict__ current,
+                                                                const float* __restrict__ previous,
+                                                                const float* __restrict__ contacts, int stride,
+                                                                int lookahead, int32_t* __restrict__ optimize) {
+    const int e = blockIdx.x * PROD_BLOCK + threadIdx.x;
+    if (e >= E) return;
+    int32_t edge = rising_edge[e];
+    optimize[e] = ga_touch_down(&edge, current + 4 * (size_t)e, previous + 4 * (size_t)e,
+                                contacts + (size_t)e * 4 * stride, stride, lookahead);
+    rising_edge[e] = edge;
+}
+
+// srbd_gait_apply_freq of srbd_host.cpp per environment (ga_apply_freq): lane e owns the three words it rewrites in
+// pgg[e], frg[e] and stc[e].
+__global__ void __launch_bounds__(PROD_BLOCK) gait_apply_freq_kernel(srbd_pgg* __restrict__ pgg,
+                                                                     srbd_frg* __restrict__ frg,
+                                                                     srbd_stc* __restrict__ stc, int E,
+                                                                     const int32_t* __restrict__ optimize,
+                                                                     const float* __restrict__ best_freq) {
+#pragma clang fp contract(off)
+    const int e = blockIdx.x * PROD_BLOCK + threadIdx.x;
+    if (e >= E) return;
+    ga_apply_freq(pgg + e, frg ? frg + e : nullptr, stc ? stc + e : nullptr, optimize[e], best_freq[e]);
+}
+
 }  // namespace srbd
 
 using namespace srbd;
@@ -515,6 +548,28 @@ extern "C" int srbd_stc_step_device(srbd_stc* d_stc, int32_t num_envs, double dt
     j.full_stance = io->full_stance;
     hipLaunchKernelGGL(stc_step_kernel, dim3(blocks_of(num_envs)), dim3(PROD_BLOCK), 0, stream_of(hip_stream), d_stc,
                        num_envs, j);
+    return launch_status();
+}
+
+extern "C" int srbd_stc_touch_down_device(int32_t* d_rising_edge, int32_t num_envs, const float* d_current,
+                                          const float* d_previous, const float* d_contacts, int32_t contact_stride,
+                                          int32_t horizon, int32_t lookahead, int32_t* d_optimize, void* hip_stream) {
+    if (!d_rising_edge || !d_current || !d_previous || !d_contacts || !d_optimize || !envs_ok(num_envs))
+        return SRBD_E_INVALID;
+    if (horizon < 2 || horizon > SRBD_MAX_HORIZON || contact_stride < horizon) return SRBD_E_INVALID;
+    if (lookahead < 1 || lookahead > horizon - 1) return SRBD_E_INVALID;  // the reference's IndexError
+    hipLaunchKernelGGL(touch_down_kernel, dim3((unsigned)((num_envs + PROD_BLOCK - 1) / PROD_BLOCK)), dim3(PROD_BLOCK),
+                       0, stream_of(hip_stream), d_rising_edge, num_envs, d_current, d_previous, d_contacts,
+                       contact_stride, lookahead, d_optimize);
+    return launch_status();
+}
+
+extern "C" int srbd_gait_apply_freq_device(srbd_pgg* d_pgg, srbd_frg* d_frg, srbd_stc* d_stc, int32_t num_envs,
+                                           const int32_t* d_optimize, const float* d_best_freq, void* hip_stream) {
+    if (!d_pgg || !d_optimize || !d_best_freq || !envs_ok(num_envs)) return SRBD_E_INVALID;
+    hipLaunchKernelGGL(gait_apply_freq_kernel, dim3((unsigned)((num_envs + PROD_BLOCK - 1) / PROD_BLOCK)),
+                       dim3(PROD_BLOCK), 0, stream_of(hip_stream), d_pgg, d_frg, d_stc, num_envs, d_optimize,
+                       d_best_freq);
     return launch_status();
 }
 

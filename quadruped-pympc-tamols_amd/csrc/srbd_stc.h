@@ -18,8 +18,8 @@
 // outputs stay finite and the feedback-linearisation term reduces to the bias force h.
 // Out of scope: the early-stance detector (neither generator here reads its hit moment or hit point, and
 // reflex_next_steps_height_enhancement is off by default, so it changes no output of this path); inverse kinematics
-// and des_joints_pos; the kinodynamic branch; the re-timing from optimize_swing / best_sample_freq (WBI:354-358: the
-// per-environment swing_period and step_height fields and srbd_stc_set_timing leave room for it); the scipy generator.
+// and des_joints_pos; the kinodynamic branch; the scipy generator.  The re-timing from optimize_swing /
+// best_sample_freq (WBI:354-358) lives in srbd_gait_adapt.h.
 #pragma once
 
 #include <math.h>

@@ -93,6 +93,18 @@ class BatchDeviceIO(C.Structure):
     ]
 
 
+MAX_FREQS = 8  # SRBD_MAX_FREQS
+
+
+class BatchGaitIO(C.Structure):
+    """srbd_batch_gait_io (include/srbd_mpc.h): the device arrays and shared values of one srbd_batch_set_gait_device
+    call."""
+    _fields_ = [
+        ("pgg", _P), ("timings", _P), ("nominal_freqs", _P), ("optimize", _P), ("freq_rows", _P),
+        ("available", _F * MAX_FREQS), ("n_freq", _I), ("pgg_dt", _F), ("duty_factor", _F), ("pad", _I),
+    ]
+
+
 class TamolsBatchIO(C.Structure):
     """srbd_tamols_batch_io (include/srbd_mpc.h): the device arrays of one srbd_tamols_batch_device call."""
     _fields_ = [
@@ -269,6 +281,8 @@ SIGNATURES.update({
     "srbd_stc_step": (_I, [C.POINTER(SrbdStc), C.POINTER(SrbdStcIo), _D]),
     "srbd_stc_apex": (_I, [C.POINTER(SrbdStc), _DP, _D]),
     "srbd_stc_full_stance": (_I, [_DP]),
+    "srbd_stc_touch_down": (_I, [_IP, _DP, _DP, _DP, _I, _I, _I]),
+    "srbd_gait_apply_freq": (_I, [C.POINTER(SrbdPgg), C.POINTER(SrbdFrg), C.POINTER(SrbdStc), _I, _F]),
     "srbd_vm_modulate": (_I, [_D, _DP, _DP, _DP, _DP, _DP, _DP]),
     "srbd_terrain_est_init": (_I, [C.POINTER(SrbdTerrainEst)]),
     "srbd_terrain_estimate": (_I, [C.POINTER(SrbdTerrainEst), _DP, _D, _DP, _DP]),
@@ -316,6 +330,10 @@ SIGNATURES.update({
     "srbd_stc_step_device": (_I, [_P, _I, _D, C.POINTER(SrbdStcBatchIo), _P]),
     "srbd_vm_modulate_device": (_I, [_I, C.POINTER(SrbdVmBatchIo), _P]),
     "srbd_terrain_ref_step_device": (_I, [_P, _I, C.POINTER(SrbdTerrainRefBatchIo), _P]),
+    # the gait adaptation loop: trigger, device form of srbd_batch_set_gait, frequency write-back
+    "srbd_stc_touch_down_device": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _P, _P]),
+    "srbd_batch_set_gait_device": (_I, [_P, C.POINTER(BatchGaitIO), _P]),
+    "srbd_gait_apply_freq_device": (_I, [_P, _P, _P, _I, _P, _P, _P]),
 })
 
 # srbd_time_launch kinds (include/srbd_mpc.h)
@@ -855,6 +873,52 @@ class BatchContext:
         """srbd_batch_clear_gait: back to the caller's contact sequences (best_freq 0)."""
         self.check(lib.srbd_batch_clear_gait(self.h), "srbd_batch_clear_gait")
 
+    def set_gait_device(self, optimize, available, pgg_dt: float, duty: float, *, pgg=None, timings=None,
+                        nominal_freqs=None, freq_rows=None, stream=None):
+        """srbd_batch_set_gait_device: ``set_gait`` from torch tensors of the context's device, one launch enqueued on
+        ``stream`` (None: ``torch.cuda.current_stream()``) without a host synchronisation; the following
+        ``step_device`` runs the gait-adaptive rollout.  optimize (E,) int32, the trigger's flags; available: the
+        configured candidate frequencies (a host sequence of 1..8, shared).  The leg phases come from exactly one of
+        ``pgg`` -- the (E, PGG_BYTES) uint8 state of a ``BatchedPeriodicGaitGenerator`` -- and ``timings`` (E, 4)
+        float32; the nominal step frequencies from ``nominal_freqs`` (E,) float32 when given, else from ``pgg``.
+        freq_rows None (device draws) or (E, N) float32 injected per-sample frequencies.  Each environment's
+        candidate set is formed on the device as ``Sampling_MPC._freq_set`` forms it.  After this call the host
+        ``step`` is refused until ``set_gait`` or ``clear_gait`` (the host staging is stale); ``step_device`` is
+        not."""
+        import torch
+
+        E = self.E
+        dev = torch.device("cuda", self.cfg.device_id)
+        av = np.ascontiguousarray(available, dtype=np.float32).reshape(-1)
+        if not 1 <= av.size <= MAX_FREQS:
+            raise ValueError(f"available must hold 1..{MAX_FREQS} candidate frequencies, got {av.size}")
+        if (pgg is None) == (timings is None):
+            raise ValueError("exactly one of pgg and timings must be given")
+        if pgg is None and nominal_freqs is None:
+            raise ValueError("timings need nominal_freqs")
+        f32_, i32, u8 = (torch.float32,), (torch.int32,), (torch.uint8,)
+        specs = [("optimize", optimize, (E,), i32)]
+        for name, t, shape, dt in (("pgg", pgg, (E, PGG_BYTES), u8), ("timings", timings, (E, 4), f32_),
+                                   ("nominal_freqs", nominal_freqs, (E,), f32_),
+                                   ("freq_rows", freq_rows, (E, self.N), f32_)):
+            if t is not None:
+                specs.append((name, t, shape, dt))
+        _device_tensors(specs)
+        for name, t, _, _ in specs:
+            if t.device != dev:
+                raise ValueError(f"{name} must be on {dev}, got {t.device}")
+
+        def ptr(t):
+            return None if t is None else t.data_ptr()
+
+        io = BatchGaitIO(pgg=ptr(pgg), timings=ptr(timings), nominal_freqs=ptr(nominal_freqs), optimize=ptr(optimize),
+                         freq_rows=ptr(freq_rows), available=(_F * MAX_FREQS)(*av.tolist()), n_freq=int(av.size),
+                         pgg_dt=float(pgg_dt), duty_factor=float(duty), pad=0)
+        s = torch.cuda.current_stream(dev) if stream is None else stream
+        # the null stream by its explicit handle, as in step_device
+        self.check(lib.srbd_batch_set_gait_device(self.h, C.byref(io), C.c_void_p(s.cuda_stream or 1)),
+                   "srbd_batch_set_gait_device")
+
     def set_cost_terms(self, r_force=(0.0, 0.0, 0.0), w_smooth: float = 0.0, w_cone: float = 0.0):
         """srbd_batch_set_cost_terms: the opt-in force regularisation / GRF smoothing / cone-violation terms for every
         environment (all 0: the reference's cost)."""
@@ -896,16 +960,8 @@ class BatchContext:
         self.check(lib.srbd_batch_copy_costs(self.h, out.ctypes.data), "srbd_batch_copy_costs")
         return out
 
-    def step_device(self, states, refs, contacts, best, seeds, counters, *, noise=None, want_costs=False,
-                    stream=None):
-        """srbd_batch_step_device: one step of every environment on torch tensors of the context's device, enqueued
-        on ``stream`` (None: ``torch.cuda.current_stream()``) without a host synchronisation.  states / refs (E, 24),
-        contacts (E, 4, >=H), best (E, P) float32, updated in place; seeds / counters (E,) int64 or uint64
-        (reinterpreted); noise None or (E, N, P) float32.  Every tensor contiguous.  Returns a dict of freshly
-        allocated tensors: grf (E, 12), predicted_state (E, 24), best_cost, best_freq (E,) float32, best_index, status
-        (E,) int32, and costs (E, N) with ``want_costs``.  The values are what ``step`` returns for the same inputs,
-        bit for bit; they are ready in stream order (consume them on ``stream``, or synchronise it).  The inputs are
-        read in stream order too: tensors produced on another stream need the usual event / ``record_stream`` care."""
+    def check_step_device(self, states, refs, contacts, best, seeds, counters, noise=None):
+        """The argument checks of ``step_device`` (ValueError; nothing is enqueued); returns the context's device."""
         import torch
 
         E, H, P, N = self.E, self.cfg.horizon, self.P, self.N
@@ -938,6 +994,22 @@ class BatchContext:
         for name, t in given:  # dtypes and shapes first, so a CPU tensor of the wrong shape is refused for its shape
             if t.device != dev:
                 raise ValueError(f"{name} must be on {dev}, got {t.device}")
+        return dev
+
+    def step_device(self, states, refs, contacts, best, seeds, counters, *, noise=None, want_costs=False,
+                    stream=None):
+        """srbd_batch_step_device: one step of every environment on torch tensors of the context's device, enqueued
+        on ``stream`` (None: ``torch.cuda.current_stream()``) without a host synchronisation.  states / refs (E, 24),
+        contacts (E, 4, >=H), best (E, P) float32, updated in place; seeds / counters (E,) int64 or uint64
+        (reinterpreted); noise None or (E, N, P) float32.  Every tensor contiguous.  Returns a dict of freshly
+        allocated tensors: grf (E, 12), predicted_state (E, 24), best_cost, best_freq (E,) float32, best_index, status
+        (E,) int32, and costs (E, N) with ``want_costs``.  The values are what ``step`` returns for the same inputs,
+        bit for bit; they are ready in stream order (consume them on ``stream``, or synchronise it).  The inputs are
+        read in stream order too: tensors produced on another stream need the usual event / ``record_stream`` care."""
+        import torch
+
+        E, N = self.E, self.N
+        dev = self.check_step_device(states, refs, contacts, best, seeds, counters, noise)
         s = torch.cuda.current_stream(dev) if stream is None else stream
         with torch.cuda.stream(s):  # the outputs belong to the stream that writes them
             out = {"grf": torch.empty((E, 12), dtype=torch.float32, device=dev),
@@ -1236,6 +1308,74 @@ def frg_step_device(frg, base_pos, yaws, base_lin_vel, ref_lin_vel, hips, feet, 
 
     return _enqueue(dev, stream, lambda: torch.empty((E, 4, 3), dtype=torch.float64, device=dev) if out is None
                     else out, call, "srbd_frg_step_device")
+
+
+def stc_touch_down_device(rising_edge, current, previous, contacts, lookahead: int = 3, horizon=None, out=None,
+                          stream=None):
+    """srbd_stc_touch_down_device: ``check_touch_down_condition`` of every environment, one launch enqueued on
+    ``stream`` (None: torch's current stream) without a host synchronisation.  rising_edge (E,) int32, the
+    per-environment state, updated in place; current / previous (E, 4) float32; contacts (E, 4, >=horizon) float32
+    (horizon None: every column); out None (allocated) or (E,) int32.  Returns the flags, (E,) int32."""
+    import torch
+
+    E = int(rising_edge.shape[0]) if isinstance(rising_edge, torch.Tensor) and rising_edge.dim() == 1 else 0
+    if not 1 <= E <= MAX_ENVS:
+        raise ValueError(f"rising_edge must be a torch tensor of shape (1..{MAX_ENVS},), got "
+                         f"{tuple(getattr(rising_edge, 'shape', ()))}")
+    if not isinstance(contacts, torch.Tensor) or contacts.dim() != 3:
+        raise ValueError(f"contacts must be a torch tensor of shape ({E}, 4, >=horizon)")
+    stride = int(contacts.shape[2])
+    H = stride if horizon is None else int(horizon)
+    if not 2 <= H <= MAX_HORIZON or stride < H:
+        raise ValueError(f"horizon must be 2..{MAX_HORIZON} and at most the contacts' {stride} columns, got {H}")
+    if not 1 <= int(lookahead) <= H - 1:
+        raise IndexError(f"lookahead must be 1..{H - 1} (horizon - 1), got {lookahead}")
+    i32, f32_ = (torch.int32,), (torch.float32,)
+    specs = [("rising_edge", rising_edge, (E,), i32), ("current", current, (E, 4), f32_),
+             ("previous", previous, (E, 4), f32_), ("contacts", contacts, (E, 4, stride), f32_)]
+    if out is not None:
+        specs.append(("out", out, (E,), i32))
+    dev = _device_tensors(specs)
+    return _enqueue(
+        dev, stream, lambda: torch.empty(E, dtype=torch.int32, device=dev) if out is None else out,
+        lambda o, s: lib.srbd_stc_touch_down_device(rising_edge.data_ptr(), E, current.data_ptr(), previous.data_ptr(),
+                                                    contacts.data_ptr(), stride, H, int(lookahead), o.data_ptr(), s),
+        "srbd_stc_touch_down_device")
+
+
+def gait_apply_freq_device(pgg, optimize, best_freq, *, frg=None, stc=None, stream=None):
+    """srbd_gait_apply_freq_device: the step-frequency write-back (wb_interface.py:354-358) of every environment, one
+    launch enqueued on ``stream`` without a host synchronisation.  pgg (E, PGG_BYTES) uint8, and optionally frg
+    (E, FRG_BYTES) and stc (E, STC_BYTES) uint8: the device states, rewritten in place where optimize[e] == 1 and
+    best_freq[e] is positive and finite.  optimize (E,) int32, best_freq (E,) float32."""
+    import torch
+
+    E = _num_envs_of(pgg)
+    u8 = (torch.uint8,)
+    specs = [("pgg", pgg, (E, PGG_BYTES), u8), ("optimize", optimize, (E,), (torch.int32,)),
+             ("best_freq", best_freq, (E,), (torch.float32,))]
+    if frg is not None:
+        specs.append(("frg", frg, (E, FRG_BYTES), u8))
+    if stc is not None:
+        specs.append(("stc", stc, (E, STC_BYTES), u8))
+    dev = _device_tensors(specs)
+    _enqueue(dev, stream, lambda: None,
+             lambda o, s: lib.srbd_gait_apply_freq_device(pgg.data_ptr(), None if frg is None else frg.data_ptr(),
+                                                          None if stc is None else stc.data_ptr(), E,
+                                                          optimize.data_ptr(), best_freq.data_ptr(), s),
+             "srbd_gait_apply_freq_device")
+
+
+def apply_step_frequency(optimize, best_freq, gait=None, frg=None, stc=None, stream=None):
+    """The step-frequency write-back after a gait-adaptive step (wb_interface.py:354-358) on the batched device
+    classes: ``gait`` a ``BatchedPeriodicGaitGenerator``, ``frg`` a ``BatchedFootholdReferenceGenerator`` and ``stc``
+    a ``BatchedSwingTrajectoryController`` (or their state tensors; frg and stc optional).  optimize (E,) int32 from
+    ``check_touch_down_condition``, best_freq (E,) float32 from ``compute_control_device``.  One launch, no host
+    synchronisation."""
+    if gait is None:
+        raise ValueError("apply_step_frequency needs the gait generator (gait=)")
+    gait_apply_freq_device(getattr(gait, "state", gait), optimize, best_freq, frg=getattr(frg, "state", frg),
+                           stc=getattr(stc, "state", stc), stream=stream)
 
 
 STC_BYTES = C.sizeof(SrbdStc)

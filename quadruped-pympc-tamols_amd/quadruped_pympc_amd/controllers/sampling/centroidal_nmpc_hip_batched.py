@@ -125,8 +125,14 @@ class Batched_Sampling_MPC:
     # class) the best rows' frequencies
     _device_step_frequencies_from_result = False
 
+    def _set_gait_device(self, **gait_arguments):
+        """The gait keywords of ``compute_control_device``: the gait-adaptive class enqueues them."""
+        raise ValueError("gait, timings, nominal_step_frequencies, optimize_swings and step_frequencies belong to the "
+                         "gait-adaptive Batched_Sampling_MPC (centroidal_nmpc_hip_gait_adaptive_batched)")
+
     def compute_control_device(self, states, references, contact_sequences, best_control_parameters, keys, *,
-                               noise=None, stream=None):
+                               noise=None, stream=None, gait=None, timings=None, nominal_step_frequencies=None,
+                               optimize_swings=None, step_frequencies=None):
         """``compute_control`` on torch tensors of the context's device (``srbd_batch_step_device``): nothing crosses
         to the host and nothing waits for the device; the step is enqueued on ``stream`` (None: torch's current
         stream) and the returned tensors are ready in that stream's order.
@@ -138,11 +144,18 @@ class Batched_Sampling_MPC:
         device is not provided: split them on the host (``with_newkey``) and upload the packed keys.
 
         Returns the single class's tuple: (GRFs (E, 12), footholds (E, 12), predicted states (E, 24), best parameters
-        (E, P), best costs (E,), step frequencies (E,), costs (E, N) lazy -- fetched to the host on first use)."""
+        (E, P), best costs (E,), step frequencies (E,), costs (E, N) lazy -- fetched to the host on first use).
+
+        The gait keywords (the gait-adaptive class only; see its ``_set_gait_device``): when any is given, the
+        step's arguments are checked first and the gait setting is enqueued on ``stream`` ahead of the step
+        (``srbd_batch_set_gait_device``); without them the step runs with the last gait setting made."""
         import torch
 
         ctx = self.context
         E = self.num_envs
+        gait_arguments = dict(gait=gait, timings=timings, nominal_step_frequencies=nominal_step_frequencies,
+                              optimize_swings=optimize_swings, step_frequencies=step_frequencies)
+        with_gait = any(v is not None for v in gait_arguments.values())
         if not isinstance(keys, torch.Tensor):
             raise ValueError("keys must be a torch tensor")
         dev = keys.device
@@ -159,6 +172,9 @@ class Batched_Sampling_MPC:
             seeds = keys
             with torch.cuda.stream(s):
                 counters = torch.full((E,), self._calls + 1, dtype=torch.int64, device=dev)
+        if with_gait:  # every refusal before anything is enqueued
+            ctx.check_step_device(states, references, contact_sequences, best_control_parameters, seeds, counters, noise)
+            self._set_gait_device(stream=stream, **gait_arguments)
         out = ctx.step_device(states, references, contact_sequences, best_control_parameters, seeds, counters,
                               noise=noise, stream=stream)
         self._calls += 1

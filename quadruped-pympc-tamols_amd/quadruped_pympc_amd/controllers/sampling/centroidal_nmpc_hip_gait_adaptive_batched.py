@@ -8,6 +8,12 @@ sample draws its step frequency on the device from its environment's set and rol
 Environment ``e`` of a ``compute_control`` call returns what the single gait-adaptive class returns with the same
 key, bit for bit, ``best_step_frequency`` included.
 
+``compute_control_device(..., gait=, optimize_swings=)`` is the same step with every per-environment value on the device (``srbd_batch_set_gait_device``
++ ``srbd_batch_step_device``): the leg phases come from a ``BatchedPeriodicGaitGenerator``'s state or a tensor, the
+``optimize_swing`` flags from ``BatchedSwingTrajectoryController.check_touch_down_condition``, and
+``apply_step_frequency`` writes the best frequencies back into the device states (wb_interface.py:354-358), so a
+gait-adaptive loop never leaves the device or waits for it.
+
 MPPI and random sampling; ``sampling_method == 'cem_mppi'`` raises ``NotImplementedError`` from the base class.
 Gait-adaptive sampling together with the opt-in cost terms has no batch form (the library refuses it).
 """
@@ -15,6 +21,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from ... import _lib
 from .centroidal_nmpc_hip_batched import Batched_Sampling_MPC as _BatchedBase
 from .centroidal_nmpc_hip_gait_adaptive import PGG_DUTY_FACTOR
 from .centroidal_nmpc_hip_gait_adaptive import Sampling_MPC as _SingleGaitAdaptive
@@ -33,8 +40,7 @@ class Batched_Sampling_MPC(_BatchedBase):
         self.step_freq_delta = self._one_ga.step_freq_delta
         self.dt = self._one_ga.dt
 
-    # compute_control_device (inherited) steps with the gait setting of the last compute_control / context.set_gait
-    # call -- the leg phases and candidate sets are host values -- and returns the best rows' step frequencies
+    # the device step returns the best rows' step frequencies in the frequency slot
     _device_step_frequencies_from_result = True
 
     def freq_sets(self, nominal_step_frequencies, optimize_swings) -> np.ndarray:
@@ -56,3 +62,27 @@ class Batched_Sampling_MPC(_BatchedBase):
                                                                       best_control_parameters, keys, noise=noise)
         freq = np.array([r.best_freq for r in self.last_results], dtype=f32)
         return grf, fh, pred, best, cost, freq, costs
+
+    def _set_gait_device(self, *, gait=None, timings=None, nominal_step_frequencies=None, optimize_swings=None,
+                         step_frequencies=None, stream=None):
+        """The gait keywords of the inherited ``compute_control_device(states, refs, contacts, best, keys, *, gait=None,
+        timings=None, nominal_step_frequencies=None, optimize_swings, step_frequencies=None, noise=None,
+        stream=None)``: ``set_gait_device`` enqueued on ``stream`` ahead of the device step, so nothing crosses to the
+        host and nothing waits for the device.  The leg phases come from exactly one of ``gait`` (a
+        ``BatchedPeriodicGaitGenerator`` or its state tensor) and ``timings`` (E, 4) float32;
+        nominal_step_frequencies (E,) float32, or None for ``gait``'s own step frequencies; optimize_swings (E,) int32
+        as ``check_touch_down_condition`` returns them (required); step_frequencies None or (E, N) float32 injected
+        per-sample frequencies (with ``noise=``, the parity mode).  The step then returns the (E,) float32 device
+        tensor of the best rows' step frequencies in the frequency slot."""
+        if optimize_swings is None:
+            raise ValueError("optimize_swings is required with the gait arguments")
+        self.context.set_gait_device(optimize_swings, self.step_freq_delta, self.dt, PGG_DUTY_FACTOR,
+                                     pgg=getattr(gait, "state", gait), timings=timings,
+                                     nominal_freqs=nominal_step_frequencies, freq_rows=step_frequencies, stream=stream)
+
+    @staticmethod
+    def apply_step_frequency(optimize_swings, best_step_frequencies, gait=None, frg=None, stc=None, stream=None):
+        """wb_interface.py:354-358 for every environment on the device (``_lib.apply_step_frequency``): where
+        optimize_swings[e] == 1, ``gait``'s step frequency, ``frg``'s stance time and ``stc``'s swing period are
+        re-timed from best_step_frequencies[e], the frequency slot of ``compute_control_device``."""
+        _lib.apply_step_frequency(optimize_swings, best_step_frequencies, gait=gait, frg=frg, stc=stc, stream=stream)

@@ -3,7 +3,8 @@
 Mirror of ``quadruped_pympc/helpers/swing_trajectory_controller.py`` (reference): the same constructor, attributes
 and methods (``compute_swing_control_cartesian_space`` :48-94, ``update_swing_time`` :120-127,
 ``check_apex_condition`` :129-138, ``check_full_stance_condition`` :140-146,
-``regenerate_swing_trajectory_generator`` :35-46), with the 'bezier_ref' and 'explicit' swing generators.  The state
+``regenerate_swing_trajectory_generator`` :35-46, ``check_touch_down_condition`` :148-165), with the 'bezier_ref' and
+'explicit' swing generators.  The state
 lives in a ``srbd_stc`` struct and every method runs in ``libsrbd_hip.so``'s C++ host functions
 (``include/srbd_host.h``).  ``BatchedSwingTrajectoryController`` keeps ``num_envs`` of these structs on the device and
 runs the whole of ``WBInterface.compute_stance_and_swing_torque``'s leg law (wb_interface.py:369-415, :435-465) for
@@ -53,6 +54,16 @@ class SwingTrajectoryController:
         self._gp = C.byref(self._g)
         _check(_lib.lib.srbd_stc_init(self._gp, float(step_height), float(swing_period), float(position_gain_fb),
                                       float(velocity_gain_fb), _generator_code(generator)), "srbd_stc_init")
+        self._edge = C.c_int32(0)
+
+    @property
+    def rising_edge_detected(self):
+        """The touch-down trigger's state, a bool as in the reference."""
+        return bool(self._edge.value)
+
+    @rising_edge_detected.setter
+    def rising_edge_detected(self, value):
+        self._edge.value = int(bool(value))
 
     # plain attributes of the reference, backed by the C struct
     step_height = property(lambda s: s._g.step_height)
@@ -133,6 +144,21 @@ class SwingTrajectoryController:
         return _check(_lib.lib.srbd_stc_full_stance(_lib.dptr(_arr(current_contact, (4,), "current_contact"))),
                       "check_full_stance_condition")
 
+    def check_touch_down_condition(self, current_contact, previous_contact, contact_sequence, lookahead=3):
+        """1 when all feet have touched down since the last trigger (a rising edge of full stance), the first
+        ``lookahead`` columns of the contact sequence are full stance and column ``lookahead`` is not; else 0
+        (``srbd_stc_touch_down``).  IndexError where the reference's ``contact_sequence[:, lookahead]`` raises it."""
+        seq = np.ascontiguousarray(contact_sequence, dtype=np.float64)
+        if seq.ndim != 2 or seq.shape[0] != 4:
+            raise ValueError(f"contact_sequence must be (4, horizon), got {seq.shape}")
+        rc = _lib.lib.srbd_stc_touch_down(C.byref(self._edge), _lib.dptr(_arr(current_contact, (4,), "current_contact")),
+                                          _lib.dptr(_arr(previous_contact, (4,), "previous_contact")), _lib.dptr(seq),
+                                          seq.shape[1], seq.shape[1], int(lookahead))
+        if rc < 0:
+            raise IndexError(f"lookahead must be 1..{seq.shape[1] - 1} for a sequence of {seq.shape[1]} columns, got "
+                             f"{lookahead}")
+        return rc
+
     def step(self, dt, jac, jac_dot, q_dot, foot_pos, foot_vel, qfrc_passive, qfrc_bias, mass_matrix, grfs, lift_off,
              touch_down, contact, apex_interval=0.01):
         """One whole control step (``srbd_stc_step``): the clock update, the four legs, friction compensation and the
@@ -163,8 +189,9 @@ class BatchedSwingTrajectoryController:
     position_gain_fb[e], velocity_gain_fb[e], generator[e])`` whose ``step`` is called each control step: its state
     keeps the host struct's bytes and its outputs are the host's, bit for bit.  The four numbers are scalars or
     length-E sequences, ``generator`` a name or a sequence of E names.  The state is one (E, sizeof(srbd_stc)) uint8
-    tensor, ``state``, built from host ``srbd_stc_init`` structs.  ``step`` enqueues on the current stream and does
-    not wait for the device; ``state_dict`` does.  The Jacobians, mass matrices, bias and passive forces are the
+    tensor, ``state``, built from host ``srbd_stc_init`` structs; the touch-down trigger's state is ``rising_edge``,
+    an (E,) int32 tensor.  ``step`` and ``check_touch_down_condition`` enqueue on the current stream and do not wait
+    for the device; ``state_dict`` does.  The Jacobians, mass matrices, bias and passive forces are the
     simulator's to provide."""
 
     def __init__(self, num_envs, step_height, swing_period, position_gain_fb, velocity_gain_fb,
@@ -200,6 +227,7 @@ class BatchedSwingTrajectoryController:
                                "in device memory; SwingTrajectoryController is the host form)")
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.state = torch.empty((E, _lib.STC_BYTES), dtype=torch.uint8, device=self.device)
+        self.rising_edge = torch.zeros(E, dtype=torch.int32, device=self.device)
         self._out = None
         self.load_state_dict(host)
 
@@ -226,9 +254,12 @@ class BatchedSwingTrajectoryController:
 
     def state_dict(self):
         """The host structs, a ``(SrbdStc * E)`` ctypes array (waits for the device): for checkpoints and tests.
-        ``bytes()`` of it is a plain byte string; ``load_state_dict`` takes either."""
+        ``bytes()`` of it is a plain byte string; ``load_state_dict`` takes either.  The trigger's state rides along
+        as the array's ``rising_edge`` attribute, an (E,) int32 NumPy array."""
         raw = self.state.cpu().numpy().tobytes()
-        return (_lib.SrbdStc * self.num_envs).from_buffer_copy(raw)
+        structs = (_lib.SrbdStc * self.num_envs).from_buffer_copy(raw)
+        structs.rising_edge = self.rising_edge.cpu().numpy().copy()
+        return structs
 
     def load_state_dict(self, structs):
         import torch
@@ -237,8 +268,20 @@ class BatchedSwingTrajectoryController:
         if raw.size != self.num_envs * _lib.STC_BYTES:
             raise ValueError(f"{self.num_envs} srbd_stc structs expected ({self.num_envs * _lib.STC_BYTES} bytes), got "
                              f"{raw.size} bytes")
+        # the trigger's state: what state_dict attached, or no edge pending (a plain byte string carries none)
+        edge = np.asarray(getattr(structs, "rising_edge", np.zeros(self.num_envs)), dtype=np.int32)
+        if edge.shape != (self.num_envs,):
+            raise ValueError(f"rising_edge must have {self.num_envs} entries, got shape {edge.shape}")
         with torch.cuda.stream(torch.cuda.current_stream(self.device)):
             self.state.copy_(torch.from_numpy(raw.reshape(self.num_envs, _lib.STC_BYTES).copy()))
+            self.rising_edge.copy_(torch.from_numpy(edge.copy()))
+
+    def check_touch_down_condition(self, current, previous, contacts, lookahead=3, stream=None):
+        """``check_touch_down_condition`` of every environment (``srbd_stc_touch_down_device``): current / previous
+        (E, 4) float32 as ``BatchedPeriodicGaitGenerator.run`` returns them, contacts (E, 4, H) float32 as its
+        ``compute_contact_sequence`` returns them.  Returns the (E,) int32 cuda tensor of flags, ``optimize_swing`` per
+        environment; ``rising_edge`` is updated in place.  One launch, no host synchronisation."""
+        return _lib.stc_touch_down_device(self.rising_edge, current, previous, contacts, lookahead, stream=stream)
 
     def regenerate_swing_trajectory_generator(self, step_height, swing_period):
         """Every environment's step height and swing period (wb_interface.py:358); the clocks are left alone.
