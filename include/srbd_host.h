@@ -22,6 +22,11 @@
  *                                       write-back of WBInterface.compute_stance_and_swing_torque
  *                                       quadruped_pympc/helpers/swing_trajectory_controller.py:148-165
  *                                       quadruped_pympc/interfaces/wb_interface.py:354-358
+ *   srbd_vfa_init / _mode / _commit / _reset
+ *                                    <- the apex gate of WBInterface.update_state_and_reference around the foothold
+ *                                       search and VisualFootholdAdaptation's state
+ *                                       quadruped_pympc/interfaces/wb_interface.py:230-246
+ *                                       quadruped_pympc/helpers/visual_foothold_adaptation.py:59-72
  *   srbd_vm_modulate / srbd_terrain_est_init / srbd_terrain_estimate / srbd_reference_assemble
  *                                    <- VelocityModulator, TerrainEstimator and the reference row of
  *                                       WBInterface.update_state_and_reference
@@ -265,6 +270,67 @@ int srbd_stc_touch_down(int32_t* rising_edge, const double current_contact[4], c
                         int32_t horizon, int32_t lookahead);
 int srbd_gait_apply_freq(srbd_pgg* pgg, srbd_frg* frg /* or NULL */, srbd_stc* stc /* or NULL */, int32_t optimize,
                          float best_freq);
+
+/* ---- Apex-gated foothold adaptation: the state machine WBInterface.update_state_and_reference keeps around the
+ * foothold search (csrc/srbd_vfa.h, which the device form srbd_vfa_step_device of srbd_mpc.h compiles too).
+ *   srbd_vfa_init / srbd_vfa_reset <- VisualFootholdAdaptation.__init__ / reset
+ *                                     quadruped_pympc/helpers/visual_foothold_adaptation.py:38-46, :63-64
+ *   srbd_vfa_mode                  <- the two conditions of quadruped_pympc/interfaces/wb_interface.py:232 and :243
+ *   srbd_vfa_commit                <- update_footholds_adaptation :59-61, reset :63-64, get_footholds_adapted :66-72,
+ *                                     and what compute_adaptation :193-228 stores per leg
+ * The reference, per control step (wb_interface.py:230-246):
+ *   if stc.check_apex_condition(contact, 0.01) and not vfa.initialized:  search; footholds_adaptation = result;
+ *                                                                        initialized = True
+ *   if stc.check_full_stance_condition(contact):                         initialized = False
+ *   not initialized: footholds_adaptation = seeds, return the seeds;  initialized: return footholds_adaptation
+ * so it searches once per swing, at the apex, holds that result until the next full stance, and passes the seeds
+ * through from there until the next apex.  Three modes name the three paths:
+ *   SRBD_VFA_SEARCH  apex and not initialized
+ *   SRBD_VFA_HOLD    initialized and not full stance
+ *   SRBD_VFA_PASS    everything else (not initialized without an apex; or full stance, which resets)
+ * An apex needs a leg in swing and full stance needs none, so a search and the reset never fall on one step.  Both
+ * conditions are srbd_stc_apex's and srbd_stc_full_stance's, on the swing clocks as the last leg-controller step left
+ * them: the reference checks the apex before this step's update_swing_time.
+ * State (plain data, sizeof 320, no padding: four words, 36 doubles, four words; the caller may copy, inspect or
+ * persist it, and an array of them in device memory keeps every double aligned).  Legs FL FR RL RR.
+ *   initialized  the reference's `initialized`, one word per leg, always all four equal: replicated so that the
+ *                device kernel's block (leg, environment) reads and writes only its own word
+ *   footholds    the reference's footholds_adaptation
+ *   boxes        the reference's footholds_constraints, two vertices per leg; NaN where the reference holds None
+ *   valid        whether the leg's last search found a candidate
+ * Stale constraint: a search that finds no candidate for a leg leaves that leg's box as it was (the reference assigns
+ * footholds_constraints only for a feasible leg, :209-228), so the box returned with valid 0 is the last feasible
+ * search's, or NaN if there was none.  Neither the reset nor a pass-through touches boxes or valid.
+ * Out of scope: a per-environment masked reset of the loop's other device state, the 'height' and 'vfa' strategies,
+ * the early-stance detector, start-and-stop and inverse kinematics. */
+enum { SRBD_VFA_PASS = 0, SRBD_VFA_SEARCH = 1, SRBD_VFA_HOLD = 2 };
+typedef struct srbd_vfa {
+    int32_t initialized[4]; /* 0 / 1, all four equal (16 bytes: the doubles behind them stay aligned) */
+    double footholds[12];   /* 4 x 3 */
+    double boxes[24];       /* 4 x 2 x 3 */
+    int32_t valid[4];       /* the struct ends on a multiple of 8 */
+} srbd_vfa;
+
+/* Not initialized, zero footholds, NaN boxes, valid 0.  SRBD_E_INVALID: NULL. */
+int srbd_vfa_init(srbd_vfa* g);
+/* The reference's reset(): initialized = 0, nothing else.  SRBD_E_INVALID: NULL. */
+int srbd_vfa_reset(srbd_vfa* g);
+/* *mode = the step's mode from g->initialized, the clocks of stc and the contact flags (a leg is in swing iff its
+ * flag == 0).  Nothing is written to g.  SRBD_E_INVALID (nothing written): a NULL pointer, an apex_interval that is
+ * not finite, a g whose four initialized words differ. */
+int srbd_vfa_mode(const srbd_vfa* g, const srbd_stc* stc, const double contact[4], double apex_interval,
+                  int32_t* mode);
+/* The step's state update and what get_footholds_adapted returns, per leg:
+ *   SEARCH  footholds = searched_footholds; boxes = searched_boxes only where searched_valid (see above); valid =
+ *           searched_valid; initialized = 1
+ *   HOLD    nothing is stored
+ *   PASS    footholds = seeds; initialized = 0; boxes and valid are left alone
+ * and in all three out_footholds / out_boxes / out_valid are the state's after that.  The three searched_ pointers may
+ * be NULL unless mode is SEARCH.  SRBD_E_INVALID (nothing written): a NULL required pointer, an unknown mode, a g
+ * whose four initialized words differ. */
+int srbd_vfa_commit(srbd_vfa* g, int32_t mode, const double seeds[12], const double searched_footholds[12],
+                    const double searched_boxes[24], const int32_t searched_valid[4], double out_footholds[12],
+                    double out_boxes[24], int32_t out_valid[4]);
 
 /* ---- Velocity modulator, terrain estimator and the reference row's first twelve entries: what
  * WBInterface.update_state_and_reference builds every control step from the velocity command, before and after the

@@ -681,6 +681,47 @@ typedef struct srbd_tamols_batch_io {
 } srbd_tamols_batch_io;
 int srbd_tamols_batch_device(srbd_terrain* terrain /* NULL: patch form */, const srbd_tamols_params* params,
                              int32_t num_envs, const srbd_tamols_batch_io* io, void* hip_stream);
+/* The same search behind the reference's apex gate (wb_interface.py:230-246 with VisualFootholdAdaptation's state,
+ * visual_foothold_adaptation.py:59-72): an environment searches once per swing, at the apex, holds that foothold until
+ * the next full stance and passes its seeds through from there to the next apex -- where srbd_tamols_batch_device
+ * searches every leg of every environment on every call.  srbd_host.h (srbd_vfa, srbd_vfa_mode, srbd_vfa_commit) and
+ * csrc/srbd_vfa.h state the machine; this is its device form.
+ *   State: d_vfa is an array of num_envs srbd_vfa structs in device memory (initialise on the host with srbd_vfa_init
+ *   and upload; the caller may download and inspect them); d_stc the num_envs srbd_stc structs srbd_stc_step_device
+ *   advances, read only here.  The gate reads the swing clocks as the last srbd_stc_step_device left them, so within
+ *   a control step this call comes before that one (the reference checks the apex before update_swing_time).
+ *   io is srbd_tamols_batch_device's, every field with its meaning there, except: io->contact is required (float32 as
+ *   srbd_pgg_run_device writes it; the gate's swing legs are those == 0.0f, the search's stance legs those == 1.0f);
+ *   footholds, boxes, valid and ref's entries 12..23 receive what get_footholds_adapted returns (the search's result,
+ *   the held footholds, or the seeds; the box of a leg whose last search was infeasible is its older one, see
+ *   srbd_host.h); seed_heights, scores and heightmaps_out are written for searching environments only, other
+ *   environments' rows are left untouched.  d_mode, when given, receives SRBD_VFA_SEARCH / _HOLD / _PASS per environment.
+ *   Launch shape: srbd_tamols_batch_device's grid (4 legs x num_envs) and block.  Block (leg, e) forms the mode itself
+ *   from d_stc[e], io->contact[e] and its own word d_vfa[e].initialized[leg] -- the word is replicated per leg for
+ *   this, nothing crosses blocks; one wave reads it, once, before any lane of the block writes it -- and branches
+ *   before the patch stage: a HOLD or PASS block copies its leg's ten
+ *   values and leaves; a SEARCH block runs the ungated kernel's stages through the same device functions.
+ *   Equivalence: for environment e the call does, on a host srbd_vfa with d_vfa[e]'s bytes, srbd_vfa_mode (contacts
+ *   widened to double); then, when the mode is SEARCH, what srbd_tamols_batch_device returns for that environment's
+ *   inputs; then srbd_vfa_commit.  Afterwards d_vfa[e] holds the host struct's bytes, every output row the host's
+ *   values bit for bit (NaNs position for position), d_mode[e] the mode.  Environments are independent: a NaN seed or
+ *   yaw in one changes nothing in another, and a non-searching environment reads neither its yaw, hips, patch nor the
+ *   terrain.  A d_vfa[e] whose four initialized words differ (which no call here produces) is not refused on the
+ *   device: each leg follows its own word.
+ *   Enqueue contract (the producers' above): exactly one launch on hip_stream, no synchronising HIP call, no device
+ *   memory touched from the host; the stream handle is read as srbd_prepare_state_device reads it; no event and no
+ *   ordering rule; d_stc is read only.
+ *   SRBD_E_INVALID (before any HIP call): everything srbd_tamols_batch_device refuses; a NULL d_vfa, d_stc or
+ *   io->contact; an apex_interval that is not finite.  A failed launch: SRBD_E_HIP, or SRBD_E_NODEVICE where no device
+ *   exists.
+ *   Out of scope: a per-environment masked reset of the loop's device state (clear d_vfa[e].initialized yourself, in
+ *   stream order); the 'height' and 'vfa' strategies; the early-stance detector, start-and-stop and inverse kinematics;
+ *   compacting the searching environments into a smaller grid (their count would have to reach the host). */
+struct srbd_vfa;
+struct srbd_stc;
+int srbd_vfa_step_device(struct srbd_vfa* d_vfa, const struct srbd_stc* d_stc, srbd_terrain* terrain /* NULL: patch form */,
+                         const srbd_tamols_params* params, int32_t num_envs, const srbd_tamols_batch_io* io,
+                         double apex_interval, int32_t* d_mode /* E, or NULL */, void* hip_stream);
 /* Self-test: out_cs[2 i], out_cs[2 i + 1] = the cos and sin srbd_tamols_batch_device's kernel forms of yaws[i],
  * evaluated on the host by the same function (plain float64 operations and fma: the same bits on both sides). */
 int srbd_selftest_yaw_sincos(const double* yaws, int32_t n, double* out_cs);

@@ -19,6 +19,7 @@
 #include "srbd_jaxrng.h"
 #include "srbd_stc.h"
 #include "srbd_terrain.h"
+#include "srbd_vfa.h"
 
 namespace {
 
@@ -314,6 +315,43 @@ extern "C" int srbd_gait_apply_freq(srbd_pgg* pgg, srbd_frg* frg, srbd_stc* stc,
                                     float best_freq) {  // WBI:354-358
     if (!pgg) return SRBD_E_INVALID;
     return srbd::ga_apply_freq(pgg, frg, stc, optimize, best_freq);
+}
+
+// ------------------------------------------- apex-gated foothold adaptation: the state machine (srbd_vfa.h)
+extern "C" int srbd_vfa_init(srbd_vfa* g) {  // VFA:38-46
+    if (!g) return SRBD_E_INVALID;
+    memset(g, 0, sizeof(*g));
+    for (int k = 0; k < 24; ++k) g->boxes[k] = NAN;
+    return SRBD_OK;
+}
+
+extern "C" int srbd_vfa_reset(srbd_vfa* g) {  // VFA:63-64
+    if (!g) return SRBD_E_INVALID;
+    for (int l = 0; l < 4; ++l) g->initialized[l] = 0;
+    return SRBD_OK;
+}
+
+extern "C" int srbd_vfa_mode(const srbd_vfa* g, const srbd_stc* stc, const double contact[4], double apex_interval,
+                             int32_t* mode) {  // WBI:232, :243
+    if (!g || !stc || !contact || !mode || !std::isfinite(apex_interval) || !srbd::vfa_struct_ok(g))
+        return SRBD_E_INVALID;
+    *mode = srbd::vfa_mode(g->initialized[0], stc, contact, apex_interval);
+    return SRBD_OK;
+}
+
+extern "C" int srbd_vfa_commit(srbd_vfa* g, int32_t mode, const double seeds[12], const double searched_footholds[12],
+                               const double searched_boxes[24], const int32_t searched_valid[4],
+                               double out_footholds[12], double out_boxes[24], int32_t out_valid[4]) {
+    if (!g || !seeds || !out_footholds || !out_boxes || !out_valid || !srbd::vfa_mode_ok(mode) ||
+        !srbd::vfa_struct_ok(g))
+        return SRBD_E_INVALID;
+    const bool search = mode == SRBD_VFA_SEARCH;
+    if (search && (!searched_footholds || !searched_boxes || !searched_valid)) return SRBD_E_INVALID;
+    for (int l = 0; l < 4; ++l)
+        srbd::vfa_commit_leg(g, l, mode, seeds + 3 * l, search ? searched_footholds + 3 * l : nullptr,
+                             search ? searched_boxes + 6 * l : nullptr, search ? searched_valid[l] : 0,
+                             out_footholds + 3 * l, out_boxes + 6 * l, out_valid + l);
+    return SRBD_OK;
 }
 
 // ------------------------------------------- velocity modulator, terrain estimator, reference row (srbd_terrain.h)

@@ -4,6 +4,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/srbd_host.h"
 #include "srbd_core.h"
 
 namespace srbd {
@@ -326,8 +327,17 @@ struct TamolsBatchJob {
     int use_terrain;  // 1: raycast from `t` (centres = the seeds, yaws[e]), 0: read `hm`
     int lattice;      // use_terrain with finite spacings: the lattice queries, for a finite yaw cos / sin
     double dist_x, dist_y, inv_dx, inv_dy, ray_z;
+    // the apex gate (srbd_vfa_step_device; read by tamols_batch_kernel<true> alone): the per-environment state and
+    // swing clocks, the apex window's half width and the modes (E words, or NULL)
+    srbd_vfa* vfa;
+    const srbd_stc* stc;
+    int32_t* mode;
+    double apex_interval;
 };
 size_t tamols_batch_lds(int rows, int cols);  // dynamic LDS bytes of one block
 void launch_tamols_batch(const TamolsBatchJob& j, hipStream_t s);
+// The same grid and block with the gate: block (leg, e) forms environment e's mode (srbd_vfa.h vfa_mode) and, unless it
+// is SEARCH, copies its leg's held foothold or seed and leaves before the search's first stage.
+void launch_tamols_batch_gated(const TamolsBatchJob& j, hipStream_t s);
 
 }  // namespace srbd

@@ -30,7 +30,9 @@
 // of the sampler's best frequency (srbd_gait_adapt.h; STC:148-165, wb_interface.py:354-358).  One lane per
 // environment, no cross-lane traffic.
 // srbd_tamols_batch_device, the loop's foothold search, is validated and enqueued here too; its kernel lives with the
-// single-environment one (tamols_kernel.hip tamols_batch_kernel), whose device functions it runs.
+// single-environment one (tamols_kernel.hip tamols_batch_kernel), whose device functions it runs.  So is
+// srbd_vfa_step_device, the same search behind the reference's apex gate (srbd_vfa.h; wb_interface.py:230-246): the
+// same job with the gate's four fields, the same grid, the kernel's gated instantiation.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
@@ -612,8 +614,11 @@ extern "C" int srbd_terrain_ref_step_device(srbd_terrain_est* d_terrain, int32_t
     return launch_status();
 }
 
-extern "C" int srbd_tamols_batch_device(srbd_terrain* terrain, const srbd_tamols_params* params, int32_t num_envs,
-                                        const srbd_tamols_batch_io* io, void* hip_stream) {
+namespace {
+
+// What srbd_tamols_batch_device refuses, and the launch's job from its arguments (srbd_vfa_step_device adds the gate).
+int tamols_batch_job(srbd_terrain* terrain, const srbd_tamols_params* params, int32_t num_envs,
+                     const srbd_tamols_batch_io* io, TamolsBatchJob& j) {
     if (!params || !io || !io->seeds || !io->hips || !io->footholds || !io->boxes || !io->valid || !envs_ok(num_envs))
         return SRBD_E_INVALID;
     if (io->rows < 1 || io->cols < 1 || (int64_t)io->rows * io->cols > TAMOLS_MAXCAND) return SRBD_E_INVALID;
@@ -622,7 +627,7 @@ extern "C" int srbd_tamols_batch_device(srbd_terrain* terrain, const srbd_tamols
     } else if (!io->heightmaps || io->heightmaps_out) {
         return SRBD_E_INVALID;
     }
-    TamolsBatchJob j = {};
+    j = {};
     j.seeds = io->seeds;
     j.hips = io->hips;
     j.vel = io->forward_vel;
@@ -655,7 +660,32 @@ extern "C" int srbd_tamols_batch_device(srbd_terrain* terrain, const srbd_tamols
     } else {
         j.hm = io->heightmaps;
     }
+    return SRBD_OK;
+}
+
+}  // namespace
+
+extern "C" int srbd_tamols_batch_device(srbd_terrain* terrain, const srbd_tamols_params* params, int32_t num_envs,
+                                        const srbd_tamols_batch_io* io, void* hip_stream) {
+    TamolsBatchJob j;
+    const int rc = tamols_batch_job(terrain, params, num_envs, io, j);
+    if (rc != SRBD_OK) return rc;
     launch_tamols_batch(j, stream_of(hip_stream));
+    return launch_status();
+}
+
+extern "C" int srbd_vfa_step_device(srbd_vfa* d_vfa, const srbd_stc* d_stc, srbd_terrain* terrain,
+                                    const srbd_tamols_params* params, int32_t num_envs, const srbd_tamols_batch_io* io,
+                                    double apex_interval, int32_t* d_mode, void* hip_stream) {
+    if (!d_vfa || !d_stc || !io || !io->contact || !std::isfinite(apex_interval)) return SRBD_E_INVALID;
+    TamolsBatchJob j;
+    const int rc = tamols_batch_job(terrain, params, num_envs, io, j);
+    if (rc != SRBD_OK) return rc;
+    j.vfa = d_vfa;
+    j.stc = d_stc;
+    j.mode = d_mode;
+    j.apex_interval = apex_interval;
+    launch_tamols_batch_gated(j, stream_of(hip_stream));
     return launch_status();
 }
 

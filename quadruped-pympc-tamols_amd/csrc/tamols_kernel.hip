@@ -18,6 +18,7 @@
 // Outputs go straight to host-mapped memory; the host polls the tagged words (no copy, no stream sync, no
 // fence and flag behind the data).  A raycast lattice patch takes one block per leg (TamolsJob::lattice).
 // float64 keeps the host oracle's decisions (reach bounds, argmin) bit-for-bit comparable.
+#include "srbd_vfa.h"
 #include "terrain_ray.h"
 #include "yaw_sincos.h"
 
@@ -734,6 +735,21 @@ void launch_tamols_fused(const TamolsJob& j, hipStream_t s, const StepInputK* ks
 // sized from the patch (dynamic: px, py, pz, sc of rows * cols doubles and the query stage nn), so several
 // blocks share a CU.  The environment's TamolsArgs / TamolsJob (what the device functions read) is assembled in LDS
 // from the caller's per-environment arrays; the yaw's cos / sin by yaw_sincos.h (two lanes of wave 2).
+//
+// GATED (srbd_vfa_step_device): the apex gate of srbd_vfa.h in front of and behind the same stages.  Block (leg, e)
+// forms environment e's mode itself, from stc[e]'s clocks, contact[e] (both read-only here) and its own word
+// vfa[e].initialized[leg]; the four blocks of an environment read four equal words, so they agree without a word
+// crossing blocks.  The branch is block-uniform and comes first: a HOLD or PASS block touches no LDS but the one word
+// that carries the mode from wave 0 to the others, and neither the environment's yaw, hips, patch nor the scene --
+// ten lanes copy the leg's ten slots (vfa_commit_slot), three of them
+// the reference row's feet, and the block is gone.  It still held the search's LDS for that long, which is why it
+// does nothing else.  A SEARCH block runs the stages below unchanged and ends in vfa_commit_leg where the ungated
+// kernel stores its outputs.
+constexpr int TAMOLS_PARAM_DOUBLES = (int)(sizeof(srbd_tamols_params) / sizeof(double));
+static_assert(sizeof(srbd_tamols_params) % sizeof(double) == 0 && offsetof(TamolsBatchJob, p) % sizeof(double) == 0 &&
+                  TAMOLS_PARAM_DOUBLES <= 64,
+              "the gated kernel copies the parameters as doubles, one per lane of wave 1");
+template <bool GATED>
 __global__ void __launch_bounds__(TAMOLS_BATCH_THREADS) tamols_batch_kernel(const TamolsBatchJob bj) {
     extern __shared__ double bsm[];
     __shared__ TamolsJob j;
@@ -744,6 +760,30 @@ __global__ void __launch_bounds__(TAMOLS_BATCH_THREADS) tamols_batch_kernel(cons
     const int leg = blockIdx.x, e = blockIdx.y, tid = threadIdx.x;
     const int nc = bj.rows * bj.cols, nq = nc * TAMOLS_NQ + 1;
     const size_t el = (size_t)e * 4 + leg;
+    if constexpr (GATED) {
+        // Wave 0 alone reads the gate's words and forms the mode (its lanes the same loads and comparisons), and hands
+        // it to the other waves through one word of static LDS behind a barrier.  So the block's own word
+        // initialized[leg] is read once, before the barrier, and written (lane 9 of a PASS block below, thread 0 of a
+        // SEARCH block at the end) only after it: no wave can read the word after another has rewritten it.
+        __shared__ int32_t gate_mode;
+        if (tid < 64) {
+            double ct[4];
+            for (int l = 0; l < 4; ++l) ct[l] = (double)bj.contact[4 * (size_t)e + l];
+            const int32_t m = vfa_mode(bj.vfa[e].initialized[leg], bj.stc + e, ct, bj.apex_interval);
+            if (tid == 0) gate_mode = m;
+        }
+        __syncthreads();
+        const int32_t mode = __builtin_amdgcn_readfirstlane(gate_mode);  // block-uniform; tells the compiler so
+        if (leg == 0 && tid == 0 && bj.mode) bj.mode[e] = mode;
+        if (mode != SRBD_VFA_SEARCH) {
+            if (tid < 10) {
+                const double v = vfa_commit_slot(bj.vfa + e, leg, mode, tid, bj.seeds + 12 * (size_t)e + 3 * leg, nullptr,
+                                                 nullptr, 0, bj.footholds + 3 * el, bj.boxes + 6 * el, bj.valid + el);
+                if (tid < 3 && bj.ref) bj.ref[24 * (size_t)e + 12 + 3 * leg + tid] = v;
+            }
+            return;
+        }
+    }
     double* px = bsm;
     double* py = px + nc;
     double* pz = py + nc;
@@ -778,8 +818,16 @@ __global__ void __launch_bounds__(TAMOLS_BATCH_THREADS) tamols_batch_kernel(cons
         j.inv_dy = bj.inv_dy;
         j.ray_z = bj.ray_z;
         pn = 0;
-    } else if (tid == 64) {
-        a.p = bj.p;
+    } else if (GATED ? (tid >= 64 && tid < 64 + TAMOLS_PARAM_DOUBLES) : tid == 64) {
+        if constexpr (GATED) {
+            // One double per lane straight from the kernel-argument segment.  The struct assignment of the ungated
+            // instantiation makes this one park the 168 bytes in scratch memory at kernel entry -- eleven scratch
+            // stores by every lane of every block, the exiting ones included -- so it is not used here.
+            const auto ka = (const __attribute__((address_space(4))) double*)__builtin_amdgcn_kernarg_segment_ptr();
+            reinterpret_cast<double*>(&a.p)[tid - 64] = ka[offsetof(TamolsBatchJob, p) / sizeof(double) + (tid - 64)];
+        } else {
+            a.p = bj.p;
+        }
     }
     if (bj.use_terrain && tid >= 128 && tid < 130) {  // a wave of their own: the sine's series and the cosine's
         const double yaw = bj.yaws[e];
@@ -942,9 +990,14 @@ __global__ void __launch_bounds__(TAMOLS_BATCH_THREADS) tamols_batch_kernel(cons
         for (int k = 0; k < 6; ++k) b[k] = NAN;
         valid = 0;
     }
-    for (int k = 0; k < 3; ++k) bj.footholds[3 * el + k] = f[k];
-    for (int k = 0; k < 6; ++k) bj.boxes[6 * el + k] = b[k];
-    bj.valid[el] = valid;
+    if constexpr (GATED) {  // the search's result into the state; the outputs are the state's (an older box if !valid)
+        vfa_commit_leg(bj.vfa + e, leg, SRBD_VFA_SEARCH, a.seeds + 3 * leg, f, b, valid, bj.footholds + 3 * el,
+                       bj.boxes + 6 * el, bj.valid + el);
+    } else {
+        for (int k = 0; k < 3; ++k) bj.footholds[3 * el + k] = f[k];
+        for (int k = 0; k < 6; ++k) bj.boxes[6 * el + k] = b[k];
+        bj.valid[el] = valid;
+    }
     if (bj.seed_heights) bj.seed_heights[el] = seedh;
     if (bj.ref)
         for (int k = 0; k < 3; ++k) bj.ref[24 * (size_t)e + 12 + 3 * leg + k] = f[k];
@@ -958,8 +1011,13 @@ size_t tamols_batch_lds(int rows, int cols) {
 }
 
 void launch_tamols_batch(const TamolsBatchJob& j, hipStream_t s) {
-    hipLaunchKernelGGL(tamols_batch_kernel, dim3(4, j.E), dim3(TAMOLS_BATCH_THREADS), tamols_batch_lds(j.rows, j.cols),
-                       s, j);
+    hipLaunchKernelGGL(tamols_batch_kernel<false>, dim3(4, j.E), dim3(TAMOLS_BATCH_THREADS),
+                       tamols_batch_lds(j.rows, j.cols), s, j);
+}
+
+void launch_tamols_batch_gated(const TamolsBatchJob& j, hipStream_t s) {
+    hipLaunchKernelGGL(tamols_batch_kernel<true>, dim3(4, j.E), dim3(TAMOLS_BATCH_THREADS),
+                       tamols_batch_lds(j.rows, j.cols), s, j);
 }
 
 }  // namespace srbd

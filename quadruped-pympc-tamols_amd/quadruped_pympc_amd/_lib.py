@@ -228,6 +228,14 @@ class SrbdStcBatchIo(C.Structure):
     ]
 
 
+VFA_PASS, VFA_SEARCH, VFA_HOLD = 0, 1, 2
+
+
+class SrbdVfa(C.Structure):
+    """srbd_vfa (include/srbd_host.h): the apex-gated foothold adaptation's state."""
+    _fields_ = [("initialized", _I * 4), ("footholds", _D * 12), ("boxes", _D * 24), ("valid", _I * 4)]
+
+
 class SrbdTerrainEst(C.Structure):
     """srbd_terrain_est (include/srbd_host.h): TerrainEstimator state."""
     _fields_ = [("roll", _D), ("pitch", _D), ("height", _D), ("roll_activated", _I), ("pitch_activated", _I)]
@@ -283,6 +291,10 @@ SIGNATURES.update({
     "srbd_stc_full_stance": (_I, [_DP]),
     "srbd_stc_touch_down": (_I, [_IP, _DP, _DP, _DP, _I, _I, _I]),
     "srbd_gait_apply_freq": (_I, [C.POINTER(SrbdPgg), C.POINTER(SrbdFrg), C.POINTER(SrbdStc), _I, _F]),
+    "srbd_vfa_init": (_I, [C.POINTER(SrbdVfa)]),
+    "srbd_vfa_reset": (_I, [C.POINTER(SrbdVfa)]),
+    "srbd_vfa_mode": (_I, [C.POINTER(SrbdVfa), C.POINTER(SrbdStc), _DP, _D, _IP]),
+    "srbd_vfa_commit": (_I, [C.POINTER(SrbdVfa), _I, _DP, _DP, _DP, _IP, _DP, _DP, _IP]),
     "srbd_vm_modulate": (_I, [_D, _DP, _DP, _DP, _DP, _DP, _DP]),
     "srbd_terrain_est_init": (_I, [C.POINTER(SrbdTerrainEst)]),
     "srbd_terrain_estimate": (_I, [C.POINTER(SrbdTerrainEst), _DP, _D, _DP, _DP]),
@@ -334,6 +346,8 @@ SIGNATURES.update({
     "srbd_stc_touch_down_device": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _P, _P]),
     "srbd_batch_set_gait_device": (_I, [_P, C.POINTER(BatchGaitIO), _P]),
     "srbd_gait_apply_freq_device": (_I, [_P, _P, _P, _I, _P, _P, _P]),
+    # the apex-gated foothold adaptation: srbd_tamols_batch_device behind the gate
+    "srbd_vfa_step_device": (_I, [_P, _P, _P, C.POINTER(TamolsParams), _I, C.POINTER(TamolsBatchIO), _D, _P, _P]),
 })
 
 # srbd_time_launch kinds (include/srbd_mpc.h)
@@ -1180,20 +1194,14 @@ def prepare_state_device(state_in, ref_in, current_contact, previous_contact, pa
 MAX_CAND = 320
 
 
-def tamols_batch_device(seeds, hips, params, *, terrain=None, yaws=None, heightmaps=None, rows=13, cols=7,
-                        dist_x=0.04, dist_y=0.04, ray_z=10.0, forward_vel=None, base_pos=None, contact=None, feet=None,
-                        ref=None, out=None, want_seed_heights=False, want_scores=False, want_heightmaps=False,
-                        stream=None):
-    """srbd_tamols_batch_device: the TAMOLS foothold search of every environment, one launch enqueued on ``stream``
-    (None: torch's current stream) without a host synchronisation.  seeds / hips (E, 4, 3) float64, ``params`` a
-    TamolsParams.  Terrain form: ``terrain`` a GpuTerrain on the tensors' device and ``yaws`` (E,) float64; the
-    patches are raycast around the seeds (rows x cols, dist_x, dist_y, ray_z).  Patch form: ``heightmaps``
-    (E, 4, rows, cols, 3) float64, whose shape gives rows and cols.  Optional per-environment inputs: forward_vel /
-    base_pos (E, 3) float64, contact (E, 4) float32 (stance iff 1.0), feet (E, 4, 3) float64.  ``ref`` (E, 24)
-    float64: its entries 12..23 receive the footholds.  ``out``: a dict of preallocated outputs (any of footholds
-    (E, 4, 3), boxes (E, 4, 2, 3), valid (E, 4) int32, seed_heights (E, 4), scores (E, 4, rows * cols), heightmaps
-    (E, 4, rows, cols, 3)); absent footholds / boxes / valid are allocated, the other three only when asked for by
-    their ``want_`` flag.  Returns the dict of the tensors written."""
+def _tamols_batch_enqueue(native, what, seeds, hips, params, *, terrain=None, yaws=None, heightmaps=None, rows=13,
+                          cols=7, dist_x=0.04, dist_y=0.04, ray_z=10.0, forward_vel=None, base_pos=None, contact=None,
+                          feet=None, ref=None, out=None, want_seed_heights=False, want_scores=False,
+                          want_heightmaps=False, stream=None, extra_inputs=lambda E: (), extra_outputs=lambda E: ()):
+    """What ``tamols_batch_device`` and ``vfa_step_device`` share: the checks of the search's tensors, its outputs and
+    its srbd_tamols_batch_io.  ``native(terrain_handle, params, E, io, outputs, stream)`` makes the C call ``what``;
+    ``extra_inputs(E)`` yields further (name, tensor, shape, dtypes) to check, ``extra_outputs(E)`` further
+    (name, shape, dtypes) outputs, always allocated when not given in ``out``."""
     import torch
 
     E = int(seeds.shape[0]) if isinstance(seeds, torch.Tensor) and seeds.dim() == 3 else 0
@@ -1229,6 +1237,10 @@ def tamols_batch_device(seeds, hips, params, *, terrain=None, yaws=None, heightm
             specs.append((name, t, shape, dt))
     shapes = {"footholds": ((E, 4, 3), f64), "boxes": ((E, 4, 2, 3), f64), "valid": ((E, 4), i32),
               "seed_heights": ((E, 4), f64), "scores": ((E, 4, nc), f64), "heightmaps": ((E, 4, rows, cols, 3), f64)}
+    for name, t, shape, dt in extra_inputs(E):
+        specs.append((name, t, shape, dt))
+    for name, shape, dt in extra_outputs(E):
+        shapes[name] = (shape, dt)
     given = dict(out or {})
     for name, t in given.items():
         if name not in shapes:
@@ -1238,6 +1250,7 @@ def tamols_batch_device(seeds, hips, params, *, terrain=None, yaws=None, heightm
     wanted = ["footholds", "boxes", "valid"] + [n for n, w in (("seed_heights", want_seed_heights),
                                                                  ("scores", want_scores),
                                                                  ("heightmaps", want_heightmaps)) if w]
+    wanted += [name for name, _, _ in extra_outputs(E)]
 
     def alloc():
         o = dict(given)
@@ -1256,9 +1269,63 @@ def tamols_batch_device(seeds, hips, params, *, terrain=None, yaws=None, heightm
                            footholds=ptr(o["footholds"]), boxes=ptr(o["boxes"]), valid=ptr(o["valid"]),
                            seed_heights=ptr(o.get("seed_heights")), scores=ptr(o.get("scores")),
                            heightmaps_out=ptr(o.get("heightmaps")), ref=ptr(ref))
-        return lib.srbd_tamols_batch_device(None if terrain is None else terrain.h, C.byref(params), E, C.byref(io), s)
+        return native(None if terrain is None else terrain.h, C.byref(params), E, C.byref(io), o, s)
 
-    return _enqueue(dev, stream, alloc, call, "srbd_tamols_batch_device")
+    return _enqueue(dev, stream, alloc, call, what)
+
+
+
+
+def tamols_batch_device(seeds, hips, params, *, terrain=None, yaws=None, heightmaps=None, rows=13, cols=7,
+                        dist_x=0.04, dist_y=0.04, ray_z=10.0, forward_vel=None, base_pos=None, contact=None, feet=None,
+                        ref=None, out=None, want_seed_heights=False, want_scores=False, want_heightmaps=False,
+                        stream=None):
+    """srbd_tamols_batch_device: the TAMOLS foothold search of every environment, one launch enqueued on ``stream``
+    (None: torch's current stream) without a host synchronisation.  seeds / hips (E, 4, 3) float64, ``params`` a
+    TamolsParams.  Terrain form: ``terrain`` a GpuTerrain on the tensors' device and ``yaws`` (E,) float64; the
+    patches are raycast around the seeds (rows x cols, dist_x, dist_y, ray_z).  Patch form: ``heightmaps``
+    (E, 4, rows, cols, 3) float64, whose shape gives rows and cols.  Optional per-environment inputs: forward_vel /
+    base_pos (E, 3) float64, contact (E, 4) float32 (stance iff 1.0), feet (E, 4, 3) float64.  ``ref`` (E, 24)
+    float64: its entries 12..23 receive the footholds.  ``out``: a dict of preallocated outputs (any of footholds
+    (E, 4, 3), boxes (E, 4, 2, 3), valid (E, 4) int32, seed_heights (E, 4), scores (E, 4, rows * cols), heightmaps
+    (E, 4, rows, cols, 3)); absent footholds / boxes / valid are allocated, the other three only when asked for by
+    their ``want_`` flag.  Returns the dict of the tensors written."""
+    return _tamols_batch_enqueue(
+        lambda th, p, E, io, o, s: lib.srbd_tamols_batch_device(th, p, E, io, s), "srbd_tamols_batch_device", seeds,
+        hips, params, terrain=terrain, yaws=yaws, heightmaps=heightmaps, rows=rows, cols=cols, dist_x=dist_x,
+        dist_y=dist_y, ray_z=ray_z, forward_vel=forward_vel, base_pos=base_pos, contact=contact, feet=feet, ref=ref,
+        out=out, want_seed_heights=want_seed_heights, want_scores=want_scores, want_heightmaps=want_heightmaps,
+        stream=stream)
+
+
+VFA_BYTES = C.sizeof(SrbdVfa)
+
+
+def vfa_step_device(vfa, stc, seeds, hips, params, contact, *, apex_interval: float = 0.01, **kw):
+    """srbd_vfa_step_device: ``tamols_batch_device`` behind the reference's apex gate, one launch enqueued on
+    ``stream`` without a host synchronisation.  vfa (E, VFA_BYTES) uint8: the srbd_vfa structs, updated in place; stc
+    (E, STC_BYTES) uint8: the srbd_stc structs ``stc_step_device`` advances, read only; contact (E, 4) float32,
+    required.  Every other argument is ``tamols_batch_device``'s.  An environment at its swing apex that has not
+    searched since its last full stance searches; one that has, holds its footholds until the next full stance; every
+    other one returns its seeds.  Returns ``tamols_batch_device``'s dict plus ``mode`` (E,) int32 (VFA_SEARCH /
+    VFA_HOLD / VFA_PASS; ``out['mode']`` to preallocate); seed_heights, scores and heightmaps rows are written for
+    searching environments only."""
+    import math
+
+    import torch
+
+    if contact is None:
+        raise ValueError("the gate needs the contact flags")
+    interval = float(apex_interval)
+    if not math.isfinite(interval):
+        raise ValueError(f"apex_interval must be finite, got {apex_interval}")
+    u8, i32 = (torch.uint8,), (torch.int32,)
+    return _tamols_batch_enqueue(
+        lambda th, p, E, io, o, s: lib.srbd_vfa_step_device(vfa.data_ptr(), stc.data_ptr(), th, p, E, io, interval,
+                                                            o["mode"].data_ptr(), s),
+        "srbd_vfa_step_device", seeds, hips, params, contact=contact,
+        extra_inputs=lambda E: (("vfa", vfa, (E, VFA_BYTES), u8), ("stc", stc, (E, STC_BYTES), u8)),
+        extra_outputs=lambda E: (("mode", (E,), i32),), **kw)
 
 
 FRG_BYTES = C.sizeof(SrbdFrg)

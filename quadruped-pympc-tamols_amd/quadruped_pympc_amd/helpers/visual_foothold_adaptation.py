@@ -241,6 +241,34 @@ class VisualFootholdAdaptation:
             return reference_footholds, self.footholds_constraints
         return self.footholds_adaptation, self.footholds_constraints
 
+    def adaptation_mode(self, stc, current_contact, interval=0.01) -> int:
+        """Which of the gate's three paths this control step takes (``srbd_vfa_mode``, include/srbd_host.h):
+        ``_lib.VFA_SEARCH`` at a swing apex while not ``initialized``, ``_lib.VFA_HOLD`` while ``initialized`` and not in
+        full stance, else ``_lib.VFA_PASS``.  ``stc`` is the host ``SwingTrajectoryController``, whose clocks are read
+        as its last ``update_swing_time`` left them."""
+        g = _lib.SrbdVfa()
+        for l in range(4):
+            g.initialized[l] = int(bool(self.initialized))
+        contact = np.ascontiguousarray(current_contact, dtype=np.float64).reshape(4)
+        mode = C.c_int32(0)
+        rc = _lib.lib.srbd_vfa_mode(C.byref(g), C.byref(stc._g), _lib.dptr(contact), float(interval), C.byref(mode))
+        if rc != _lib.OK:
+            raise ValueError(f"srbd_vfa_mode failed ({rc})")
+        return int(mode.value)
+
+    def step_gated(self, stc, current_contact, reference_footholds, search, interval=0.01):
+        """The reference's gate around the search (wb_interface.py:232-246) as one call: at a swing apex, while not
+        ``initialized``, ``search()`` runs -- the caller's closure over ``compute_adaptation`` (which ends in
+        ``update_footholds_adaptation``); full stance resets; then ``get_footholds_adapted``.  Returns
+        ``(footholds, constraints, mode)``."""
+        mode = self.adaptation_mode(stc, current_contact, interval)
+        if mode == _lib.VFA_SEARCH:
+            search()
+        if stc.check_full_stance_condition(current_contact):
+            self.reset()
+        footholds, constraints = self.get_footholds_adapted(reference_footholds)
+        return footholds, constraints, mode
+
     @property
     def search(self) -> TamolsSearch:
         if self._search is None:
@@ -320,8 +348,78 @@ class BatchedVisualFootholdAdaptation:
         self.tamols_params = cfg.simulation_params.get("tamols_params", {})
         self.robot_name = cfg.robot
         self._params_src = self._params_struct = self._params_robot = None
+        self._state = None
+        self._mode = None
 
     _params = VisualFootholdAdaptation._params
+
+    @property
+    def state(self):
+        """(E, sizeof(srbd_vfa)) uint8 cuda tensor: the gate's per-environment state (``initialized``, the held
+        footholds, boxes and validity), built from host ``srbd_vfa_init`` structs on the current device at first use."""
+        if self._state is None:
+            import torch
+
+            if not torch.cuda.is_available():
+                raise RuntimeError("BatchedVisualFootholdAdaptation: no HIP device visible (the gate's state lives in "
+                                   "device memory; VisualFootholdAdaptation is the host form)")
+            host = (_lib.SrbdVfa * self.num_envs)()
+            for e in range(self.num_envs):
+                _lib.lib.srbd_vfa_init(C.byref(host[e]))
+            dev = torch.device("cuda", torch.cuda.current_device())
+            self._state = torch.empty((self.num_envs, _lib.VFA_BYTES), dtype=torch.uint8, device=dev)
+            self.load_state_dict(host)
+        return self._state
+
+    def state_dict(self):
+        """The host structs, a ``(SrbdVfa * E)`` ctypes array (waits for the device): for checkpoints and tests."""
+        return (_lib.SrbdVfa * self.num_envs).from_buffer_copy(self.state.cpu().numpy().tobytes())
+
+    def load_state_dict(self, structs):
+        import torch
+
+        raw = np.frombuffer(bytes(structs), dtype=np.uint8)
+        if raw.size != self.num_envs * _lib.VFA_BYTES:
+            raise ValueError(f"{self.num_envs} srbd_vfa structs expected ({self.num_envs * _lib.VFA_BYTES} bytes), got "
+                             f"{raw.size} bytes")
+        state = self._state if self._state is not None else self.state
+        with torch.cuda.stream(torch.cuda.current_stream(state.device)):
+            state.copy_(torch.from_numpy(raw.reshape(self.num_envs, _lib.VFA_BYTES).copy()))
+
+    def reset(self, stream=None):
+        """The reference's ``reset()`` for every environment: ``initialized`` cleared, in stream order (``stream``
+        None: torch's current stream), nothing else touched and nothing synchronised."""
+        import torch
+
+        state = self.state
+        o = _lib.SrbdVfa.initialized.offset // 4
+        with torch.cuda.stream(torch.cuda.current_stream(state.device) if stream is None else stream):
+            state.view(torch.int32)[:, o:o + 4].zero_()
+
+    def step_device(self, seeds, hips, forward_vel, base_position, current_contact, current_feet_pos, *, stc,
+                    terrain=None, yaws=None, heightmaps=None, ref=None, apex_interval=0.01, stream=None, **patch):
+        """The reference's gated adaptation (wb_interface.py:232-246) of every environment, one launch enqueued on
+        ``stream`` (``srbd_vfa_step_device``); nothing is synchronised.  The arguments are
+        ``compute_adaptation_device``'s, ``current_contact`` required; ``stc`` is the
+        ``BatchedSwingTrajectoryController`` (or its state tensor) whose swing clocks the gate reads -- as its last
+        ``step`` left them, so within a control step this call comes before ``stc.step``.  An environment at its swing
+        apex that has not searched since its last full stance searches, as ``compute_adaptation_device`` would; one
+        that has searched returns the footholds it holds; every other one returns its seeds.  Returns (footholds
+        (E, 4, 3), boxes (E, 4, 2, 3), valid (E, 4) int32, mode (E,) int32 of ``_lib.VFA_SEARCH`` / ``VFA_HOLD`` /
+        ``VFA_PASS``); a leg whose last search found no candidate returns valid 0 with the box of its last feasible
+        search (NaN if none).  ``ref``'s feet receive the footholds.  ``mode`` is allocated once and rewritten by
+        every call."""
+        if getattr(seeds, "shape", (0,))[0] != self.num_envs:
+            raise ValueError(f"seeds must hold {self.num_envs} environments, got {tuple(getattr(seeds, 'shape', ()))}")
+        given = dict(patch.pop("out", None) or {})
+        if "mode" not in given and self._mode is not None:
+            given["mode"] = self._mode
+        out = _lib.vfa_step_device(self.state, getattr(stc, "state", stc), seeds, hips, self._params(), current_contact,
+                                   apex_interval=apex_interval, terrain=terrain, yaws=yaws, heightmaps=heightmaps,
+                                   forward_vel=forward_vel, base_pos=base_position, feet=current_feet_pos, ref=ref,
+                                   stream=stream, out=given, **patch)
+        self._mode = out["mode"]
+        return out["footholds"], out["boxes"], out["valid"], out["mode"]
 
     def compute_adaptation_device(self, seeds, hips, forward_vel, base_position, current_contact, current_feet_pos, *,
                                   terrain=None, yaws=None, heightmaps=None, ref=None, stream=None, **patch):
