@@ -33,6 +33,8 @@
  *                                       quadruped_pympc/helpers/velocity_modulator.py:19-46
  *                                       quadruped_pympc/helpers/terrain_estimator.py:5-106
  *                                       quadruped_pympc/interfaces/wb_interface.py:168-172, :250-291
+ *   srbd_loop_reset                  <- the episode's end, simulation/simulation.py:773-781, and WBInterface.reset
+ *                                       quadruped_pympc/interfaces/wb_interface.py:469-484
  *   srbd_shm_publish / srbd_shm_read <- the MPC -> WBC shared-memory seqlock of ros2/run_controller.py
  *                                       (payload layout :50-83, writer :343-358, reader :565-580)
  *
@@ -301,8 +303,8 @@ int srbd_gait_apply_freq(srbd_pgg* pgg, srbd_frg* frg /* or NULL */, srbd_stc* s
  * Stale constraint: a search that finds no candidate for a leg leaves that leg's box as it was (the reference assigns
  * footholds_constraints only for a feasible leg, :209-228), so the box returned with valid 0 is the last feasible
  * search's, or NaN if there was none.  Neither the reset nor a pass-through touches boxes or valid.
- * Out of scope: a per-environment masked reset of the loop's other device state, the 'height' and 'vfa' strategies,
- * the early-stance detector, start-and-stop and inverse kinematics. */
+ * Out of scope: the 'height' and 'vfa' strategies, the early-stance detector, start-and-stop and inverse kinematics
+ * (the per-environment masked reset of this and the loop's other state is srbd_loop_reset, below). */
 enum { SRBD_VFA_PASS = 0, SRBD_VFA_SEARCH = 1, SRBD_VFA_HOLD = 2 };
 typedef struct srbd_vfa {
     int32_t initialized[4]; /* 0 / 1, all four equal (16 bytes: the doubles behind them stay aligned) */
@@ -385,6 +387,36 @@ int srbd_reference_assemble(const srbd_terrain_est* g, double ref_z, double base
 /* Self-test: out[i] = the arctangent both sides use, of x[i] >= 0 (+inf and NaN included), evaluated on the host by
  * the function the device kernel compiles (plain float64 add, multiply and divide: the same bits on both sides). */
 int srbd_selftest_atan(const double* x, int32_t n, double* out);
+
+/* ---- Restarting one environment of the loop: what the reference does when an episode ends, and what a batch needs
+ * besides (csrc/srbd_reset.h, which the device form srbd_loop_reset_device of srbd_mpc.h compiles too).
+ *   srbd_loop_reset <- the episode's end of simulation/simulation.py:773-781 (env.reset, quadrupedpympc_wrapper.reset),
+ *                      which reaches WBInterface.reset, quadruped_pympc/interfaces/wb_interface.py:469-484
+ * Two levels:
+ *   SRBD_RESET_REFERENCE (1)  WBInterface.reset statement for statement: srbd_pgg_reset on pgg (step_freq is left
+ *       alone, as the reference leaves it); frg->lift_off = initial_feet, that table only -- the _h tables, touch_down,
+ *       the velocity history, stc and the terrain filter are untouched (wb_interface.py:477-479 has those resets
+ *       commented out); vfa->initialized[0..3] = 0 (srbd_vfa_reset), nothing else of it.  rising_edge and best_params
+ *       are not touched.
+ *   SRBD_RESET_EPISODE (2)    every struct handed in becomes, byte for byte, what its constructor call produced: pgg,
+ *       stc, terrain_est and vfa the bytes of their snapshot (a copy of the struct taken when the loop was built: so
+ *       step_freq and swing_period go back to their constructor values even after srbd_gait_apply_freq changed them);
+ *       frg what srbd_frg_init(snapshot stance_time, snapshot hip_height, initial_feet) builds, with hip_offset the
+ *       snapshot's: all four position tables copies of the new feet, the history empty and zeroed,
+ *       last_reference_footholds zero; *rising_edge = 0; best_params[0..num_params) = 0.0f.  The reference has no such
+ *       call, one process being one robot; a batch needs it so that a restarted episode does not inherit the previous
+ *       one's 20-entry velocity history and swing clocks.
+ * At both levels the reference also sets current_contact = [1, 1, 1, 1] (wb_interface.py:483): the contact flags are
+ * the caller's own arrays here (the device call takes them as contact_rows).
+ * Every struct pointer, rising_edge and best_params may be NULL: that piece is not part of the caller's loop.
+ * SRBD_E_INVALID, nothing changed: a level outside {1, 2}; frg without initial_feet; at level 2 a struct without its
+ * snapshot; best_params with num_params < 1. */
+enum { SRBD_RESET_REFERENCE = 1, SRBD_RESET_EPISODE = 2 };
+int srbd_loop_reset(int32_t level, const double initial_feet[12], srbd_pgg* pgg, srbd_frg* frg, srbd_stc* stc,
+                    srbd_terrain_est* terrain_est, srbd_vfa* vfa, const srbd_pgg* pgg_snapshot,
+                    const srbd_frg* frg_snapshot, const srbd_stc* stc_snapshot,
+                    const srbd_terrain_est* terrain_est_snapshot, const srbd_vfa* vfa_snapshot, int32_t* rising_edge,
+                    float* best_params, int32_t num_params);
 
 /* ---- MPC -> WBC shared-memory seqlock (single writer, any number of readers) ---- */
 #define SRBD_SHM_DOUBLES 75

@@ -714,9 +714,9 @@ int srbd_tamols_batch_device(srbd_terrain* terrain /* NULL: patch form */, const
  *   SRBD_E_INVALID (before any HIP call): everything srbd_tamols_batch_device refuses; a NULL d_vfa, d_stc or
  *   io->contact; an apex_interval that is not finite.  A failed launch: SRBD_E_HIP, or SRBD_E_NODEVICE where no device
  *   exists.
- *   Out of scope: a per-environment masked reset of the loop's device state (clear d_vfa[e].initialized yourself, in
- *   stream order); the 'height' and 'vfa' strategies; the early-stance detector, start-and-stop and inverse kinematics;
- *   compacting the searching environments into a smaller grid (their count would have to reach the host). */
+ *   Out of scope: the 'height' and 'vfa' strategies; the early-stance detector, start-and-stop and inverse kinematics;
+ *   compacting the searching environments into a smaller grid (their count would have to reach the host).  The
+ *   per-environment masked reset of d_vfa and the loop's other device state is srbd_loop_reset_device, below. */
 struct srbd_vfa;
 struct srbd_stc;
 int srbd_vfa_step_device(struct srbd_vfa* d_vfa, const struct srbd_stc* d_stc, srbd_terrain* terrain /* NULL: patch form */,
@@ -960,6 +960,65 @@ int srbd_batch_set_gait_device(srbd_batch* b, const srbd_batch_gait_io* io, void
 int srbd_gait_apply_freq_device(struct srbd_pgg* d_pgg, struct srbd_frg* d_frg, struct srbd_stc* d_stc,
                                 int32_t num_envs, const int32_t* d_optimize, const float* d_best_freq,
                                 void* hip_stream);
+
+/* ---- Restarting single environments of the batched loop, device-resident: the episode's end of the reference's
+ * simulation loop (simulation/simulation.py:773-781: on is_terminated, is_truncated or the step limit, env.reset and
+ * quadrupedpympc_wrapper.reset(initial_feet_pos), which reaches WBInterface.reset, quadruped_pympc/interfaces/
+ * wb_interface.py:469-484, and controller.reset()) for the environments a mask names, in one launch.  srbd_host.h
+ * (srbd_loop_reset) and csrc/srbd_reset.h state the two levels; this is their device form.
+ *   io->mask (num_envs int32) chooses per environment:
+ *     0      not reset: no byte of environment e is written, not even with the value it holds, and none of its inputs
+ *            is read (io->initial_feet[e], the snapshots' entry e): a NaN there changes nothing anywhere.
+ *     2      SRBD_RESET_EPISODE: io->pgg[e], stc[e], terrain_est[e], vfa[e] take the bytes of their snapshot's entry e
+ *            (the same arrays as they were when the loop was built: clone them then); io->frg[e] becomes
+ *            srbd_frg_init(snapshot stance_time, snapshot hip_height, initial_feet[e]) with the snapshot's hip_offset;
+ *            io->rising_edge[e] = 0; io->best_params[e][0..num_params) = 0.0f.
+ *     other  SRBD_RESET_REFERENCE, WBInterface.reset statement for statement: srbd_pgg_reset on pgg[e] (step_freq left
+ *            alone), frg[e].lift_off = initial_feet[e] (that table only), vfa[e].initialized[0..3] = 0.  stc,
+ *            terrain_est, rising_edge and best_params are not touched.
+ *     at both levels every io->contact_rows[i][e][0..4) = 1.0f (self.current_contact = [1, 1, 1, 1], :483): the
+ *     caller names which of its num_envs x 4 float32 contact tensors these are (the loop's previous-contact rows).
+ *   Every struct array, rising_edge and best_params may be NULL: that piece is not part of the caller's loop.  A
+ *   snapshot is required for every struct that is given, whatever the mask holds: the levels live in device memory, so
+ *   the host call's rule (a snapshot at level 2 only) cannot be applied here.  initial_feet (num_envs x 4 x 3 float64)
+ *   is required with frg.  The struct arrays are 8-byte aligned (any device allocation is).
+ *   Launch shape: one wave per environment, four waves per 256-thread block, ceil(num_envs / 4) blocks.  The wave
+ *   loads its mask word once, makes it wave-uniform and leaves at once when it is 0; otherwise a struct's 8-byte words
+ *   are spread over the 64 lanes (srbd_frg, 104 words, takes two rounds) as 8-byte loads and stores.  No LDS, no
+ *   atomics, no scratch; waves share nothing.
+ *   Equivalence: environment e afterwards holds, byte for byte, what srbd_loop_reset leaves on host copies of its
+ *   structs at the level its mask word selects, and every contact row holds ones.  Environments are independent.
+ *   Enqueue contract (the producers' above): exactly one launch on hip_stream, no synchronising HIP call, no device
+ *   memory touched from the host; the stream handle is read as srbd_prepare_state_device reads it -- and as
+ *   srbd_batch_step_device reads an explicit one (hipStreamLegacy selects the legacy null stream; NULL selects it too,
+ *   there being no batch whose stream it could mean).  The call touches no srbd_batch: the gait fields of a batch's
+ *   step input are rewritten by srbd_batch_set_gait_device every step, so it enters no ordering rule of the batch.
+ *   SRBD_E_INVALID (before any HIP call, with a message for srbd_last_error(NULL)): num_envs outside 1..4096; a NULL
+ *   io or io->mask; n_contact_rows outside 0..4 or a NULL row among them; frg without initial_feet; a struct without
+ *   its snapshot; best_params with num_params < 1; a struct array or snapshot that is not 8-byte aligned.  A failed
+ *   launch: SRBD_E_HIP, or SRBD_E_NODEVICE where no device exists.
+ *   Out of scope: the simulator's own reset; advancing or re-seeding the per-environment keys (the caller's tensor);
+ *   compacting the reset environments into a smaller grid (their count would have to reach the host). */
+struct srbd_terrain_est;
+typedef struct srbd_loop_reset_io {
+    const int32_t* mask;          /* E */
+    const double* initial_feet;   /* E x 4 x 3, or NULL when frg is */
+    struct srbd_pgg* pgg;         /* E device structs each, or NULL */
+    struct srbd_frg* frg;
+    struct srbd_stc* stc;
+    struct srbd_terrain_est* terrain_est;
+    struct srbd_vfa* vfa;
+    const struct srbd_pgg* pgg_snapshot; /* E device structs each: required where the struct array is given */
+    const struct srbd_frg* frg_snapshot;
+    const struct srbd_stc* stc_snapshot;
+    const struct srbd_terrain_est* terrain_est_snapshot;
+    const struct srbd_vfa* vfa_snapshot;
+    int32_t* rising_edge;         /* E, or NULL */
+    float* best_params;           /* E x num_params, or NULL */
+    float* contact_rows[4];       /* n_contact_rows tensors of E x 4 */
+    int32_t num_params, n_contact_rows;
+} srbd_loop_reset_io;
+int srbd_loop_reset_device(int32_t num_envs, const srbd_loop_reset_io* io, void* hip_stream);
 
 /* Diagnostic: enable != 0 stamps the phases of the following TAMOLS calls; out_us[5] (may be NULL)
  * receives the last call's mean per-block durations of (patch, queries, scores, slice argmin + count)

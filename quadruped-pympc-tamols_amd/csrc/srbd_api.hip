@@ -188,6 +188,8 @@ static int fail(srbd_ctx* c, int code, const std::string& m) {
     return code;
 }
 
+int srbd::fail_global(int code, const char* message) { return fail(nullptr, code, message); }
+
 // ------------------------------------------------------------------ configuration
 static int params_leg(const srbd_config* c) {
     if (c->parametrization == SRBD_LINEAR_SPLINE) return (c->num_splines + 1) * 3;

@@ -17,6 +17,7 @@
 #include "srbd_frg.h"
 #include "srbd_gait_adapt.h"
 #include "srbd_jaxrng.h"
+#include "srbd_reset.h"
 #include "srbd_stc.h"
 #include "srbd_terrain.h"
 #include "srbd_vfa.h"
@@ -34,23 +35,11 @@ double pymod1(double x) {
     return r;
 }
 
-void gait_offsets(int32_t gait, double off[4]) {  // PGG:24-41
-    static const double tab[7][4] = {{0.5, 1.0, 1.0, 0.5},    {0.8, 0.3, 0.8, 0.3},  {0.5, 0.5, 0.0, 0.0},
-                                     {0.0, 0.25, 0.75, 0.5},  {0.0, 0.25, 0.5, 0.75}, {0.0, 0.5, 0.75, 0.25},
-                                     {0.5, 1.0, 0.75, 1.25}};
-    static const double other[4] = {0.0, 0.5, 0.5, 0.0};
-    memcpy(off, (gait >= 0 && gait < 7) ? tab[gait] : other, sizeof(double) * 4);
-}
-
 }  // namespace
 
 extern "C" int srbd_pgg_reset(srbd_pgg* g) {
     if (!g) return SRBD_E_INVALID;
-    gait_offsets(g->gait_type, g->phase_offset);
-    for (int l = 0; l < 4; ++l) {
-        g->phase_signal[l] = g->phase_offset[l];
-        g->init[l] = 0;
-    }
+    for (int l = 0; l < 4; ++l) srbd::pgg_reset_leg(g, l);  // PGG:22-46 (srbd_reset.h, shared with the device reset)
     return SRBD_OK;
 }
 
@@ -155,14 +144,11 @@ extern "C" int srbd_prepare_state(const double state_in[24], const double ref_in
 // ------------------------------------------------------------------ foothold reference generator (srbd_frg.h)
 extern "C" int srbd_frg_init(srbd_frg* g, double stance_time, double hip_height, const double* lift_off) {  // FRG:15-51
     if (!g || !lift_off || !std::isfinite(stance_time) || !std::isfinite(hip_height)) return SRBD_E_INVALID;
-    memset(g, 0, sizeof(*g));
-    g->stance_time = stance_time;
-    g->hip_height = hip_height;
-    g->hip_offset = 0.1;
-    memcpy(g->lift_off, lift_off, sizeof(g->lift_off));
-    memcpy(g->lift_off_h, lift_off, sizeof(g->lift_off_h));  // the reference's "TODO wrong", reproduced
-    memcpy(g->touch_down, lift_off, sizeof(g->touch_down));
-    memcpy(g->touch_down_h, lift_off, sizeof(g->touch_down_h));
+    double feet[12];  // lift_off may be a table of g itself
+    memcpy(feet, lift_off, sizeof(feet));
+    // srbd_reset.h, shared with the device reset: the four tables are copies of lift_off (the _h tables too: the
+    // reference's "TODO wrong", reproduced), everything behind them zero
+    srbd::frg_init_words(g, stance_time, hip_height, 0.1, feet, 0, 1);
     return SRBD_OK;
 }
 
@@ -327,7 +313,7 @@ extern "C" int srbd_vfa_init(srbd_vfa* g) {  // VFA:38-46
 
 extern "C" int srbd_vfa_reset(srbd_vfa* g) {  // VFA:63-64
     if (!g) return SRBD_E_INVALID;
-    for (int l = 0; l < 4; ++l) g->initialized[l] = 0;
+    for (int l = 0; l < 4; ++l) srbd::vfa_reset_leg(g, l);
     return SRBD_OK;
 }
 
@@ -351,6 +337,23 @@ extern "C" int srbd_vfa_commit(srbd_vfa* g, int32_t mode, const double seeds[12]
         srbd::vfa_commit_leg(g, l, mode, seeds + 3 * l, search ? searched_footholds + 3 * l : nullptr,
                              search ? searched_boxes + 6 * l : nullptr, search ? searched_valid[l] : 0,
                              out_footholds + 3 * l, out_boxes + 6 * l, out_valid + l);
+    return SRBD_OK;
+}
+
+// ------------------------------------------- per-environment reset of the loop's state (srbd_reset.h)
+extern "C" int srbd_loop_reset(int32_t level, const double initial_feet[12], srbd_pgg* pgg, srbd_frg* frg,
+                               srbd_stc* stc, srbd_terrain_est* terrain_est, srbd_vfa* vfa,
+                               const srbd_pgg* pgg_snapshot, const srbd_frg* frg_snapshot,
+                               const srbd_stc* stc_snapshot, const srbd_terrain_est* terrain_est_snapshot,
+                               const srbd_vfa* vfa_snapshot, int32_t* rising_edge, float* best_params,
+                               int32_t num_params) {  // WBI:469-484, SIM:773-781
+    const srbd::LoopResetEnv x = {initial_feet,  pgg,          frg,          stc,
+                                  terrain_est,   vfa,          pgg_snapshot, frg_snapshot,
+                                  stc_snapshot,  terrain_est_snapshot, vfa_snapshot, rising_edge,
+                                  best_params,   num_params};
+    if (level != SRBD_RESET_REFERENCE && level != SRBD_RESET_EPISODE) return SRBD_E_INVALID;
+    if (srbd::loop_reset_refusal(x, level)) return SRBD_E_INVALID;
+    srbd::loop_reset_env(x, level, 0, 1);
     return SRBD_OK;
 }
 

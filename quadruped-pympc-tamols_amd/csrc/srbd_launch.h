@@ -340,4 +340,29 @@ void launch_tamols_batch(const TamolsBatchJob& j, hipStream_t s);
 // is SEARCH, copies its leg's held foothold or seed and leaves before the search's first stage.
 void launch_tamols_batch_gated(const TamolsBatchJob& j, hipStream_t s);
 
+// The per-environment reset of the loop's device state (srbd_loop_reset_device; srbd_producers.hip
+// loop_reset_kernel): the arrays of one call (include/srbd_mpc.h srbd_loop_reset_io), E entries each.  One wave per
+// environment, LOOP_RESET_WAVES of them per block.
+constexpr int LOOP_RESET_WAVES = 4;
+struct LoopResetJob {
+    const int32_t* mask;
+    const double* feet;
+    srbd_pgg* pgg;
+    srbd_frg* frg;
+    srbd_stc* stc;
+    srbd_terrain_est* terr;
+    srbd_vfa* vfa;
+    const srbd_pgg* pgg0;
+    const srbd_frg* frg0;
+    const srbd_stc* stc0;
+    const srbd_terrain_est* terr0;
+    const srbd_vfa* vfa0;
+    int32_t* rising_edge;
+    float* best;
+    float* rows[4];
+    int32_t num_params, n_rows;
+};
+// srbd_api.hip: the calling thread's error text (srbd_last_error(NULL)) for an entry point that has no handle.
+int fail_global(int code, const char* message);
+
 }  // namespace srbd

@@ -33,14 +33,20 @@
 // single-environment one (tamols_kernel.hip tamols_batch_kernel), whose device functions it runs.  So is
 // srbd_vfa_step_device, the same search behind the reference's apex gate (srbd_vfa.h; wb_interface.py:230-246): the
 // same job with the gate's four fields, the same grid, the kernel's gated instantiation.
+// loop_reset_kernel (srbd_loop_reset_device) restarts the environments a mask names (srbd_reset.h; simulation/
+// simulation.py:773-781, wb_interface.py:469-484): one wave per environment, see the kernel.
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <stdio.h>
+
+#include <initializer_list>
 
 #include "../../include/srbd_host.h"
 #include "../../include/srbd_mpc.h"
 #include "srbd_frg.h"
 #include "srbd_gait_adapt.h"
 #include "srbd_launch.h"
+#include "srbd_reset.h"
 #include "srbd_stc.h"
 #include "srbd_terrain.h"
 #include "yaw_sincos.h"
@@ -421,6 +427,40 @@ __global__ void __launch_bounds__(PROD_BLOCK) gait_apply_freq_kernel(srbd_pgg* _
     ga_apply_freq(pgg + e, frg ? frg + e : nullptr, stc ? stc + e : nullptr, optimize[e], best_freq[e]);
 }
 
+// srbd_loop_reset of srbd_host.cpp per environment (srbd_reset.h loop_reset_env, the statements both sides run).  One
+// wave owns one environment: the wave index and with it e are wave-uniform, the mask word is loaded once and made
+// uniform too, and a wave whose word is 0 leaves after that one load -- it reads nothing else of its environment and
+// writes nothing.  A reset wave spreads each struct's 8-byte words over its lanes (lane l takes the words l, l + 64,
+// ..: consecutive lanes, consecutive addresses) and lanes 0..15 the up to four contact rows.  Every pointer of the job
+// is a kernel argument, so the branches on them are uniform as well.  Waves share nothing: no LDS, no atomics.
+__global__ void __launch_bounds__(64 * LOOP_RESET_WAVES) loop_reset_kernel(int E, const LoopResetJob j) {
+    const int e = blockIdx.x * LOOP_RESET_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (e >= E) return;
+    const int32_t level = loop_reset_level(__builtin_amdgcn_readfirstlane(j.mask[e]));
+    if (level == 0) return;
+    const int lane = threadIdx.x & 63;
+    const size_t n = (size_t)e;
+    const LoopResetEnv x = {j.feet ? j.feet + 12 * n : nullptr,
+                            j.pgg ? j.pgg + n : nullptr,
+                            j.frg ? j.frg + n : nullptr,
+                            j.stc ? j.stc + n : nullptr,
+                            j.terr ? j.terr + n : nullptr,
+                            j.vfa ? j.vfa + n : nullptr,
+                            j.pgg0 ? j.pgg0 + n : nullptr,
+                            j.frg0 ? j.frg0 + n : nullptr,
+                            j.stc0 ? j.stc0 + n : nullptr,
+                            j.terr0 ? j.terr0 + n : nullptr,
+                            j.vfa0 ? j.vfa0 + n : nullptr,
+                            j.rising_edge ? j.rising_edge + n : nullptr,
+                            j.best ? j.best + n * (size_t)j.num_params : nullptr,
+                            j.num_params};
+    loop_reset_env(x, level, lane, 64);
+    const int r = lane >> 2;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        if (i == r && i < j.n_rows) loop_reset_contact(j.rows[i] + 4 * n, lane & 3, 4);
+}
+
 }  // namespace srbd
 
 using namespace srbd;
@@ -686,6 +726,52 @@ extern "C" int srbd_vfa_step_device(srbd_vfa* d_vfa, const srbd_stc* d_stc, srbd
     j.mode = d_mode;
     j.apex_interval = apex_interval;
     launch_tamols_batch_gated(j, stream_of(hip_stream));
+    return launch_status();
+}
+
+extern "C" int srbd_loop_reset_device(int32_t num_envs, const srbd_loop_reset_io* io, void* hip_stream) {
+    if (!envs_ok(num_envs)) return fail_global(SRBD_E_INVALID, "srbd_loop_reset_device: num_envs must be 1..4096");
+    if (!io) return fail_global(SRBD_E_INVALID, "srbd_loop_reset_device: null io");
+    if (!io->mask) return fail_global(SRBD_E_INVALID, "srbd_loop_reset_device: null mask");
+    if (io->n_contact_rows < 0 || io->n_contact_rows > 4)
+        return fail_global(SRBD_E_INVALID, "srbd_loop_reset_device: n_contact_rows must be 0..4");
+    LoopResetJob j = {};
+    for (int i = 0; i < io->n_contact_rows; ++i) {
+        if (!io->contact_rows[i]) return fail_global(SRBD_E_INVALID, "srbd_loop_reset_device: null contact row");
+        j.rows[i] = io->contact_rows[i];
+    }
+    j.n_rows = io->n_contact_rows;
+    j.mask = io->mask;
+    j.feet = io->initial_feet;
+    j.pgg = io->pgg;
+    j.frg = io->frg;
+    j.stc = io->stc;
+    j.terr = io->terrain_est;
+    j.vfa = io->vfa;
+    j.pgg0 = io->pgg_snapshot;
+    j.frg0 = io->frg_snapshot;
+    j.stc0 = io->stc_snapshot;
+    j.terr0 = io->terrain_est_snapshot;
+    j.vfa0 = io->vfa_snapshot;
+    j.rising_edge = io->rising_edge;
+    j.best = io->best_params;
+    j.num_params = io->num_params;
+    // the host call's refusals; the levels are in device memory, so a struct needs its snapshot whatever they are
+    const LoopResetEnv x = {j.feet, j.pgg, j.frg, j.stc, j.terr, j.vfa, j.pgg0, j.frg0, j.stc0, j.terr0, j.vfa0,
+                            j.rising_edge, j.best, j.num_params};
+    if (const char* why = loop_reset_refusal(x, -1)) {
+        static thread_local char text[96];
+        snprintf(text, sizeof(text), "srbd_loop_reset_device: %s", why);
+        return fail_global(SRBD_E_INVALID, text);
+    }
+    for (const void* p : {(const void*)j.feet, (const void*)j.pgg, (const void*)j.frg, (const void*)j.stc,
+                          (const void*)j.terr, (const void*)j.vfa, (const void*)j.pgg0, (const void*)j.frg0,
+                          (const void*)j.stc0, (const void*)j.terr0, (const void*)j.vfa0})
+        if ((uintptr_t)p % 8 != 0)
+            return fail_global(SRBD_E_INVALID, "srbd_loop_reset_device: a struct array is not 8-byte aligned");
+    const unsigned blocks = (unsigned)((num_envs + LOOP_RESET_WAVES - 1) / LOOP_RESET_WAVES);
+    hipLaunchKernelGGL(loop_reset_kernel, dim3(blocks), dim3(64 * LOOP_RESET_WAVES), 0, stream_of(hip_stream),
+                       num_envs, j);
     return launch_status();
 }
 

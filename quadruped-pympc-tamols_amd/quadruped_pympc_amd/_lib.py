@@ -253,6 +253,18 @@ class SrbdTerrainRefBatchIo(C.Structure):
                 ("feet", _P), ("frg", _P), ("ref_z", _D), ("ref", _P), ("terrain", _P)]
 
 
+RESET_REFERENCE, RESET_EPISODE = 1, 2
+
+
+class SrbdLoopResetIo(C.Structure):
+    """srbd_loop_reset_io (include/srbd_mpc.h): the device arrays of one srbd_loop_reset_device call."""
+    _fields_ = [("mask", _P), ("initial_feet", _P),
+                ("pgg", _P), ("frg", _P), ("stc", _P), ("terrain_est", _P), ("vfa", _P),
+                ("pgg_snapshot", _P), ("frg_snapshot", _P), ("stc_snapshot", _P), ("terrain_est_snapshot", _P),
+                ("vfa_snapshot", _P), ("rising_edge", _P), ("best_params", _P), ("contact_rows", _P * 4),
+                ("num_params", _I), ("n_contact_rows", _I)]
+
+
 SHM_DOUBLES = 75
 
 
@@ -348,6 +360,11 @@ SIGNATURES.update({
     "srbd_gait_apply_freq_device": (_I, [_P, _P, _P, _I, _P, _P, _P]),
     # the apex-gated foothold adaptation: srbd_tamols_batch_device behind the gate
     "srbd_vfa_step_device": (_I, [_P, _P, _P, C.POINTER(TamolsParams), _I, C.POINTER(TamolsBatchIO), _D, _P, _P]),
+    # the per-environment reset of the loop's state: the host call and its device form
+    "srbd_loop_reset": (_I, [_I, _DP, C.POINTER(SrbdPgg), C.POINTER(SrbdFrg), C.POINTER(SrbdStc),
+                             C.POINTER(SrbdTerrainEst), C.POINTER(SrbdVfa), C.POINTER(SrbdPgg), C.POINTER(SrbdFrg),
+                             C.POINTER(SrbdStc), C.POINTER(SrbdTerrainEst), C.POINTER(SrbdVfa), _IP, _FP, _I]),
+    "srbd_loop_reset_device": (_I, [_I, C.POINTER(SrbdLoopResetIo), _P]),
 })
 
 # srbd_time_launch kinds (include/srbd_mpc.h)
@@ -1606,3 +1623,75 @@ def terrain_ref_step_device(terrain, base_pos, com_pos, yaws, lin, ang, ref, ref
         return lib.srbd_terrain_ref_step_device(terrain.data_ptr(), E, C.byref(io), s)
 
     return _enqueue(dev, stream, lambda: out, call, "srbd_terrain_ref_step_device")
+
+
+LOOP_RESET_STRUCTS = ("pgg", "frg", "stc", "terrain_est", "vfa")
+
+
+def loop_reset_device(mask, initial_feet=None, *, pgg=None, frg=None, stc=None, terrain_est=None, vfa=None,
+                      snapshots=None, rising_edge=None, best_params=None, contact_rows=(), stream=None):
+    """srbd_loop_reset_device: restart the environments ``mask`` names, one launch enqueued on ``stream`` (None:
+    torch's current stream) without a host synchronisation.  mask (E,) int32: 0 leaves environment e untouched and
+    unread, 2 is the episode reset (every struct back to its snapshot's bytes, frg rebuilt on the new feet, the
+    trigger word and the warm-start row cleared), any other value the reference's ``WBInterface.reset``
+    (wb_interface.py:469-484).  pgg / frg / stc / terrain_est / vfa: the (E, *_BYTES) uint8 device states, each
+    optional; ``snapshots`` maps the same names to tensors of the same shape, one for every state given;
+    initial_feet (E, 4, 3) float64, required with frg; rising_edge (E,) int32; best_params (E, P) float32;
+    contact_rows up to four (E, 4) float32 tensors, set to ones for every reset environment."""
+    import torch
+
+    E = int(mask.shape[0]) if isinstance(mask, torch.Tensor) and mask.dim() == 1 else 0
+    if not 1 <= E <= MAX_ENVS:
+        raise ValueError(f"mask must be a torch tensor of shape (1..{MAX_ENVS},), got "
+                         f"{tuple(getattr(mask, 'shape', ()))}")
+    u8, f32_, i32 = (torch.uint8,), (torch.float32,), (torch.int32,)
+    sizes = dict(pgg=PGG_BYTES, frg=FRG_BYTES, stc=STC_BYTES, terrain_est=TERRAIN_EST_BYTES, vfa=VFA_BYTES)
+    given = dict(pgg=pgg, frg=frg, stc=stc, terrain_est=terrain_est, vfa=vfa)
+    snapshots = dict(snapshots or {})
+    unknown = set(snapshots) - set(LOOP_RESET_STRUCTS)
+    if unknown:
+        raise ValueError(f"unknown snapshot {sorted(unknown)[0]!r}: the structs are {', '.join(LOOP_RESET_STRUCTS)}")
+    specs = [("mask", mask, (E,), i32)]
+    for name in LOOP_RESET_STRUCTS:
+        if given[name] is None:
+            continue
+        if snapshots.get(name) is None:
+            raise ValueError(f"{name} is given without its snapshot (snapshots[{name!r}])")
+        specs.append((name, given[name], (E, sizes[name]), u8))
+        specs.append((f"snapshots[{name!r}]", snapshots[name], (E, sizes[name]), u8))
+    if frg is not None and initial_feet is None:
+        raise ValueError("frg is given without initial_feet")
+    if initial_feet is not None:
+        specs.append(("initial_feet", initial_feet, (E, 4, 3), (torch.float64,)))
+    if rising_edge is not None:
+        specs.append(("rising_edge", rising_edge, (E,), i32))
+    P = 0
+    if best_params is not None:
+        P = int(best_params.shape[1]) if isinstance(best_params, torch.Tensor) and best_params.dim() == 2 else 0
+        if P < 1:
+            raise ValueError(f"best_params must be ({E}, >=1) float32, got {tuple(getattr(best_params, 'shape', ()))}")
+        specs.append(("best_params", best_params, (E, P), f32_))
+    rows = tuple(contact_rows)
+    if len(rows) > 4:
+        raise ValueError(f"at most 4 contact rows, got {len(rows)}")
+    for i, r in enumerate(rows):
+        specs.append((f"contact_rows[{i}]", r, (E, 4), f32_))
+    dev = _device_tensors(specs)
+
+    def ptr(t):
+        return None if t is None else t.data_ptr()
+
+    def call(o, s):
+        io = SrbdLoopResetIo(mask=mask.data_ptr(), initial_feet=ptr(initial_feet), rising_edge=ptr(rising_edge),
+                             best_params=ptr(best_params), num_params=P, n_contact_rows=len(rows),
+                             contact_rows=(_P * 4)(*[r.data_ptr() for r in rows]))
+        for name in LOOP_RESET_STRUCTS:
+            if given[name] is not None:
+                setattr(io, name, given[name].data_ptr())
+                setattr(io, name + "_snapshot", snapshots[name].data_ptr())
+        rc = lib.srbd_loop_reset_device(E, C.byref(io), s)
+        if rc == E_INVALID:
+            raise ValueError(last_error(None))
+        return rc
+
+    _enqueue(dev, stream, lambda: None, call, "srbd_loop_reset_device")

@@ -210,9 +210,17 @@ class BatchedPeriodicGaitGenerator:
         with self._on(stream):
             self.state.copy_(torch.from_numpy(raw.reshape(self.num_envs, _lib.PGG_BYTES).copy()))
 
-    def reset(self, stream=None):
+    def reset(self, stream=None, *, mask=None):
         """``PeriodicGaitGenerator.reset`` of every environment: the phases back to the gaits' offsets, the holds
-        cleared."""
+        cleared.  ``mask`` (E,) bool, int32 or int64 cuda tensor: only the environments whose entry is not zero, one
+        launch (``srbd_loop_reset_device`` at the reference's level), the others untouched; no host wait."""
+        if mask is not None:
+            from .loop_reset import reference_words
+
+            # the words are 0 or 1, so the snapshot the call asks for is never read: the state stands in for it
+            _lib.loop_reset_device(reference_words(mask, self.num_envs, stream), pgg=self.state,
+                                   snapshots={"pgg": self.state}, stream=stream)
+            return
         ph, off, ini = self._views()
         with self._on(stream):
             ph.copy_(off)

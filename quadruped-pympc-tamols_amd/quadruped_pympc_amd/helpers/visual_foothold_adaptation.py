@@ -386,12 +386,21 @@ class BatchedVisualFootholdAdaptation:
         with torch.cuda.stream(torch.cuda.current_stream(state.device)):
             state.copy_(torch.from_numpy(raw.reshape(self.num_envs, _lib.VFA_BYTES).copy()))
 
-    def reset(self, stream=None):
+    def reset(self, stream=None, *, mask=None):
         """The reference's ``reset()`` for every environment: ``initialized`` cleared, in stream order (``stream``
-        None: torch's current stream), nothing else touched and nothing synchronised."""
+        None: torch's current stream), nothing else touched and nothing synchronised.  ``mask`` (E,) bool, int32 or
+        int64 cuda tensor: only the environments whose entry is not zero, one launch (``srbd_loop_reset_device`` at
+        the reference's level), the others untouched."""
         import torch
 
         state = self.state
+        if mask is not None:
+            from .loop_reset import reference_words
+
+            # the words are 0 or 1, so the snapshot the call asks for is never read: the state stands in for it
+            _lib.loop_reset_device(reference_words(mask, self.num_envs, stream), vfa=state, snapshots={"vfa": state},
+                                   stream=stream)
+            return
         o = _lib.SrbdVfa.initialized.offset // 4
         with torch.cuda.stream(torch.cuda.current_stream(state.device) if stream is None else stream):
             state.view(torch.int32)[:, o:o + 4].zero_()
