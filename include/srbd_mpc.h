@@ -485,10 +485,10 @@ int srbd_interface_step(srbd_ctx* ctx, srbd_interface_io* io, const float* conta
  *   beyond that one environment fills the GPU and separate contexts lose nothing).
  *   Supported: MPPI and random sampling; the three parametrizations at any H and S srbd_create takes; the Philox
  *   and both JAX streams; injected noise.
- *   SRBD_E_INVALID (with a message saying which and why): a larger N or num_envs, CEM-MPPI (its draws depend on
- *   the sigma each step produces, and its merge is one context's column-split hand-off), rank / world_size other
- *   than 0 / 1.  use_graph is ignored.  Gait-adaptive sampling and the opt-in cost terms have batch forms
- *   (srbd_batch_set_gait, srbd_batch_set_cost_terms below), but not both at once.  There are no batch forms of CEM,
+ *   SRBD_E_INVALID (with a message saying which and why): a larger N or num_envs, CEM-MPPI (sigma is part of every
+ *   CEM step: srbd_batch_create_cem and the _cem step calls below), rank / world_size other than 0 / 1.  use_graph
+ *   is ignored.  Gait-adaptive sampling and the opt-in cost terms have batch forms
+ *   (srbd_batch_set_gait, srbd_batch_set_cost_terms below), but not both at once.  There are no batch forms of
  *   armed steps or the single context's device-resident chains (srbd_device_step_local and its kin); the batch's
  *   device-resident form is srbd_batch_step_device.  A failed allocation: SRBD_E_NOMEM; no device: SRBD_E_NODEVICE.
  *   A call that returns an error has changed nothing in best_params.  A step whose launches end without publishing
@@ -578,6 +578,46 @@ typedef struct srbd_batch_device_io {
     float* costs;              /* E x N saturated costs, or NULL */
 } srbd_batch_device_io;
 int srbd_batch_step_device(srbd_batch* b, const srbd_batch_device_io* io, void* hip_stream);
+
+/* Batched CEM-MPPI.  CEM's sigma is part of every step (in: the spread the draws are scaled by; out: the elite rows'
+ * clipped standard deviation, centroidal_nmpc_jax.py:1075-1081), so a CEM batch has a creator and step calls of its
+ * own; srbd_batch_create keeps refusing SRBD_CEM_MPPI.
+ *   srbd_batch_create_cem: srbd_batch_create's ranges (1 <= num_envs <= 4096, N <= 16 384, rank / world_size 0 / 1)
+ *   with method == SRBD_CEM_MPPI and 2 <= num_elite <= SRBD_MAX_ELITE as srbd_create requires (0 selects 10).  Any
+ *   other method, and every violation, returns SRBD_E_INVALID with a message, before any HIP call.
+ *   srbd_batch_step_cem: srbd_batch_step with sigma, E x P, in / out.  Injected noise is used as given (it is not
+ *   multiplied by sigma, as srbd_step treats it); device draws are the unscaled srbd_draw_noise rows, multiplied by
+ *   sigma[e] where they are read.
+ *   srbd_batch_step_cem_device: srbd_batch_step_device with cem->sigma, E x P device memory of the batch's device
+ *   (it must not overlap the other arrays).  sigma_reset > 0: every environment starts this step from that constant
+ *   and sigma is only written -- the reference's with_newsigma(sigma_cem_mppi) at the first sampling iteration of a
+ *   control step (srbd_controller_interface.py:128-129), at no extra launch.  sigma_reset == 0: sigma is read and
+ *   rewritten.  The enqueue contract, the stream handle, the ordering rule and the five launches are
+ *   srbd_batch_step_device's; the call makes no synchronising HIP call.  Capturing it into a HIP graph is not
+ *   supported.
+ *   Equivalence: environment e returns exactly what srbd_step returns on a context srbd_create(cfg) for the same
+ *   inputs, sigma[e], (seeds[e], counters[e]) and noise stream -- every output bit for bit, the new sigma included
+ *   (the merge block folds the one fixed reduction tree with every column in one block, where one context splits
+ *   the columns over blocks: the same sums in the same order).  The device form returns the host form's bytes.
+ *   Settings: srbd_batch_set_rng as for any batch.  srbd_batch_set_cost_terms works on a CEM batch (one context runs
+ *   CEM with the opt-in cost terms on its four-lane kernel, and the batch restates that form); environment e then
+ *   equals a context that received srbd_set_cost_terms.  srbd_batch_set_gait and srbd_batch_set_gait_device return
+ *   SRBD_E_INVALID on a CEM batch, as srbd_set_gait does on a CEM context.
+ *   Mixing: srbd_batch_step / srbd_batch_step_device on a CEM batch, and the _cem steps on a batch made by
+ *   srbd_batch_create, return SRBD_E_INVALID and change nothing.  srbd_batch_copy_costs serves both kinds.
+ *   SRBD_E_INVALID besides (before anything is enqueued): b, io or cem NULL, a required pointer NULL (sigma among
+ *   them, also with sigma_reset > 0: it is written), contact_stride < H, sigma_reset negative or not finite. */
+typedef struct srbd_batch_cem_io {
+    float* sigma;        /* E x P, in / out (sigma_reset > 0: out only) */
+    float sigma_reset;   /* > 0: the step starts from this constant; 0: from sigma */
+    int32_t pad;
+} srbd_batch_cem_io;
+int srbd_batch_create_cem(const srbd_config* cfg, int32_t num_envs, srbd_batch** out);
+int srbd_batch_step_cem(srbd_batch* b, const float* states, const float* refs, const float* contacts,
+                        int32_t contact_stride, float* best_params, float* sigma, const float* noise,
+                        const uint64_t* seeds, const uint64_t* counters, srbd_result* out, float* out_costs);
+int srbd_batch_step_cem_device(srbd_batch* b, const srbd_batch_device_io* io, const srbd_batch_cem_io* cem,
+                               void* hip_stream);
 
 /* The producers of the device-resident step on the device: the periodic gait generator and
  * prepare_state_and_reference (srbd_host.h: srbd_pgg_run, srbd_pgg_contact_sequence, srbd_prepare_state) for

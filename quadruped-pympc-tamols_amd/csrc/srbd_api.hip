@@ -2706,7 +2706,8 @@ extern "C" const char* srbd_batch_last_error(const srbd_batch* b) {
 
 extern "C" int srbd_batch_num_envs(const srbd_batch* b) { return b ? b->E : SRBD_E_INVALID; }
 
-extern "C" int srbd_batch_create(const srbd_config* cfg, int32_t num_envs, srbd_batch** out) {
+// cem: srbd_batch_create_cem (CEM-MPPI and nothing else); else srbd_batch_create (everything but CEM-MPPI)
+static int batch_create(const srbd_config* cfg, int32_t num_envs, srbd_batch** out, bool cem) {
     if (!cfg || !out) return fail(nullptr, SRBD_E_INVALID, "null argument");
     *out = nullptr;
     if (num_envs < 1 || num_envs > BATCH_MAX_ENVS)
@@ -2716,10 +2717,14 @@ extern "C" int srbd_batch_create(const srbd_config* cfg, int32_t num_envs, srbd_
                     "num_samples per environment must be <= " + std::to_string(BATCH_MAX_SAMPLES) +
                         " (256 leaves, what one merge block folds): beyond that one environment fills the GPU, use "
                         "separate contexts");
-    if (cfg->method == SRBD_CEM_MPPI)
+    if (!cem && cfg->method == SRBD_CEM_MPPI)
         return fail(nullptr, SRBD_E_INVALID,
-                    "CEM-MPPI has no batch form: its draws depend on each step's sigma and its merge is the "
-                    "column-split hand-off of one context");
+                    "srbd_batch_create does not take CEM-MPPI (sigma is part of every step): create the batch with "
+                    "srbd_batch_create_cem and step it with srbd_batch_step_cem / srbd_batch_step_cem_device");
+    if (cem && cfg->method != SRBD_CEM_MPPI)
+        return fail(nullptr, SRBD_E_INVALID,
+                    "srbd_batch_create_cem takes method SRBD_CEM_MPPI only: MPPI and random sampling go through "
+                    "srbd_batch_create");
     if ((cfg->world_size > 1) || cfg->rank != 0)
         return fail(nullptr, SRBD_E_INVALID, "a batch is unsharded: rank / world_size must be 0 / 1");
     ModelConst mc;
@@ -2793,6 +2798,16 @@ extern "C" int srbd_batch_create(const srbd_config* cfg, int32_t num_envs, srbd_
     return SRBD_OK;
 }
 
+extern "C" int srbd_batch_create(const srbd_config* cfg, int32_t num_envs, srbd_batch** out) {
+    return batch_create(cfg, num_envs, out, false);
+}
+
+// A CEM-MPPI batch: build_model checks num_elite (2 .. SRBD_MAX_ELITE) as it does for srbd_create; the leaf records
+// carry each leaf's K smallest keys, the merge block folds every column unsplit and writes out[e].sigma.
+extern "C" int srbd_batch_create_cem(const srbd_config* cfg, int32_t num_envs, srbd_batch** out) {
+    return batch_create(cfg, num_envs, out, true);
+}
+
 extern "C" int srbd_batch_set_rng(srbd_batch* b, int32_t kind) {
     if (!b) return SRBD_E_INVALID;
     if (kind != SRBD_RNG_PHILOX && kind != SRBD_RNG_JAX && kind != SRBD_RNG_JAX_LEGACY)
@@ -2811,6 +2826,9 @@ extern "C" int srbd_batch_set_gait(srbd_batch* b, const float* timings, float pg
     srbd_ctx* c = &b->c;
     ModelConst& mc = c->mc;
     if (!timings || !freq_sets) return fail(c, SRBD_E_INVALID, "null argument");
+    if (mc.method == SRBD_CEM_MPPI)
+        return fail(c, SRBD_E_INVALID,
+                    "gait-adaptive CEM is not provided (the reference's branch is broken as wired, SURVEY App. B #2)");
     if (n_freq < 1 || n_freq > SRBD_MAX_FREQS)
         return fail(c, SRBD_E_INVALID, "n_freq must be in [1, " + std::to_string(SRBD_MAX_FREQS) + "]");
     if (mc.kind != SRBD_ZERO_ORDER && mc.S + 1 > GA_MAXCB) return fail(c, SRBD_E_INVALID, "num_splines > 32");
@@ -2865,6 +2883,9 @@ extern "C" int srbd_batch_set_gait_device(srbd_batch* b, const srbd_batch_gait_i
         return fail(c, SRBD_E_INVALID, "n_freq must be in [1, " + std::to_string(SRBD_MAX_FREQS) + "]");
     if (!b) return fail(nullptr, SRBD_E_INVALID, "srbd_batch_set_gait_device: null batch");
     ModelConst& mc = c->mc;
+    if (mc.method == SRBD_CEM_MPPI)
+        return fail(c, SRBD_E_INVALID,
+                    "gait-adaptive CEM is not provided (the reference's branch is broken as wired, SURVEY App. B #2)");
     if (mc.kind != SRBD_ZERO_ORDER && mc.S + 1 > GA_MAXCB) return fail(c, SRBD_E_INVALID, "num_splines > 32");
     if (mc.cost_on)
         return fail(c, SRBD_E_INVALID,
@@ -2955,12 +2976,18 @@ extern "C" int srbd_batch_copy_costs(srbd_batch* b, float* out_costs) {
     return SRBD_OK;
 }
 
-extern "C" int srbd_batch_step(srbd_batch* b, const float* states, const float* refs, const float* contacts,
-                               int32_t contact_stride, float* best_params, const float* noise, const uint64_t* seeds,
-                               const uint64_t* counters, srbd_result* out, float* out_costs) {
+// srbd_batch_step (sigma NULL, cem false) and srbd_batch_step_cem
+static int batch_step_host(srbd_batch* b, const float* states, const float* refs, const float* contacts,
+                           int32_t contact_stride, float* best_params, float* sigma, bool cem, const float* noise,
+                           const uint64_t* seeds, const uint64_t* counters, srbd_result* out, float* out_costs) {
     if (!b) return SRBD_E_INVALID;
     srbd_ctx* c = &b->c;
     const ModelConst& mc = c->mc;
+    if (!cem && mc.method == SRBD_CEM_MPPI)
+        return fail(c, SRBD_E_INVALID, "CEM: sigma is part of the step (srbd_batch_step_cem)");
+    if (cem && mc.method != SRBD_CEM_MPPI)
+        return fail(c, SRBD_E_INVALID, "srbd_batch_step_cem: not a CEM batch (srbd_batch_create_cem)");
+    if (cem && !sigma) return fail(c, SRBD_E_INVALID, "CEM: sigma is part of the step");
     if (!states || !refs || !contacts || !best_params || !seeds || !counters || !out || contact_stride < mc.H)
         return fail(c, SRBD_E_INVALID, "invalid step arguments");
     if (b->ga_staging_stale)
@@ -2978,11 +3005,13 @@ extern "C" int srbd_batch_step(srbd_batch* b, const float* states, const float* 
         StepInput* in = b->h_in + e;
         const int rc = fill_input(&c->cfg, mc, in, states + 24 * (size_t)e, refs + 24 * (size_t)e,
                                   contacts + (size_t)e * 4 * contact_stride, contact_stride,
-                                  best_params + (size_t)e * P, nullptr, seeds[e], counters[e]);
+                                  best_params + (size_t)e * P, cem ? sigma + (size_t)e * P : nullptr, seeds[e],
+                                  counters[e]);
         if (rc) return fail(c, rc, "invalid step arguments");
-        in->noise_scaled = noise ? 1 : 0;
+        in->noise_scaled = noise ? 1 : 0;  // CEM: injected noise is used as given, device draws are unscaled
     }
-    launch_batch_copy(b->d_in_host, b->d_in, E, offsetof(StepInput, best) + sizeof(float) * (size_t)P, c->stream);
+    launch_batch_copy(b->d_in_host, b->d_in, E, offsetof(StepInput, best) + sizeof(float) * (size_t)P, c->stream,
+                      offsetof(StepInput, sigma), cem ? sizeof(float) * (size_t)P : 0);
     if (noise) {
         const size_t bytes = sizeof(float) * (size_t)E * mc.n_local * P;
         if (!b->d_noise_rm) {
@@ -3019,6 +3048,7 @@ extern "C" int srbd_batch_step(srbd_batch* b, const float* states, const float* 
     for (int e = 0; e < E; ++e) {
         const StepOutput& o = b->h_out[e];
         memcpy(best_params + (size_t)e * P, o.best, sizeof(float) * P);
+        if (cem) memcpy(sigma + (size_t)e * P, o.sigma, sizeof(float) * P);
         memcpy(out[e].grf, o.grf, sizeof(out[e].grf));
         memcpy(out[e].predicted_state, o.pred, sizeof(out[e].predicted_state));
         out[e].best_cost = o.best_cost;
@@ -3029,15 +3059,40 @@ extern "C" int srbd_batch_step(srbd_batch* b, const float* states, const float* 
     return SRBD_OK;
 }
 
+extern "C" int srbd_batch_step(srbd_batch* b, const float* states, const float* refs, const float* contacts,
+                               int32_t contact_stride, float* best_params, const float* noise, const uint64_t* seeds,
+                               const uint64_t* counters, srbd_result* out, float* out_costs) {
+    return batch_step_host(b, states, refs, contacts, contact_stride, best_params, nullptr, false, noise, seeds,
+                           counters, out, out_costs);
+}
+
+extern "C" int srbd_batch_step_cem(srbd_batch* b, const float* states, const float* refs, const float* contacts,
+                                   int32_t contact_stride, float* best_params, float* sigma, const float* noise,
+                                   const uint64_t* seeds, const uint64_t* counters, srbd_result* out,
+                                   float* out_costs) {
+    return batch_step_host(b, states, refs, contacts, contact_stride, best_params, sigma, true, noise, seeds, counters,
+                           out, out_costs);
+}
+
 // srbd_batch_step with every array in the caller's device memory, enqueued on the caller's stream: batch_pack_kernel
 // builds d_in[e] as fill_input does, the draws / transpose (reading io->noise in place), rollouts and merges are the
 // host step's launches, the merge blocks write their records to d_out (device memory) and batch_unpack_kernel scatters
 // them and the costs rows to the caller's arrays.  The sequence word is advanced and stored as in the host step, and
 // not waited on.  No synchronising call: the event behind the last launch orders the other entry points after it.
-extern "C" int srbd_batch_step_device(srbd_batch* b, const srbd_batch_device_io* io, void* hip_stream) {
+// srbd_batch_step_device (cem NULL, is_cem false) and srbd_batch_step_cem_device: batch_pack_cem_kernel also writes
+// d_in[e].sigma (the caller's rows or the reset constant) and batch_unpack_cem_kernel also scatters d_out[e].sigma.
+static int batch_step_dev(srbd_batch* b, const srbd_batch_device_io* io, const srbd_batch_cem_io* cem, bool is_cem,
+                          void* hip_stream) {
     // the arguments first, so a bad io is named as such whatever b is (b == NULL: the calling thread's error text)
     srbd_ctx* c = b ? &b->c : nullptr;
-    if (!io) return fail(c, SRBD_E_INVALID, "srbd_batch_step_device: null io");
+    const std::string fn = is_cem ? "srbd_batch_step_cem_device" : "srbd_batch_step_device";
+    if (!io) return fail(c, SRBD_E_INVALID, fn + ": null io");
+    if (is_cem) {
+        if (!cem) return fail(c, SRBD_E_INVALID, fn + ": null cem");
+        if (!cem->sigma) return fail(c, SRBD_E_INVALID, fn + ": null required pointer: sigma");
+        if (!(cem->sigma_reset >= 0.0f && cem->sigma_reset < INFINITY))
+            return fail(c, SRBD_E_INVALID, fn + ": sigma_reset must be finite and >= 0");
+    }
     {
         const struct {
             const void* p;
@@ -3050,12 +3105,16 @@ extern "C" int srbd_batch_step_device(srbd_batch* b, const srbd_batch_device_io*
                    {io->best_freq, "best_freq"},   {io->status, "status"}};
         for (const auto& r : req)
             if (!r.p)
-                return fail(c, SRBD_E_INVALID, std::string("srbd_batch_step_device: null required pointer: ") + r.name);
+                return fail(c, SRBD_E_INVALID, fn + ": null required pointer: " + r.name);
     }
-    if (!b) return fail(nullptr, SRBD_E_INVALID, "srbd_batch_step_device: null batch");
+    if (!b) return fail(nullptr, SRBD_E_INVALID, fn + ": null batch");
     const ModelConst& mc = c->mc;
+    if (!is_cem && mc.method == SRBD_CEM_MPPI)
+        return fail(c, SRBD_E_INVALID, "CEM: sigma is part of the step (srbd_batch_step_cem_device)");
+    if (is_cem && mc.method != SRBD_CEM_MPPI)
+        return fail(c, SRBD_E_INVALID, fn + ": not a CEM batch (srbd_batch_create_cem)");
     if (io->contact_stride < mc.H)
-        return fail(c, SRBD_E_INVALID, "srbd_batch_step_device: contact_stride is smaller than the horizon");
+        return fail(c, SRBD_E_INVALID, fn + ": contact_stride is smaller than the horizon");
     HIP_TRY(c, hipSetDevice(c->cfg.device_id));
     // NULL is the batch's own stream, so the null stream goes by its explicit handle (handed on as the null stream)
     hipStream_t s = (hipStream_t)hip_stream;
@@ -3064,7 +3123,7 @@ extern "C" int srbd_batch_step_device(srbd_batch* b, const srbd_batch_device_io*
     const int E = b->E;
     // the previous device step on another stream still owns the internal buffers
     if (b->dev_pending && b->dev_stream != s) HIP_TRY(c, hipStreamWaitEvent(s, b->dev_done, 0));
-    launch_batch_pack(mc, c->cfg.q_diag + 12, *io, b->d_in, E, s);
+    launch_batch_pack(mc, c->cfg.q_diag + 12, *io, b->d_in, E, s, is_cem ? cem : nullptr);
     if (io->noise)
         launch_batch_transpose(mc, io->noise, b->d_noise, E, s);
     else
@@ -3076,7 +3135,7 @@ extern "C" int srbd_batch_step_device(srbd_batch* b, const srbd_batch_device_io*
     const uint32_t seq = ++c->seq;
     launch_batch_merge(mc, b->d_in, b->d_rec, c->wrec_stride, b->d_noise, b->d_out, b->d_eflag, b->d_count, c->d_flag,
                        seq, E, s);
-    launch_batch_unpack(mc, *io, b->d_out, b->d_costs, E, s);
+    launch_batch_unpack(mc, *io, b->d_out, b->d_costs, E, s, is_cem ? cem->sigma : nullptr);
     const hipError_t le = hipGetLastError();
     // recorded whatever the launches returned: what was enqueued still orders the other entry points
     const hipError_t re = hipEventRecord(b->dev_done, s);
@@ -3086,4 +3145,13 @@ extern "C" int srbd_batch_step_device(srbd_batch* b, const srbd_batch_device_io*
     HIP_TRY(c, re);
     b->stepped = true;
     return SRBD_OK;
+}
+
+extern "C" int srbd_batch_step_device(srbd_batch* b, const srbd_batch_device_io* io, void* hip_stream) {
+    return batch_step_dev(b, io, nullptr, false, hip_stream);
+}
+
+extern "C" int srbd_batch_step_cem_device(srbd_batch* b, const srbd_batch_device_io* io, const srbd_batch_cem_io* cem,
+                                          void* hip_stream) {
+    return batch_step_dev(b, io, cem, true, hip_stream);
 }

@@ -10,13 +10,16 @@
 //   batch_rollout_kernel    rollout_quad_kernel's plain form (MPPI / random sampling) and, with EXT, its form with
 //                           the opt-in cost terms: one 64-sample leaf per 256-thread block, leaf records only (no
 //                           in-launch fold, merge or draws: with E x nleaf blocks in flight the tail those forms
-//                           shorten is amortised)
+//                           shorten is amortised); with CEMT its CEM form (srbd_batch_create_cem): sigma scaling
+//                           and the K smallest keys of every leaf
 //   batch_rollout_ga_kernel rollout_ga_quad_kernel (gait-adaptive sampling), the same block and record layout
 //   batch_merge_kernel      one block per environment: merge_body over its leaf records -> out[e]; the last block to
 //                           finish publishes the step's sequence word
 // The device-resident step (srbd_batch_step_device) replaces the input copy and the host's read of out[e]:
 //   batch_pack_kernel       in[e] from the caller's device arrays, as fill_input (srbd_api.hip) builds it on the host
 //   batch_unpack_kernel     out[e] (device memory on this path) and the costs row -> the caller's device arrays
+// A CEM batch (srbd_batch_step_cem, srbd_batch_step_cem_device) moves sigma with them: batch_copy2_kernel,
+// batch_pack_cem_kernel and batch_unpack_cem_kernel; batch_merge_kernel runs merge_body's unsplit CEM form as it is.
 // The device form of srbd_batch_set_gait (srbd_batch_set_gait_device):
 //   batch_set_gait_kernel   the gait fields of in[e] from the caller's device arrays, as fill_gait (srbd_api.hip)
 //                           writes them on the host, and the injected frequency rows into the batch's array
@@ -34,12 +37,22 @@ __global__ void __launch_bounds__(256) batch_copy_kernel(const uint4* __restrict
     const size_t o = (size_t)blockIdx.x * stride_words;
     for (int i = threadIdx.x; i < nwords; i += 256) dst[o + i] = src[o + i];
 }
+// A CEM batch's copy: a second range of each input (sigma[P]) besides the first, as copy16_kernel has
+__global__ void __launch_bounds__(256) batch_copy2_kernel(const uint4* __restrict__ src, uint4* __restrict__ dst,
+                                                          int nwords, int stride_words, int off2_words,
+                                                          int nwords2) {
+    const size_t o = (size_t)blockIdx.x * stride_words;
+    for (int i = threadIdx.x; i < nwords; i += 256) dst[o + i] = src[o + i];
+    for (int i = threadIdx.x; i < nwords2; i += 256) dst[o + off2_words + i] = src[o + off2_words + i];
+}
 
 // fill_input (srbd_api.hip) on the device, one wave per environment: state | ref, the contact columns (the first H
 // from the caller's stride, the rest of MAXH zero), fzref, cost_feet, the key halves, noise_scaled and best.  Every
 // float operation is the host's, in its order and unfused (the pragma: the host compiles this sum without FMA, and the
 // division is the compiler's correctly rounded one), so in[e] is the host path's bit for bit.  The gait fields and
 // sigma of in[e] are not written.  vec: states, refs and best_params are 16-byte aligned.
+// CEM (batch_pack_cem_kernel, srbd_batch_step_cem_device): sigma of in[e] too -- the caller's row, or the constant
+// sigma_reset when it is positive (the caller's array is then not read).  svec: cem.sigma is 16-byte aligned.
 struct BatchPackConst {
     float q_feet[12];  // srbd_config::q_diag[12..23]
     float mg;
@@ -90,15 +103,85 @@ __global__ void __launch_bounds__(64) batch_pack_kernel(const srbd_batch_device_
         in->noise_scaled = io.noise ? 1 : 0;
     }
 }
+// batch_pack_kernel restated with sigma (a sibling, so that kernel keeps its code and registers)
+__global__ void __launch_bounds__(64) batch_pack_cem_kernel(const srbd_batch_device_io io, const BatchPackConst pc,
+                                                            int vec, StepInput* __restrict__ in_arr,
+                                                            const srbd_batch_cem_io cem, int svec) {
+#pragma clang fp contract(off)
+    const int e = blockIdx.x, tid = threadIdx.x;
+    StepInput* __restrict__ in = in_arr + e;
+    if (cem.sigma_reset > 0.0f) {
+        for (int i = tid; i < pc.P; i += 64) in->sigma[i] = cem.sigma_reset;
+    } else {
+        const float* __restrict__ sp = cem.sigma + (size_t)e * pc.P;
+        if (svec)
+            for (int i = tid; i < pc.P / 4; i += 64)
+                reinterpret_cast<float4*>(in->sigma)[i] = reinterpret_cast<const float4*>(sp)[i];
+        else
+            for (int i = tid; i < pc.P; i += 64) in->sigma[i] = sp[i];
+    }
+    const float* __restrict__ st = io.states + 24 * (size_t)e;
+    const float* __restrict__ rf = io.refs + 24 * (size_t)e;
+    const float* __restrict__ bp = io.best_params + (size_t)e * pc.P;
+    static_assert(offsetof(StepInput, state) == 0 && offsetof(StepInput, ref) == 96, "state | ref head the input");
+    if (vec) {
+        if (tid < 12)
+            reinterpret_cast<float4*>(in)[tid] =
+                tid < 6 ? reinterpret_cast<const float4*>(st)[tid] : reinterpret_cast<const float4*>(rf)[tid - 6];
+        for (int i = tid; i < pc.P / 4; i += 64)
+            reinterpret_cast<float4*>(in->best)[i] = reinterpret_cast<const float4*>(bp)[i];
+    } else {
+        if (tid < 48) reinterpret_cast<float*>(in)[tid] = tid < 24 ? st[tid] : rf[tid - 24];
+        for (int i = tid; i < pc.P; i += 64) in->best[i] = bp[i];
+    }
+    if (tid < MAXH) {  // column n of the four legs
+        const int n = tid;
+        const float* __restrict__ ct = io.contacts + (size_t)e * 4 * io.contact_stride + n;
+        float c[4];
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {
+            c[l] = n < pc.H ? ct[(size_t)l * io.contact_stride] : 0.0f;
+            in->contact[l][n] = c[l];
+        }
+        if (n < pc.H) in->fzref[n] = pc.mg / (((c[0] + c[1]) + c[2]) + c[3]);  // inf when no leg is in stance
+    } else if (tid == MAXH) {
+        float cf = 0.0f;
+#pragma unroll
+        for (int i = 12; i < 24; ++i) {
+            const float d = st[i] - rf[i];
+            cf = cf + (d * pc.q_feet[i - 12]) * d;
+        }
+        in->cost_feet = cf;
+        const uint64_t seed = io.seeds[e], counter = io.counters[e];
+        in->seed_lo = (uint32_t)seed;
+        in->seed_hi = (uint32_t)(seed >> 32);
+        in->ctr_lo = (uint32_t)counter;
+        in->ctr_hi = (uint32_t)(counter >> 32);
+        in->noise_scaled = io.noise ? 1 : 0;
+    }
+}
 
 // out[e] (the merge blocks' records, device memory) and environment e's costs row into the caller's arrays: copies
 // only.  vec: best_params, grf and predicted_state are 16-byte aligned.
-__global__ void __launch_bounds__(256) batch_unpack_kernel(const srbd_batch_device_io io,
-                                                           const StepOutput* __restrict__ out_arr,
-                                                           const float* __restrict__ costs_arr, int P, int N, int ldn,
-                                                           int vec) {
+// CEM (batch_unpack_cem_kernel): out[e].sigma into the caller's sigma row too (threads 192 .. 255; svec: 16-byte
+// aligned).
+template <bool CEM>
+__device__ __forceinline__ void batch_unpack_body(const srbd_batch_device_io& io,
+                                                  const StepOutput* __restrict__ out_arr,
+                                                  const float* __restrict__ costs_arr, int P, int N, int ldn, int vec,
+                                                  float* __restrict__ sigma, int svec) {
     const int e = blockIdx.x, tid = threadIdx.x;
     const StepOutput* __restrict__ o = out_arr + e;
+    if constexpr (CEM) {
+        static_assert(offsetof(StepOutput, sigma) % 16 == 0, "float4 reads");
+        if (tid >= 192) {
+            if (svec)
+                for (int i = tid - 192; i < P / 4; i += 64)
+                    reinterpret_cast<float4*>(sigma + (size_t)e * P)[i] = reinterpret_cast<const float4*>(o->sigma)[i];
+            else
+                for (int i = tid - 192; i < P; i += 64) sigma[(size_t)e * P + i] = o->sigma[i];
+        }
+    }
     static_assert(offsetof(StepOutput, grf) % 16 == 0 && offsetof(StepOutput, pred) % 16 == 0, "float4 reads");
     if (vec) {
         for (int i = tid; i < P / 4; i += 256)
@@ -121,6 +204,19 @@ __global__ void __launch_bounds__(256) batch_unpack_kernel(const srbd_batch_devi
     }
     if (io.costs)
         for (int i = tid; i < N; i += 256) io.costs[(size_t)e * N + i] = costs_arr[(size_t)e * ldn + i];
+}
+__global__ void __launch_bounds__(256) batch_unpack_kernel(const srbd_batch_device_io io,
+                                                           const StepOutput* __restrict__ out_arr,
+                                                           const float* __restrict__ costs_arr, int P, int N, int ldn,
+                                                           int vec) {
+    batch_unpack_body<false>(io, out_arr, costs_arr, P, N, ldn, vec, nullptr, 0);
+}
+__global__ void __launch_bounds__(256) batch_unpack_cem_kernel(const srbd_batch_device_io io,
+                                                               const StepOutput* __restrict__ out_arr,
+                                                               const float* __restrict__ costs_arr, int P, int N,
+                                                               int ldn, int vec, float* __restrict__ sigma,
+                                                               int svec) {
+    batch_unpack_body<true>(io, out_arr, costs_arr, P, N, ldn, vec, sigma, svec);
 }
 
 // fill_gait (srbd_api.hip) on the device, one block per environment: thread 0 forms environment e's candidate set
@@ -174,12 +270,19 @@ __global__ void __launch_bounds__(256) batch_transpose_kernel(const float* __res
 // rollout_quad_kernel<KIND, HT, ST, CEMT = false, EXT = false> (srbd_kernels.hip) with the environment on
 // blockIdx.y: the leg-parallel force phase, the component-parallel rigid-body step, the tracking cost and the leaf
 // record, statement for statement, so the costs and records are that kernel's bits.  Left out: the step input by
-// value, the in-launch draws, folds and merges and CEM's sigma scaling.
+// value and the in-launch draws, folds and merges.
 // EXT (srbd_batch_set_cost_terms): that kernel's EXT form -- the component-parallel force phase with this lane's
 // component of extra_cost_step per leg, each step's terms pinned to their step by an empty asm on the accumulator,
 // no LDS noise stage, and for zero-order a rolling window of four prefetched slots instead of the whole horizon
 // (without the pin and the window the unrolled horizon spills: see rollout_quad_kernel).
-template <int KIND, int HT, int ST, bool EXT = false>
+// CEMT (srbd_batch_create_cem): that kernel's CEMT form -- unscaled device draws multiplied
+// by sigma_j where a parameter is decoded (at use from the LDS copy `sls` in the LDS-staged zero-order form, at
+// load_slot in the other specialised shapes, at the read in the generic one; injected noise, noise_scaled = 1, is used
+// as given), the windowed slot loads of the specialised cubic shape (CWIN), and each leaf's K smallest keys in its
+// record (block_epilogue<true>).  The parameter trails and defaults to false: every statement it adds sits under
+// `if constexpr (CEMT)`, so the MPPI / random-sampling instantiations compile to the code they were (their mangled
+// names gain the argument).
+template <int KIND, int HT, int ST, bool EXT = false, bool CEMT = false>
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) batch_rollout_kernel(
     const ModelConst mc, const StepInput* __restrict__ in_arr, const float* __restrict__ noise_arr,
     float* __restrict__ costs_arr, float* __restrict__ recs_arr, int rec_stride) {
@@ -203,6 +306,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) b
     constexpr int ZSTR = PCT + 1;
     __shared__ __attribute__((aligned(16))) float zst[ZST ? 64 * ZSTR : 1];
     __shared__ float bls[ZST ? PCT : 1];
+    __shared__ float sls[ZST && CEMT ? PCT : 1];  // CEMT: sigma beside best (39.6 KB per block: still four per CU)
     const int tid = threadIdx.x;
     const int q4 = tid & 3;
     const int c = q4 < 3 ? q4 : 2;
@@ -212,6 +316,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) b
     const size_t ldn = (size_t)mc.ldn;
     const float* __restrict__ nz = noise + k;
     const float* __restrict__ best = in->best;
+    const bool zs = CEMT && zs_scaled(mc, in);  // CEMT: CEM kernels only carry the scaling code
 
     // lane constants
     const QuadLane L = quad_lane(mc, c);
@@ -257,8 +362,12 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) b
     const auto nrs = __builtin_amdgcn_make_buffer_rsrc((void*)noise, (short)0, mc.P * mc.ldn * 4, 0x00020000);
     const int voff = (cblk * mc.ldn + k) * 4;
     const float* __restrict__ bl = best + cblk;
-    if constexpr (ZST) {
-        for (int j = tid; j < PCT; j += 256) bls[j] = best[j];
+    const float* __restrict__ sl = in->sigma + cblk;
+    if constexpr (ZST) {  // best (and sigma) -> LDS
+        for (int j = tid; j < PCT; j += 256) {
+            bls[j] = best[j];
+            if constexpr (CEMT) sls[j] = in->sigma[j];
+        }
     }
     auto load_slot = [&](const int i) __attribute__((always_inline)) {
 #pragma unroll
@@ -267,15 +376,26 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) b
                                    : (KIND == SRBD_LINEAR_SPLINE ? l * (ST + 1) + i : 10 * (i >> 2) + 4 * l + (i & 3)))
                                 : l * PL + (KIND == SRBD_CUBIC_SPLINE ? 10 * (i >> 2) + (i & 3) : i);
             const float nzv = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(nrs, voff, jr * mc.ldn * 4, 0));
-            if constexpr (ZST)
+            if constexpr (ZST) {
                 pre[l][i] = nzv;  // raw: best is added at use, the value staged for the epilogue
-            else
+            } else if constexpr (CEMT) {  // unscaled CEM device draws: Z * sigma_j (z * 1 == z; the load unconditional)
+                const float sj = sl[jr];
+                pre[l][i] = bl[jr] + nzv * (zs ? sj : 1.0f);
+            } else {
                 pre[l][i] = bl[jr] + nzv;
+            }
         }
     };
     // EXT zero-order: slot n + PW loads at step n
     constexpr int PW = (EXT && KIND == SRBD_ZERO_ORDER) ? (NPRE < 4 ? NPRE : 4) : NPRE;
-    if constexpr (CT) {
+    // CEM cubic splines with S > 1: chunk q's four slots are loaded CLEAD steps before its first step instead of up
+    // front, as rollout_quad_kernel does (without the window its C3 kernel spills 80 B per lane instead of 16)
+    constexpr int CLEAD = 2;
+    constexpr bool CWIN = CT && CEMT && KIND == SRBD_CUBIC_SPLINE && ST > 1;
+    if constexpr (CWIN) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) load_slot(i);
+    } else if constexpr (CT) {
 #pragma unroll
         for (int i = 0; i < PW; ++i) load_slot(i);
     }
@@ -288,6 +408,15 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) b
     auto step = [&](const int n) __attribute__((always_inline)) {
         if constexpr (CT && PW < NPRE)
             if (n + PW < NPRE) load_slot(n + PW);  // n is a compile-time constant here (unrolled horizon)
+        if constexpr (CWIN) {
+#pragma unroll
+            for (int q = 1; q < (CWIN ? ST : 1); ++q) {
+                const int at = q * HT / ST - CLEAD;
+                if (n == (at > 0 ? at : 0))
+#pragma unroll
+                    for (int i = 4 * q; i < 4 * q + 4; ++i) load_slot(i);
+            }
+        }
         const auto is = step_ptr(in, dep);
         float cl[4] = {0.0f, 0.0f, 0.0f, 0.0f};
         if constexpr (!ZST)
@@ -306,11 +435,13 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) b
             // component q of this leg's decoded force (slot i, parameter j of the leg when not prefetched)
             auto PQ = [&](int q, int i, int j) {
                 if constexpr (ZST) {
+                    if constexpr (CEMT) return bls[lbase + j] + pre[q][i] * (zs ? sls[lbase + j] : 1.0f);
                     return bls[lbase + j] + pre[q][i];
                 } else if constexpr (CT) {
                     return pre[q][i];
                 } else {
                     const float z = nz[(size_t)(lbase + j) * ldn];
+                    if constexpr (CEMT) return best[lbase + j] + (zs ? z * in->sigma[lbase + j] : z);
                     return best[lbase + j] + z;
                 }
             };
@@ -358,6 +489,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) b
                         return pre[l][i];
                     } else {
                         const float z = nz[(size_t)(base + j) * ldn];
+                        if constexpr (CEMT) return best[base + j] + (zs ? z * in->sigma[base + j] : z);
                         return best[base + j] + z;
                     }
                 };
@@ -420,7 +552,18 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) b
     cost = (qp<QP_B0>(cost) + qp<QP_B1>(cost)) + qp<QP_B2>(cost);
     cost = cost + in->cost_feet;  // 0, or NaN when a foot term is non-finite (Q_feet = 0)
     if (isnan(cost) || isinf(cost)) cost = 1000000.0f;
-    if (valid && q4 == 0) costs[k] = cost;
+    // KRE (the zero-order and linear CEM forms at H 16): the sample's index is formed again behind the horizon, tied to
+    // the cost so it is not hoisted.  Kept live across the unrolled horizon it is the value those two forms spill (12 B
+    // of scratch per lane, where rollout_quad_kernel's CEM forms of the shapes have none).  Not elsewhere: no other form
+    // spills it, and the C3 form (cubic H 16) measured 4-6 % slower per step with it.
+    constexpr bool KRE = CEMT && CT && !EXT && HT == 16 && KIND != SRBD_CUBIC_SPLINE;
+    int k_t = k;
+    if constexpr (KRE) {
+        int sib_t = tid >> 2;
+        asm volatile("" : "+v"(sib_t) : "v"(cost));
+        k_t = blockIdx.x * SPB + sib_t;
+    }
+    if (valid && q4 == 0) costs[k_t] = cost;
     if constexpr (ZST) {  // the block's noise, sample-major (leg lq's block of columns lq PL .. lq PL + PL - 1)
 #pragma unroll
         for (int q = 0; q < 3; ++q)
@@ -428,8 +571,8 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) b
             for (int i = 0; i < NPRE; ++i) zst[sib * ZSTR + lq * PL + q * HT + i] = pre[q][i];
     }
     const GroupArgs grp{nullptr, nullptr, 1, nullptr};  // gsize 1: leaf records only
-    block_epilogue<false, ZST>(mc, in, SPB, q4 == 0 ? sib : -1, valid, cost, noise, recs, rec_stride, 0.0f, grp, nroll,
-                               ZST ? zst : nullptr, ZSTR);
+    block_epilogue<CEMT, ZST>(mc, in, SPB, q4 == 0 ? sib : -1, valid, cost, noise, recs, rec_stride, 0.0f, grp, nroll,
+                              ZST ? zst : nullptr, ZSTR);
 }
 
 // rollout_ga_quad_kernel<KIND, HT> (srbd_kernels.hip) with the environment on blockIdx.y (srbd_batch_set_gait): the
@@ -592,28 +735,42 @@ void batch_prepare() {
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)MERGE_LDS_DYN_MAX);
 }
 
-void launch_batch_copy(const StepInput* in_host, StepInput* in, int E, size_t bytes, hipStream_t s) {
-    hipLaunchKernelGGL(batch_copy_kernel, dim3(E), dim3(256), 0, s, (const uint4*)in_host, (uint4*)in,
-                       (int)(bytes / 16), (int)(sizeof(StepInput) / 16));
+void launch_batch_copy(const StepInput* in_host, StepInput* in, int E, size_t bytes, hipStream_t s, size_t off2,
+                       size_t bytes2) {
+    if (bytes2)
+        hipLaunchKernelGGL(batch_copy2_kernel, dim3(E), dim3(256), 0, s, (const uint4*)in_host, (uint4*)in,
+                           (int)(bytes / 16), (int)(sizeof(StepInput) / 16), (int)(off2 / 16), (int)(bytes2 / 16));
+    else
+        hipLaunchKernelGGL(batch_copy_kernel, dim3(E), dim3(256), 0, s, (const uint4*)in_host, (uint4*)in,
+                           (int)(bytes / 16), (int)(sizeof(StepInput) / 16));
 }
 
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 void launch_batch_pack(const ModelConst& mc, const float* q_feet, const srbd_batch_device_io& io, StepInput* in, int E,
-                       hipStream_t s) {
+                       hipStream_t s, const srbd_batch_cem_io* cem) {
     BatchPackConst pc;
     for (int i = 0; i < 12; ++i) pc.q_feet[i] = q_feet[i];
     pc.mg = mc.mg;
     pc.H = mc.H;
     pc.P = mc.P;
     const int vec = aligned16(io.states) && aligned16(io.refs) && aligned16(io.best_params);
-    hipLaunchKernelGGL(batch_pack_kernel, dim3(E), dim3(64), 0, s, io, pc, vec, in);
+    if (cem)
+        hipLaunchKernelGGL(batch_pack_cem_kernel, dim3(E), dim3(64), 0, s, io, pc, vec, in, *cem,
+                           (int)aligned16(cem->sigma));
+    else
+        hipLaunchKernelGGL(batch_pack_kernel, dim3(E), dim3(64), 0, s, io, pc, vec, in);
 }
 
 void launch_batch_unpack(const ModelConst& mc, const srbd_batch_device_io& io, const StepOutput* out,
-                         const float* costs, int E, hipStream_t s) {
+                         const float* costs, int E, hipStream_t s, float* sigma) {
     const int vec = aligned16(io.best_params) && aligned16(io.grf) && aligned16(io.predicted_state);
-    hipLaunchKernelGGL(batch_unpack_kernel, dim3(E), dim3(256), 0, s, io, out, costs, mc.P, mc.n_local, mc.ldn, vec);
+    if (sigma)
+        hipLaunchKernelGGL(batch_unpack_cem_kernel, dim3(E), dim3(256), 0, s, io, out, costs, mc.P, mc.n_local, mc.ldn,
+                           vec, sigma, (int)aligned16(sigma));
+    else
+        hipLaunchKernelGGL(batch_unpack_kernel, dim3(E), dim3(256), 0, s, io, out, costs, mc.P, mc.n_local, mc.ldn,
+                           vec);
 }
 
 void launch_batch_set_gait(const BatchGaitJob& j, StepInput* in, float* ga_freq, int E, hipStream_t s) {
@@ -636,10 +793,18 @@ void launch_batch_rollout(const ModelConst& mc, const StepInput* in, const float
                           int rec_stride, int E, hipStream_t s) {
     const dim3 grid(mc.nleaf, E);
     const int H = mc.H, S = mc.S;
-    // mc.cost_on (srbd_batch_set_cost_terms): the EXT instantiations, on the same compile-time shapes
+    // mc.cost_on (srbd_batch_set_cost_terms): the EXT instantiations, on the same compile-time shapes; CEM
+    // (srbd_batch_create_cem): the CEMT ones, with or without EXT, as launch_rollout_t picks them
+    const bool cem = mc.method == SRBD_CEM_MPPI;
 #define SRBD_BR(K, HH, SS)                                                                                        \
     {                                                                                                             \
-        if (mc.cost_on)                                                                                           \
+        if (cem && mc.cost_on)                                                                                    \
+            hipLaunchKernelGGL((batch_rollout_kernel<K, HH, SS, true, true>), grid, dim3(256), 0, s, mc, in,      \
+                               noise, costs, recs, rec_stride);                                                   \
+        else if (cem)                                                                                             \
+            hipLaunchKernelGGL((batch_rollout_kernel<K, HH, SS, false, true>), grid, dim3(256), 0, s, mc, in,     \
+                               noise, costs, recs, rec_stride);                                                   \
+        else if (mc.cost_on)                                                                                      \
             hipLaunchKernelGGL((batch_rollout_kernel<K, HH, SS, true>), grid, dim3(256), 0, s, mc, in, noise,     \
                                costs, recs, rec_stride);                                                          \
         else                                                                                                      \

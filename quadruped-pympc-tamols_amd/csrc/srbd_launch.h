@@ -161,20 +161,24 @@ void launch_arm_copy(const uint32_t* go, uint32_t seq, uint64_t deadline_ticks, 
 void launch_div_selftest(const float* a, const float* b, int n, float* o, hipStream_t s);
 void launch_log1p_selftest(const float* t, int n, float* o, hipStream_t s);
 
-// Batched environments (srbd_batch.hip): E independent problems of one ModelConst (world 1, MPPI / random sampling)
-// per launch, environment e on blockIdx.y.  Device arrays: in[E]; noise E x P x ldn (SoA per environment); costs
+// Batched environments (srbd_batch.hip): E independent problems of one ModelConst (world 1; CEM through
+// srbd_batch_create_cem) per launch, environment e on blockIdx.y.  Device arrays: in[E]; noise E x P x ldn (SoA per environment); costs
 // E x ldn; recs E x nleaf leaf records; out[E] and `flag` host-mapped.  Every launch count is independent of E.
 constexpr int BATCH_MAX_ENVS = 4096;
 constexpr int BATCH_MAX_SAMPLES = 16384;  // 256 leaves: what one merge block folds unsplit (MERGE_SPLIT_MIN_RECS)
 void batch_prepare();  // once per batch context: the staged merge's dynamic LDS limit
-// in_host[e] -> in[e], the first `bytes` (a multiple of 16) of every StepInput; one block per environment
-void launch_batch_copy(const StepInput* in_host, StepInput* in, int E, size_t bytes, hipStream_t s);
+// in_host[e] -> in[e], the first `bytes` (a multiple of 16) of every StepInput, and with bytes2 != 0 (CEM: sigma)
+// the bytes2 at offset off2 (multiples of 16 both); one block per environment
+void launch_batch_copy(const StepInput* in_host, StepInput* in, int E, size_t bytes, hipStream_t s, size_t off2 = 0,
+                       size_t bytes2 = 0);
 // the device-resident step: in[e] from the caller's device arrays as fill_input builds it (q_feet: q_diag[12..23];
-// the gait fields and sigma are left alone), and out[e] (device memory) with the costs rows into the caller's arrays
+// the gait fields and sigma are left alone), and out[e] (device memory) with the costs rows into the caller's arrays.
+// cem / sigma != NULL (srbd_batch_step_cem_device): in[e].sigma from cem->sigma or the constant cem->sigma_reset, and
+// out[e].sigma into the caller's sigma rows, in the same launches
 void launch_batch_pack(const ModelConst& mc, const float* q_feet, const srbd_batch_device_io& io, StepInput* in, int E,
-                       hipStream_t s);
+                       hipStream_t s, const srbd_batch_cem_io* cem = nullptr);
 void launch_batch_unpack(const ModelConst& mc, const srbd_batch_device_io& io, const StepOutput* out,
-                         const float* costs, int E, hipStream_t s);
+                         const float* costs, int E, hipStream_t s, float* sigma = nullptr);
 // srbd_batch_set_gait_device: the caller's io by value, the chunk boundaries ga_chunk_bounds formed on the host and the
 // shapes; in[e]'s gait fields, and with io.freq_rows environment e's N rows into ga_freq at stride ldn
 struct BatchGaitJob {

@@ -93,6 +93,11 @@ class BatchDeviceIO(C.Structure):
     ]
 
 
+class BatchCemIO(C.Structure):
+    """srbd_batch_cem_io (include/srbd_mpc.h): sigma of one srbd_batch_step_cem_device call."""
+    _fields_ = [("sigma", _P), ("sigma_reset", _F), ("pad", _I)]
+
+
 MAX_FREQS = 8  # SRBD_MAX_FREQS
 
 
@@ -344,6 +349,9 @@ SIGNATURES.update({
     "srbd_batch_clear_gait": (_I, [_P]),
     "srbd_batch_set_cost_terms": (_I, [_P, _FP, _F, _F]),
     "srbd_batch_step_device": (_I, [_P, C.POINTER(BatchDeviceIO), _P]),
+    "srbd_batch_create_cem": (_I, [C.POINTER(SrbdConfig), _I, C.POINTER(_P)]),
+    "srbd_batch_step_cem": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "srbd_batch_step_cem_device": (_I, [_P, C.POINTER(BatchDeviceIO), C.POINTER(BatchCemIO), _P]),
     # the device producers: device arrays as plain addresses, dts / lens host arrays
     "srbd_pgg_run_device": (_I, [_P, _I, _D, _P, _P, _P]),
     "srbd_pgg_contact_sequence_device": (_I, [_P, _I, _I, _DP, _IP, _I, _P, _I, _P]),
@@ -836,7 +844,10 @@ class Context:
 class BatchContext:
     """Owns one ``srbd_batch``: ``num_envs`` independent problems of one configuration stepped by one call
     (``srbd_batch_step``, include/srbd_mpc.h).  Environment ``e`` of a step returns what ``Context(cfg).step`` returns
-    for the same inputs, bit for bit.  Inputs are copied into persistent staging arrays, as ``Context`` does."""
+    for the same inputs, bit for bit.  Inputs are copied into persistent staging arrays, as ``Context`` does.
+    CEM-MPPI configurations go through ``CemBatchContext``."""
+
+    _create = "srbd_batch_create"  # the C creator (looked up per call)
 
     def __init__(self, cfg: SrbdConfig, num_envs: int):
         self.cfg = cfg
@@ -844,10 +855,10 @@ class BatchContext:
         self.N = cfg.num_samples
         self.E = int(num_envs)
         h = _P()
-        rc = lib.srbd_batch_create(C.byref(cfg), self.E, C.byref(h))
+        rc = getattr(lib, self._create)(C.byref(cfg), self.E, C.byref(h))
         if rc != OK:
             msg = lib.srbd_batch_last_error(None)
-            raise RuntimeError(f"srbd_batch_create failed ({rc}): {msg.decode() if msg else ''}")
+            raise RuntimeError(f"{self._create} failed ({rc}): {msg.decode() if msg else ''}")
         self.h = h
         E, H = self.E, cfg.horizon
         self._states = np.zeros((E, 24), np.float32)
@@ -1037,10 +1048,19 @@ class BatchContext:
         (E,) int32, and costs (E, N) with ``want_costs``.  The values are what ``step`` returns for the same inputs,
         bit for bit; they are ready in stream order (consume them on ``stream``, or synchronise it).  The inputs are
         read in stream order too: tensors produced on another stream need the usual event / ``record_stream`` care."""
+        dev = self.check_step_device(states, refs, contacts, best, seeds, counters, noise)
+
+        def enqueue(io, handle):
+            self.check(lib.srbd_batch_step_device(self.h, C.byref(io), handle), "srbd_batch_step_device")
+
+        return self._step_device(dev, enqueue, states, refs, contacts, best, seeds, counters, noise, want_costs, stream)
+
+    def _step_device(self, dev, enqueue, states, refs, contacts, best, seeds, counters, noise, want_costs, stream):
+        """The output tensors and the io struct of a device step (the arguments already checked); ``enqueue(io,
+        stream handle)`` makes the library call."""
         import torch
 
         E, N = self.E, self.N
-        dev = self.check_step_device(states, refs, contacts, best, seeds, counters, noise)
         s = torch.cuda.current_stream(dev) if stream is None else stream
         with torch.cuda.stream(s):  # the outputs belong to the stream that writes them
             out = {"grf": torch.empty((E, 12), dtype=torch.float32, device=dev),
@@ -1061,9 +1081,87 @@ class BatchContext:
                            costs=out["costs"].data_ptr() if want_costs else None)
         # torch's default stream is the null stream, handle 0, which the C call reads as "the batch's own stream":
         # hand it on by its explicit handle (hipStreamLegacy)
-        self.check(lib.srbd_batch_step_device(self.h, C.byref(io), C.c_void_p(s.cuda_stream or 1)),
-                   "srbd_batch_step_device")
+        enqueue(io, C.c_void_p(s.cuda_stream or 1))
         return out
+
+
+class CemBatchContext(BatchContext):
+    """A CEM-MPPI ``srbd_batch`` (``srbd_batch_create_cem``, include/srbd_mpc.h): ``BatchContext`` with sigma, (E, P),
+    travelling in and out of every step.  Environment ``e`` returns what ``Context(cfg).step(..., sigma=sigma[e])``
+    returns, the new sigma included, bit for bit.  The plain ``step`` / ``step_device`` are refused by the library."""
+
+    _create = "srbd_batch_create_cem"
+
+    def __init__(self, cfg: SrbdConfig, num_envs: int):
+        super().__init__(cfg, num_envs)
+        self._sigma = np.zeros((self.E, self.P), np.float32)
+
+    def step_cem(self, states, refs, contacts, best, sigma, noise=None, seeds=None, counters=None, want_costs=False):
+        """``BatchContext.step`` with sigma (E, P), or a scalar / (P,) broadcast to it -> (best (E, P), sigma (E, P),
+        list of E SrbdResult, costs (E, N) or None).  Injected noise is used as given; device draws are scaled by
+        sigma where they are read."""
+        E, H = self.E, self.cfg.horizon
+        self._states[...] = np.reshape(states, (E, 24))
+        self._refs[...] = np.reshape(refs, (E, 24))
+        contacts = np.asarray(contacts)
+        if contacts.ndim != 3 or contacts.shape[:2] != (E, 4) or contacts.shape[2] < H:
+            raise ValueError("contact sequences must be (E, 4, >=H)")
+        self._contacts[...] = contacts[:, :, :H]
+        self._best[...] = np.reshape(best, (E, self.P))
+        self._sigma[...] = np.broadcast_to(np.asarray(sigma, dtype=np.float32), (E, self.P))
+        self._seeds[...] = 42 if seeds is None else np.asarray(seeds, np.uint64).reshape(E)
+        self._counters[...] = 0 if counters is None else np.asarray(counters, np.uint64).reshape(E)
+        a_noise = None
+        if noise is not None:
+            noise = np.ascontiguousarray(noise, dtype=np.float32)
+            if noise.shape != (E, self.N, self.P):
+                raise ValueError(f"noise must be ({E}, {self.N}, {self.P})")
+            a_noise = noise.ctypes.data
+        costs = np.empty((E, self.N), np.float32) if want_costs else None
+        a = self._addr
+        rc = lib.srbd_batch_step_cem(self.h, a[0], a[1], a[2], H, a[3], self._sigma.ctypes.data, a_noise, a[4], a[5],
+                                     C.addressof(self._results), None if costs is None else costs.ctypes.data)
+        self.check(rc, "srbd_batch_step_cem")
+        results = [SrbdResult.from_buffer_copy(r) for r in self._results]
+        return self._best.copy(), self._sigma.copy(), results, costs
+
+    def check_step_cem_device(self, states, refs, contacts, best, sigma, seeds, counters, noise=None,
+                              sigma_reset: float = 0.0):
+        """The argument checks of ``step_cem_device`` (ValueError; nothing is enqueued): sigma -- a float32 torch
+        tensor of shape (E, P), contiguous as a view (its rows packed; it may start anywhere in its storage) -- and
+        sigma_reset finite and >= 0, then ``check_step_device``, then sigma's device.  Returns the context's device."""
+        import torch
+
+        if not isinstance(sigma, torch.Tensor):
+            raise ValueError(f"sigma must be a torch tensor, got {type(sigma).__name__}")
+        if sigma.dtype != torch.float32:
+            raise ValueError(f"sigma must be torch.float32, got {sigma.dtype}")
+        if tuple(sigma.shape) != (self.E, self.P):
+            raise ValueError(f"sigma must be {(self.E, self.P)}, got {tuple(sigma.shape)}")
+        if not sigma.is_contiguous():
+            raise ValueError("sigma must be contiguous")
+        r = float(sigma_reset)
+        if not (r >= 0.0 and r != float("inf")):
+            raise ValueError(f"sigma_reset must be finite and >= 0, got {sigma_reset}")
+        dev = self.check_step_device(states, refs, contacts, best, seeds, counters, noise)
+        if sigma.device != dev:
+            raise ValueError(f"sigma must be on {dev}, got {sigma.device}")
+        return dev
+
+    def step_cem_device(self, states, refs, contacts, best, sigma, seeds, counters, *, sigma_reset: float = 0.0,
+                        noise=None, want_costs=False, stream=None):
+        """srbd_batch_step_cem_device: ``BatchContext.step_device`` with sigma, an (E, P) float32 tensor updated in
+        place.  sigma_reset > 0: every environment starts this step from that constant and sigma is only written (the
+        reference's ``with_newsigma(sigma_cem_mppi)`` at the first sampling iteration); 0: sigma is read.  The values
+        are what ``step_cem`` returns for the same inputs, bit for bit."""
+        dev = self.check_step_cem_device(states, refs, contacts, best, sigma, seeds, counters, noise, sigma_reset)
+        cem = BatchCemIO(sigma=sigma.data_ptr(), sigma_reset=float(sigma_reset), pad=0)
+
+        def enqueue(io, handle):
+            self.check(lib.srbd_batch_step_cem_device(self.h, C.byref(io), C.byref(cem), handle),
+                       "srbd_batch_step_cem_device")
+
+        return self._step_device(dev, enqueue, states, refs, contacts, best, seeds, counters, noise, want_costs, stream)
 
 
 # ---------------------------------------------------------------------- device producers (include/srbd_mpc.h)

@@ -5,8 +5,8 @@ each.  ``Batched_Sampling_MPC`` is the one-process form: one configuration (the 
 reads), and per environment a state, reference, contact sequence, warm start and noise key.  Environment ``e`` of a
 ``compute_control`` call returns what a ``Sampling_MPC`` with the same key returns, bit for bit.
 
-MPPI and random sampling; ``sampling_method == 'cem_mppi'`` has no batch form (its draws depend on the sigma each
-step produces) and raises ``NotImplementedError``.
+MPPI and random sampling; ``sampling_method == 'cem_mppi'`` raises ``NotImplementedError`` here: sigma is part of
+every CEM step, so it has a class of its own, ``Batched_CEM_Sampling_MPC`` (centroidal_nmpc_hip_cem_batched).
 """
 from __future__ import annotations
 
@@ -43,11 +43,15 @@ class LazyBatchCosts:
 class Batched_Sampling_MPC:
     """``num_envs`` sampling controllers of one configuration behind one device context."""
 
+    # False: 'cem_mppi' is refused (sigma is part of every CEM step: Batched_CEM_Sampling_MPC sets it)
+    _accepts_cem = False
+    _context_class = _lib.BatchContext
+
     def __init__(self, num_envs: int, config_module=None):
         cfg = active_config(config_module)
-        if cfg.mpc_params["sampling_method"] == "cem_mppi":
-            raise NotImplementedError("Batched_Sampling_MPC: 'cem_mppi' has no batch form (its draws depend on the "
-                                      "sigma each step produces); use one Sampling_MPC per environment")
+        if cfg.mpc_params["sampling_method"] == "cem_mppi" and not self._accepts_cem:
+            raise NotImplementedError("Batched_Sampling_MPC: 'cem_mppi' carries sigma through every step; use "
+                                      "Batched_CEM_Sampling_MPC (centroidal_nmpc_hip_cem_batched)")
         self.num_envs = int(num_envs)
         if self.num_envs < 1:
             raise ValueError("num_envs must be >= 1")
@@ -76,7 +80,7 @@ class Batched_Sampling_MPC:
     @property
     def context(self) -> "_lib.BatchContext":
         if self._ctx is None:
-            self._ctx = _lib.BatchContext(self._one._srbd_config(), self.num_envs)
+            self._ctx = self._context_class(self._one._srbd_config(), self.num_envs)
             if self.rng != "philox":
                 self._ctx.set_rng(self.rng)
         return self._ctx
