@@ -474,8 +474,10 @@ int srbd_interface_step(srbd_ctx* ctx, srbd_interface_io* io, const float* conta
  * one host wait on one published word.  The device-resident step (srbd_batch_step_device below) takes and returns
  * device arrays on the caller's stream: five launches (pack, draws or transpose, rollouts, merges, unpack) and no
  * host wait.
- *   Shared: the srbd_config -- robot, N (num_samples is per environment), H, method, parametrization, S, dts, Q,
- *   bounds.  Per environment: everything per step -- state, reference, contact sequence, warm start, noise key.
+ *   Shared: the srbd_config -- N (num_samples is per environment), H, method, parametrization, S, dts, sigmas, elite
+ *   count.  Per environment: everything per step -- state, reference, contact sequence, warm start, noise key; and,
+ *   opt-in (srbd_batch_set_env_params below), the robot, Q and the bounds: mass, mg, inertia, grf_min, grf_max, mu and
+ *   q_diag.  Until they are set, every environment has the srbd_config's.
  *   Equivalence: environment e returns exactly what srbd_step returns on a context srbd_create(cfg) (world_size 1)
  *   for the same inputs, (seeds[e], counters[e]) and noise stream -- every output bit for bit (one fixed reduction
  *   tree, keyed by the environment's own rows 0..N-1).  Device draws of environment e are srbd_draw_noise(seeds[e],
@@ -618,6 +620,51 @@ int srbd_batch_step_cem(srbd_batch* b, const float* states, const float* refs, c
                         const uint64_t* seeds, const uint64_t* counters, srbd_result* out, float* out_costs);
 int srbd_batch_step_cem_device(srbd_batch* b, const srbd_batch_device_io* io, const srbd_batch_cem_io* cem,
                                void* hip_stream);
+
+/* Per-environment robot and cost parameters: the seven srbd_config fields of the same names, one record per
+ * environment (payload, friction, inertia, force-limit and cost-weight sweeps inside one batch).
+ *   A setting holds for every following step until changed or cleared, and applies to every step entry point:
+ *   srbd_batch_step, _step_device, _step_cem, _step_cem_device, and those steps after srbd_batch_set_gait[_device] or
+ *   srbd_batch_set_cost_terms.  Everything else in the srbd_config stays shared (N, H, method, parametrization, S,
+ *   dts, sigmas, elite count).  Before the first set, and after srbd_batch_clear_env_params, the batch behaves and
+ *   launches exactly as a batch without parameters: the same kernels with the same arguments.
+ *   Equivalence: environment e returns exactly what srbd_step returns on srbd_create(cfg_e), cfg_e being the batch's
+ *   srbd_config with mass, mg, grf_min, grf_max, mu, inertia and q_diag replaced by params[e], for the same inputs,
+ *   keys, noise stream and srbd_set_gait / srbd_set_cost_terms / sigma -- every output bit for bit: costs,
+ *   best_params, the new sigma, GRFs, predicted state, best_cost, best_index, best_freq, status.  The values derived
+ *   from a record (1 / mass, -mu, the inverse inertia, mg / n_stance) are formed by the one function srbd_create's
+ *   model uses, on the host and on the device.
+ *   srbd_batch_set_env_params: params, E records in host memory; mask NULL, or E bytes: environments with mask[e] == 0
+ *   keep their parameters and their records are not read.  Every selected record is checked as srbd_create checks its
+ *   configuration (0 <= grf_min <= grf_max, mu >= 0): at the first that fails the call returns SRBD_E_INVALID, names
+ *   that environment in srbd_batch_last_error and changes nothing.  Synchronises as srbd_batch_set_cost_terms does.
+ *   srbd_batch_set_env_params_device: the same from device memory of the batch's device, one launch on the caller's
+ *   stream (hip_stream as srbd_batch_step_device reads it), no host wait and no host access to device memory; it
+ *   joins the device steps' event protocol as srbd_batch_set_gait_device does.  d_mask NULL, or E int32 words (the
+ *   mask of srbd_loop_reset_device: an episode reset re-draws its robots with it); a masked-out record is neither
+ *   read nor written.  The call cannot return a per-environment error: a selected environment whose record fails the
+ *   checks keeps its previous parameters and gets d_rejected[e] = 1; every other environment gets 0, masked-out ones
+ *   included (d_rejected NULL: not reported).  After this call every step runs the per-environment kernels until
+ *   srbd_batch_clear_env_params.
+ *   srbd_batch_get_env_params: synchronises on the batch's event and returns every environment's seven fields as set,
+ *   or the srbd_config's where never set.
+ *   srbd_batch_clear_env_params: every environment back to the srbd_config's values; synchronises.
+ *   SRBD_E_INVALID (with a message, before anything is enqueued): b, params, d_params or out NULL; d_params, d_mask
+ *   or d_rejected not 4-byte aligned.  A failed allocation of the record array: SRBD_E_NOMEM.
+ *   Refusal rule: a step never runs an environment that was given parameters on the shared values; a form without
+ *   per-environment kernels would return SRBD_E_INVALID with a message instead (there is none: every batch step form
+ *   has them). */
+typedef struct srbd_env_params { /* 39 floats, no padding; the srbd_config fields of the same names */
+    float mass, mg, grf_min, grf_max, mu;
+    float inertia[9];
+    float q_diag[24];
+    float reserved; /* the 39th float: not read by the setters' checks or the model; returned as given (0 by default) */
+} srbd_env_params;
+int srbd_batch_set_env_params(srbd_batch* b, const srbd_env_params* params, const uint8_t* mask);
+int srbd_batch_set_env_params_device(srbd_batch* b, const srbd_env_params* d_params, const int32_t* d_mask,
+                                     int32_t* d_rejected, void* hip_stream);
+int srbd_batch_get_env_params(srbd_batch* b, srbd_env_params* out);
+int srbd_batch_clear_env_params(srbd_batch* b);
 
 /* The producers of the device-resident step on the device: the periodic gait generator and
  * prepare_state_and_reference (srbd_host.h: srbd_pgg_run, srbd_pgg_contact_sequence, srbd_prepare_state) for

@@ -242,6 +242,20 @@ static void spline_coef(const srbd_config* c, float step, int horizon_leg, int* 
     *d = (qq * qq * qq - qq * qq) * 1.0f;
 }
 
+// The robot and cost fields of a configuration as one srbd_env_params record
+static srbd_env_params env_params_of(const srbd_config* cfg) {
+    srbd_env_params p;
+    p.mass = cfg->mass;
+    p.mg = cfg->mg;
+    p.grf_min = cfg->grf_min;
+    p.grf_max = cfg->grf_max;
+    p.mu = cfg->mu;
+    memcpy(p.inertia, cfg->inertia, sizeof(p.inertia));
+    memcpy(p.q_diag, cfg->q_diag, sizeof(p.q_diag));
+    p.reserved = 0.0f;
+    return p;
+}
+
 static int build_model(const srbd_config* cfg, ModelConst* mc, std::string* why) {
     const int P = srbd_num_params(cfg);
     if (P < 0) {
@@ -296,19 +310,22 @@ static int build_model(const srbd_config* cfg, ModelConst* mc, std::string* why)
     mc->t_world = world;
     mc->leaf0 = mc->row0 / LEAF_ROWS;
     mc->nleaf = (mc->n_local + LEAF_ROWS - 1) / LEAF_ROWS;
-    mc->inv_m = 1.0f / cfg->mass;
-    mc->mg = cfg->mg;
-    if (!(cfg->grf_min >= 0.0f && cfg->grf_max >= cfg->grf_min && cfg->mu >= 0.0f)) {
+    const srbd_env_params ep = env_params_of(cfg);
+    if (!env_params_ok(ep)) {
         *why = "need 0 <= grf_min <= grf_max and mu >= 0";
         return SRBD_E_INVALID;
     }
-    mc->grf_min = cfg->grf_min;
-    mc->grf_max = cfg->grf_max;
-    mc->mu = cfg->mu;
-    mc->neg_mu = -cfg->mu;
-    memcpy(mc->inertia, cfg->inertia, sizeof(mc->inertia));
-    inv3(cfg->inertia, mc->Iinv);
-    for (int i = 0; i < 12; ++i) mc->Q[i] = cfg->q_diag[i];
+    EnvModel em;
+    env_model_fill(ep, &em);  // the robot's derived constants, as a batch's per-environment records form them
+    mc->inv_m = em.inv_m;
+    mc->mg = em.mg;
+    mc->grf_min = em.grf_min;
+    mc->grf_max = em.grf_max;
+    mc->mu = em.mu;
+    mc->neg_mu = em.neg_mu;
+    memcpy(mc->inertia, em.inertia, sizeof(mc->inertia));
+    memcpy(mc->Iinv, em.Iinv, sizeof(mc->Iinv));
+    memcpy(mc->Q, em.Q, sizeof(mc->Q));
     for (int n = 0; n < MAXH; ++n) mc->dts[n] = n < cfg->horizon ? cfg->dts[n] : 0.0f;
     for (int n = 0; n < cfg->horizon; ++n)
         spline_coef(cfg, (float)n, cfg->horizon, &mc->sidx[n], &mc->sq[n], &mc->somq[n], &mc->sa[n], &mc->sb[n],
@@ -318,7 +335,7 @@ static int build_model(const srbd_config* cfg, ModelConst* mc, std::string* why)
     for (int i = 0; i < 3; ++i) mc->sigma_rs[i] = cfg->sigma_random_sampling[i];
     mc->ga = 0;
     mc->ga_freq = nullptr;
-    for (int i = 0; i < 5; ++i) mc->fz_ns[i] = mc->mg / (float)i;  // the division fill_input makes per step
+    memcpy(mc->fz_ns, em.fz_ns, sizeof(mc->fz_ns));
     // the parameter columns final_grf_pred's decode reads (the column-split merge's tail block)
     mc->ntail = 0;
     for (int leg = 0; leg < 4; ++leg) {
@@ -338,11 +355,14 @@ static int build_model(const srbd_config* cfg, ModelConst* mc, std::string* why)
 }
 
 // Host part of the per-step input (StepInput) -- identical on every rank.
+// em: the environment's record in a batch with per-environment parameters (its mg and feet weights); else NULL
 static int fill_input(const srbd_config* cfg, const ModelConst& mc, StepInput* in, const float* state,
                       const float* ref, const float* contact, int stride, const float* best, const float* sigma,
-                      uint64_t seed, uint64_t counter) {
+                      uint64_t seed, uint64_t counter, const EnvModel* em = nullptr) {
     if (!state || !ref || !contact || !best || stride < mc.H) return SRBD_E_INVALID;
     if (mc.method == SRBD_CEM_MPPI && !sigma) return SRBD_E_INVALID;
+    const float mg = em ? em->mg : mc.mg;
+    const float* q_feet = em ? em->q_feet : cfg->q_diag + 12;
     memcpy(in->state, state, sizeof(in->state));
     memcpy(in->ref, ref, sizeof(in->ref));
     memset(in->contact, 0, sizeof(in->contact));
@@ -350,12 +370,12 @@ static int fill_input(const srbd_config* cfg, const ModelConst& mc, StepInput* i
         for (int n = 0; n < mc.H; ++n) in->contact[l][n] = contact[(size_t)l * stride + n];
     for (int n = 0; n < mc.H; ++n) {
         const float ns = in->contact[0][n] + in->contact[1][n] + in->contact[2][n] + in->contact[3][n];
-        in->fzref[n] = mc.mg / ns;  // inf when no leg is in stance: neutralised by the clip (App. A.3)
+        in->fzref[n] = mg / ns;  // inf when no leg is in stance: neutralised by the clip (App. A.3)
     }
     float cf = 0.0f;
     for (int i = 12; i < 24; ++i) {
         const float e = state[i] - ref[i];
-        cf = cf + (e * cfg->q_diag[i]) * e;
+        cf = cf + (e * q_feet[i - 12]) * e;
     }
     in->cost_feet = cf;
     in->seed_lo = (uint32_t)seed;
@@ -2667,6 +2687,17 @@ struct srbd_batch {
     // srbd_batch_set_gait_device wrote d_in's gait fields past the staging: the host step, which copies the staging
     // over them, is refused until srbd_batch_set_gait or srbd_batch_clear_gait
     bool ga_staging_stale = false;
+    // per-environment robot and cost parameters (srbd_batch_set_env_params): the fields as set and the records derived
+    // from them, on the device (what the ENVT kernels and the getter read) and mirrored on the host (what the host
+    // step's fill_input and the host setter read).  Both hold the configuration's values until a setter changes them.
+    // env_on: the steps run the ENVT kernels; env_host_stale: the device setter wrote past the mirrors, the next host
+    // call that needs them downloads them.
+    srbd_env_params* d_env_raw = nullptr;  // E
+    EnvModel* d_env = nullptr;             // E
+    std::vector<srbd_env_params> h_env_raw;
+    std::vector<EnvModel> h_env;
+    bool env_on = false;
+    bool env_host_stale = false;
 };
 
 // The internal buffers (d_in, d_noise, d_rec, d_costs, d_count, d_ga_freq) are shared by the host path and the device
@@ -2675,6 +2706,32 @@ static hipError_t batch_join_host(srbd_batch* b) {
     if (!b->dev_pending) return hipSuccess;
     const hipError_t e = hipEventSynchronize(b->dev_done);
     if (e == hipSuccess) b->dev_pending = false;
+    return e;
+}
+
+// Every environment's parameters back to the configuration's, mirrors and device arrays (the stream is idle)
+static hipError_t batch_env_reset(srbd_batch* b) {
+    const srbd_env_params p = env_params_of(&b->c.cfg);
+    EnvModel m;
+    env_model_fill(p, &m);
+    b->h_env_raw.assign((size_t)b->E, p);
+    b->h_env.assign((size_t)b->E, m);
+    b->env_on = false;
+    b->env_host_stale = false;
+    hipError_t e = hipMemcpy(b->d_env_raw, b->h_env_raw.data(), sizeof(srbd_env_params) * (size_t)b->E,
+                             hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = hipMemcpy(b->d_env, b->h_env.data(), sizeof(EnvModel) * (size_t)b->E, hipMemcpyHostToDevice);
+    return e;
+}
+// The mirrors after srbd_batch_set_env_params_device (no device work of the batch is in flight)
+static hipError_t batch_env_download(srbd_batch* b) {
+    if (!b->env_host_stale) return hipSuccess;
+    hipError_t e = hipMemcpy(b->h_env_raw.data(), b->d_env_raw, sizeof(srbd_env_params) * (size_t)b->E,
+                             hipMemcpyDeviceToHost);
+    if (e == hipSuccess)
+        e = hipMemcpy(b->h_env.data(), b->d_env, sizeof(EnvModel) * (size_t)b->E, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) b->env_host_stale = false;
     return e;
 }
 
@@ -2693,6 +2750,8 @@ extern "C" void srbd_batch_destroy(srbd_batch* b) {
     (void)hipFree(b->d_count);
     (void)hipFree(b->d_noise_rm);
     (void)hipFree(b->d_ga_freq);
+    (void)hipFree(b->d_env_raw);
+    (void)hipFree(b->d_env);
     if (b->h_in) (void)hipHostFree(b->h_in);
     if (b->h_out) (void)hipHostFree(b->h_out);
     if (b->c.h_flag) (void)hipHostFree(b->c.h_flag);
@@ -2785,6 +2844,10 @@ static int batch_create(const srbd_config* cfg, int32_t num_envs, srbd_batch** o
     if ((e = hipMalloc((void**)&b->d_out, sizeof(StepOutput) * E)) != hipSuccess) return cleanup_fail("hipMalloc", e);
     if ((e = hipEventCreateWithFlags(&b->dev_done, hipEventDisableTiming)) != hipSuccess)
         return cleanup_fail("hipEventCreate", e);
+    if ((e = hipMalloc((void**)&b->d_env_raw, sizeof(srbd_env_params) * E)) != hipSuccess)
+        return cleanup_fail("hipMalloc", e);
+    if ((e = hipMalloc((void**)&b->d_env, sizeof(EnvModel) * E)) != hipSuccess) return cleanup_fail("hipMalloc", e);
+    if ((e = batch_env_reset(b)) != hipSuccess) return cleanup_fail("hipMemcpy", e);
     // the noise padding rows (n_local .. ldn) stay zero, as in a single context
     if ((e = hipMemsetAsync(b->d_noise, 0, noise_bytes, b->c.stream)) != hipSuccess ||
         (e = hipMemsetAsync(b->d_in, 0, sizeof(StepInput) * E, b->c.stream)) != hipSuccess ||
@@ -2963,6 +3026,87 @@ extern "C" int srbd_batch_set_cost_terms(srbd_batch* b, const float* r_force, fl
     return SRBD_OK;
 }
 
+// Per-environment robot and cost parameters.  The records live in device memory (d_env, read by the ENVT kernels of
+// srbd_batch.hip through launch_batch_*'s envs argument) and in host mirrors; the launches take envs only while
+// env_on, so a batch that never set parameters, or cleared them, launches the kernels it always did.
+extern "C" int srbd_batch_set_env_params(srbd_batch* b, const srbd_env_params* params, const uint8_t* mask) {
+    if (!b) return fail(nullptr, SRBD_E_INVALID, "srbd_batch_set_env_params: null batch");
+    srbd_ctx* c = &b->c;
+    if (!params) return fail(c, SRBD_E_INVALID, "srbd_batch_set_env_params: null params");
+    const int E = b->E;
+    for (int e = 0; e < E; ++e)  // before anything changes
+        if ((!mask || mask[e]) && !env_params_ok(params[e]))
+            return fail(c, SRBD_E_INVALID,
+                        "srbd_batch_set_env_params: environment " + std::to_string(e) +
+                            ": need 0 <= grf_min <= grf_max and mu >= 0 (nothing was changed)");
+    HIP_TRY(c, hipSetDevice(c->cfg.device_id));
+    HIP_TRY(c, batch_join_host(b));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // no step in flight reads the records
+    HIP_TRY(c, batch_env_download(b));
+    for (int e = 0; e < E; ++e)
+        if (!mask || mask[e]) {
+            b->h_env_raw[e] = params[e];
+            env_model_fill(params[e], &b->h_env[e]);
+        }
+    HIP_TRY(c, hipMemcpy(b->d_env_raw, b->h_env_raw.data(), sizeof(srbd_env_params) * (size_t)E,
+                         hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(b->d_env, b->h_env.data(), sizeof(EnvModel) * (size_t)E, hipMemcpyHostToDevice));
+    b->env_on = true;
+    return SRBD_OK;
+}
+
+// The same from the caller's device memory, enqueued on the caller's stream: one launch (batch_set_env_params_kernel)
+// that joins the device steps' event protocol as srbd_batch_set_gait_device does.  No synchronising call and no host
+// access to device memory: the host mirrors go stale and are downloaded by the next host call that needs them.
+extern "C" int srbd_batch_set_env_params_device(srbd_batch* b, const srbd_env_params* d_params, const int32_t* d_mask,
+                                                int32_t* d_rejected, void* hip_stream) {
+    if (!b) return fail(nullptr, SRBD_E_INVALID, "srbd_batch_set_env_params_device: null batch");
+    srbd_ctx* c = &b->c;
+    if (!d_params) return fail(c, SRBD_E_INVALID, "srbd_batch_set_env_params_device: null d_params");
+    if ((reinterpret_cast<uintptr_t>(d_params) | reinterpret_cast<uintptr_t>(d_mask) |
+         reinterpret_cast<uintptr_t>(d_rejected)) & 3)
+        return fail(c, SRBD_E_INVALID,
+                    "srbd_batch_set_env_params_device: d_params, d_mask and d_rejected must be 4-byte aligned");
+    HIP_TRY(c, hipSetDevice(c->cfg.device_id));
+    hipStream_t s = (hipStream_t)hip_stream;  // as srbd_batch_step_device reads it
+    if (!s) s = c->stream;
+    else if (s == hipStreamLegacy) s = nullptr;
+    // the previous device call on another stream still reads the records
+    if (b->dev_pending && b->dev_stream != s) HIP_TRY(c, hipStreamWaitEvent(s, b->dev_done, 0));
+    launch_batch_set_env_params(d_params, d_mask, d_rejected, b->E, b->d_env_raw, b->d_env, s);
+    const hipError_t le = hipGetLastError();
+    const hipError_t re = hipEventRecord(b->dev_done, s);
+    b->dev_stream = s;
+    b->dev_pending = re == hipSuccess;
+    HIP_TRY(c, le);
+    HIP_TRY(c, re);
+    b->env_on = true;
+    b->env_host_stale = true;
+    return SRBD_OK;
+}
+
+extern "C" int srbd_batch_get_env_params(srbd_batch* b, srbd_env_params* out) {
+    if (!b) return fail(nullptr, SRBD_E_INVALID, "srbd_batch_get_env_params: null batch");
+    srbd_ctx* c = &b->c;
+    if (!out) return fail(c, SRBD_E_INVALID, "srbd_batch_get_env_params: null out");
+    HIP_TRY(c, hipSetDevice(c->cfg.device_id));
+    HIP_TRY(c, batch_join_host(b));
+    HIP_TRY(c, batch_env_download(b));
+    memcpy(out, b->h_env_raw.data(), sizeof(srbd_env_params) * (size_t)b->E);
+    return SRBD_OK;
+}
+
+extern "C" int srbd_batch_clear_env_params(srbd_batch* b) {
+    if (!b) return fail(nullptr, SRBD_E_INVALID, "srbd_batch_clear_env_params: null batch");
+    srbd_ctx* c = &b->c;
+    if (!b->env_on) return SRBD_OK;
+    HIP_TRY(c, hipSetDevice(c->cfg.device_id));
+    HIP_TRY(c, batch_join_host(b));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, batch_env_reset(b));
+    return SRBD_OK;
+}
+
 extern "C" int srbd_batch_copy_costs(srbd_batch* b, float* out_costs) {
     if (!b || !out_costs) return SRBD_E_INVALID;
     if (!b->stepped) return fail(&b->c, SRBD_E_STATE, "no step yet");
@@ -3001,12 +3145,17 @@ static int batch_step_host(srbd_batch* b, const float* states, const float* refs
         b->dev_pending = false;
     }
     const int E = b->E, P = mc.P;
+    if (b->env_host_stale) {  // the parameters were last set on the device: the event above orders the download
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, batch_env_download(b));
+    }
+    const EnvModel* envs = b->env_on ? b->d_env : nullptr;
     for (int e = 0; e < E; ++e) {
         StepInput* in = b->h_in + e;
         const int rc = fill_input(&c->cfg, mc, in, states + 24 * (size_t)e, refs + 24 * (size_t)e,
                                   contacts + (size_t)e * 4 * contact_stride, contact_stride,
                                   best_params + (size_t)e * P, cem ? sigma + (size_t)e * P : nullptr, seeds[e],
-                                  counters[e]);
+                                  counters[e], b->env_on ? &b->h_env[e] : nullptr);
         if (rc) return fail(c, rc, "invalid step arguments");
         in->noise_scaled = noise ? 1 : 0;  // CEM: injected noise is used as given, device draws are unscaled
     }
@@ -3030,12 +3179,12 @@ static int batch_step_host(srbd_batch* b, const float* states, const float* refs
     }
     if (mc.ga)
         launch_batch_rollout_ga(mc, b->d_in, b->d_noise, b->d_costs, b->d_rec, c->wrec_stride, b->d_ga_freq, E,
-                                c->stream);
+                                c->stream, envs);
     else
-        launch_batch_rollout(mc, b->d_in, b->d_noise, b->d_costs, b->d_rec, c->wrec_stride, E, c->stream);
+        launch_batch_rollout(mc, b->d_in, b->d_noise, b->d_costs, b->d_rec, c->wrec_stride, E, c->stream, envs);
     const uint32_t seq = ++c->seq;
     launch_batch_merge(mc, b->d_in, b->d_rec, c->wrec_stride, b->d_noise, b->d_out_host, b->d_eflag, b->d_count,
-                       c->d_flag, seq, E, c->stream);
+                       c->d_flag, seq, E, c->stream, envs);
     HIP_TRY(c, hipGetLastError());
     int rc = wait_published(c, seq);
     if (rc) {  // the stream has drained (or failed): a launch that stopped part-way may have left arrivals counted
@@ -3123,18 +3272,20 @@ static int batch_step_dev(srbd_batch* b, const srbd_batch_device_io* io, const s
     const int E = b->E;
     // the previous device step on another stream still owns the internal buffers
     if (b->dev_pending && b->dev_stream != s) HIP_TRY(c, hipStreamWaitEvent(s, b->dev_done, 0));
-    launch_batch_pack(mc, c->cfg.q_diag + 12, *io, b->d_in, E, s, is_cem ? cem : nullptr);
+    const EnvModel* envs = b->env_on ? b->d_env : nullptr;
+    launch_batch_pack(mc, c->cfg.q_diag + 12, *io, b->d_in, E, s, is_cem ? cem : nullptr, envs);
     if (io->noise)
         launch_batch_transpose(mc, io->noise, b->d_noise, E, s);
     else
         launch_batch_rng(mc, b->d_in, b->d_noise, E, s);
     if (mc.ga)
-        launch_batch_rollout_ga(mc, b->d_in, b->d_noise, b->d_costs, b->d_rec, c->wrec_stride, b->d_ga_freq, E, s);
+        launch_batch_rollout_ga(mc, b->d_in, b->d_noise, b->d_costs, b->d_rec, c->wrec_stride, b->d_ga_freq, E, s,
+                                envs);
     else
-        launch_batch_rollout(mc, b->d_in, b->d_noise, b->d_costs, b->d_rec, c->wrec_stride, E, s);
+        launch_batch_rollout(mc, b->d_in, b->d_noise, b->d_costs, b->d_rec, c->wrec_stride, E, s, envs);
     const uint32_t seq = ++c->seq;
     launch_batch_merge(mc, b->d_in, b->d_rec, c->wrec_stride, b->d_noise, b->d_out, b->d_eflag, b->d_count, c->d_flag,
-                       seq, E, s);
+                       seq, E, s, envs);
     launch_batch_unpack(mc, *io, b->d_out, b->d_costs, E, s, is_cem ? cem->sigma : nullptr);
     const hipError_t le = hipGetLastError();
     // recorded whatever the launches returned: what was enqueued still orders the other entry points

@@ -161,6 +161,97 @@ __global__ void __launch_bounds__(64) batch_pack_cem_kernel(const srbd_batch_dev
     }
 }
 
+// batch_pack_kernel / batch_pack_cem_kernel restated for a batch with per-environment parameters
+// (srbd_batch_set_env_params): fzref from envs[e].mg and cost_feet from envs[e].q_feet, as fill_input forms them from
+// that environment's record on the host; everything else is those kernels' (siblings again, so they keep their code).
+template <bool CEM>
+__global__ void __launch_bounds__(64) batch_pack_env_kernel(const srbd_batch_device_io io, int H, int P, int vec,
+                                                            StepInput* __restrict__ in_arr,
+                                                            const EnvModel* __restrict__ envs,
+                                                            const srbd_batch_cem_io cem, int svec) {
+#pragma clang fp contract(off)
+    const int e = blockIdx.x, tid = threadIdx.x;
+    StepInput* __restrict__ in = in_arr + e;
+    const EnvModel* __restrict__ em = envs + e;
+    if constexpr (CEM) {
+        if (cem.sigma_reset > 0.0f) {
+            for (int i = tid; i < P; i += 64) in->sigma[i] = cem.sigma_reset;
+        } else {
+            const float* __restrict__ sp = cem.sigma + (size_t)e * P;
+            if (svec)
+                for (int i = tid; i < P / 4; i += 64)
+                    reinterpret_cast<float4*>(in->sigma)[i] = reinterpret_cast<const float4*>(sp)[i];
+            else
+                for (int i = tid; i < P; i += 64) in->sigma[i] = sp[i];
+        }
+    }
+    const float* __restrict__ st = io.states + 24 * (size_t)e;
+    const float* __restrict__ rf = io.refs + 24 * (size_t)e;
+    const float* __restrict__ bp = io.best_params + (size_t)e * P;
+    if (vec) {
+        if (tid < 12)
+            reinterpret_cast<float4*>(in)[tid] =
+                tid < 6 ? reinterpret_cast<const float4*>(st)[tid] : reinterpret_cast<const float4*>(rf)[tid - 6];
+        for (int i = tid; i < P / 4; i += 64)
+            reinterpret_cast<float4*>(in->best)[i] = reinterpret_cast<const float4*>(bp)[i];
+    } else {
+        if (tid < 48) reinterpret_cast<float*>(in)[tid] = tid < 24 ? st[tid] : rf[tid - 24];
+        for (int i = tid; i < P; i += 64) in->best[i] = bp[i];
+    }
+    if (tid < MAXH) {  // column n of the four legs
+        const int n = tid;
+        const float* __restrict__ ct = io.contacts + (size_t)e * 4 * io.contact_stride + n;
+        float c[4];
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {
+            c[l] = n < H ? ct[(size_t)l * io.contact_stride] : 0.0f;
+            in->contact[l][n] = c[l];
+        }
+        if (n < H) in->fzref[n] = em->mg / (((c[0] + c[1]) + c[2]) + c[3]);  // inf when no leg is in stance
+    } else if (tid == MAXH) {
+        float cf = 0.0f;
+#pragma unroll
+        for (int i = 12; i < 24; ++i) {
+            const float d = st[i] - rf[i];
+            cf = cf + (d * em->q_feet[i - 12]) * d;
+        }
+        in->cost_feet = cf;
+        const uint64_t seed = io.seeds[e], counter = io.counters[e];
+        in->seed_lo = (uint32_t)seed;
+        in->seed_hi = (uint32_t)(seed >> 32);
+        in->ctr_lo = (uint32_t)counter;
+        in->ctr_hi = (uint32_t)(counter >> 32);
+        in->noise_scaled = io.noise ? 1 : 0;
+    }
+}
+
+// srbd_batch_set_env_params_device: one thread per environment.  A selected environment's record (39 floats of the
+// caller's array) is checked as srbd_create checks a configuration; when it passes, the raw fields go to raw[e]
+// (srbd_batch_get_env_params) and the derived record to envs[e] through env_model_fill, the function the host setter
+// and srbd_create's model call; when it fails, both are left alone and rejected[e] = 1.  A masked-out environment's
+// record is neither read nor written; its rejected word is 0.
+__global__ void __launch_bounds__(64) batch_set_env_params_kernel(const srbd_env_params* __restrict__ params,
+                                                                  const int32_t* __restrict__ mask,
+                                                                  int32_t* __restrict__ rejected, int E,
+                                                                  srbd_env_params* __restrict__ raw,
+                                                                  EnvModel* __restrict__ envs) {
+    const int e = blockIdx.x * 64 + threadIdx.x;
+    if (e >= E) return;
+    int rej = 0;
+    if (!mask || mask[e] != 0) {
+        const srbd_env_params p = params[e];
+        if (env_params_ok(p)) {
+            EnvModel m;
+            env_model_fill(p, &m);
+            raw[e] = p;
+            envs[e] = m;
+        } else {
+            rej = 1;
+        }
+    }
+    if (rejected) rejected[e] = rej;
+}
+
 // out[e] (the merge blocks' records, device memory) and environment e's costs row into the caller's arrays: copies
 // only.  vec: best_params, grf and predicted_state are 16-byte aligned.
 // CEM (batch_unpack_cem_kernel): out[e].sigma into the caller's sigma row too (threads 192 .. 255; svec: 16-byte
@@ -282,11 +373,26 @@ __global__ void __launch_bounds__(256) batch_transpose_kernel(const float* __res
 // record (block_epilogue<true>).  The parameter trails and defaults to false: every statement it adds sits under
 // `if constexpr (CEMT)`, so the MPPI / random-sampling instantiations compile to the code they were (their mangled
 // names gain the argument).
-template <int KIND, int HT, int ST, bool EXT = false, bool CEMT = false>
+// ENVT (srbd_batch_set_env_params): the robot's and the cost's constants -- inv_m, the inertia and its inverse, the
+// force bounds, mu, Q -- come from envs[env], this block's environment record, instead of mc.  The address is
+// block-uniform and the array is read-only through a restrict pointer, so the values are scalar loads made once ahead
+// of the horizon (they take the SGPRs the kernel argument's fields took).  The parameter trails and defaults to
+// false, as CEMT does: the other instantiations take a model view of mc (model_view) and compile to the code they
+// were; they are passed envs == NULL and never read it.
+template <bool ENVT>
+__device__ __forceinline__ auto model_view(const ModelConst& mc, const EnvModel* __restrict__ envs, int env) {
+    if constexpr (ENVT)
+        return EnvRegs(envs[env]);
+    else
+        return McConst{mc};
+}
+template <int KIND, int HT, int ST, bool EXT = false, bool CEMT = false, bool ENVT = false>
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) batch_rollout_kernel(
     const ModelConst mc, const StepInput* __restrict__ in_arr, const float* __restrict__ noise_arr,
-    float* __restrict__ costs_arr, float* __restrict__ recs_arr, int rec_stride) {
+    float* __restrict__ costs_arr, float* __restrict__ recs_arr, int rec_stride,
+    const EnvModel* __restrict__ envs) {
     const int env = blockIdx.y;
+    const auto kc = model_view<ENVT>(mc, envs, env);
     const StepInput* __restrict__ in = in_arr + env;
     const float* __restrict__ noise = noise_arr + (size_t)env * mc.P * mc.ldn;
     float* __restrict__ costs = costs_arr + (size_t)env * mc.ldn;
@@ -319,9 +425,9 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) b
     const bool zs = CEMT && zs_scaled(mc, in);  // CEMT: CEM kernels only carry the scaling code
 
     // lane constants
-    const QuadLane L = quad_lane(mc, c);
-    const float Qp = sel3(c, mc.Q[0], mc.Q[1], mc.Q[2]), Qv = sel3(c, mc.Q[3], mc.Q[4], mc.Q[5]);
-    const float Qr = sel3(c, mc.Q[6], mc.Q[7], mc.Q[8]), Qw = sel3(c, mc.Q[9], mc.Q[10], mc.Q[11]);
+    const QuadLane L = quad_lane(kc, c);
+    const float Qp = sel3(c, kc.Q(0), kc.Q(1), kc.Q(2)), Qv = sel3(c, kc.Q(3), kc.Q(4), kc.Q(5));
+    const float Qr = sel3(c, kc.Q(6), kc.Q(7), kc.Q(8)), Qw = sel3(c, kc.Q(9), kc.Q(10), kc.Q(11));
     const float* st = in->state;
     const float* rf = in->ref;
     const float rp = sel3(c, rf[0], rf[1], rf[2]), rv = sel3(c, rf[3], rf[4], rf[5]);
@@ -463,8 +569,8 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) b
                 }
             }
             // shape_leg / clip_leg (srbd_core.h), this lane's leg
-            const float fz = clamp_cs((fref + rq[2]) * clq, mc.grf_min, mc.grf_max);
-            const float lo = mc.neg_mu * fz, hi = mc.mu * fz;
+            const float fz = clamp_cs((fref + rq[2]) * clq, kc.grf_min(), kc.grf_max());
+            const float lo = kc.neg_mu() * fz, hi = kc.mu() * fz;
             const float fx = clamp_cs(third(rq[0] * clq), lo, hi), fy = clamp_cs(third(rq[1] * clq), lo, hi);
             // integrate(): skew_dot(p_foot - p, f) * c (the position's components from their lanes)
             const float vx = footL[0] - qp<QP_B0>(p), vy = footL[1] - qp<QP_B1>(p), vz = footL[2] - qp<QP_B2>(p);
@@ -477,7 +583,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) b
             }
             const float temp = sel3(c, sm[0], sm[1], sm[2]);
             dep = sm[5];  // the next step's scalar loads issue from here on (step_ptr)
-            quad_rb_apply3(mc, L, quad_rb_prep(L, r, w), temp, sm[3], sm[4], sm[5], dt, p, v, r, w);
+            quad_rb_apply3(kc, L, quad_rb_prep(L, r, w), temp, sm[3], sm[4], sm[5], dt, p, v, r, w);
         } else {
             float tf[4], tt[4];
 #pragma unroll
@@ -508,10 +614,10 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) b
                     raw = sa * p1 + sb * phi + scc * p2 + sd * phin;
                 }
                 // shape_leg / clip_leg, component-wise
-                float zp = clamp_cs((fref + raw) * cl[l], mc.grf_min, mc.grf_max);
+                float zp = clamp_cs((fref + raw) * cl[l], kc.grf_min(), kc.grf_max());
                 const float xy = third(raw * cl[l]);
                 const float fz = qp<QP_B2>(c == 2 ? zp : xy);
-                const float f = c == 2 ? fz : clamp_cs(xy, mc.neg_mu * fz, mc.mu * fz);
+                const float f = c == 2 ? fz : clamp_cs(xy, kc.neg_mu() * fz, kc.mu() * fz);
                 tf[l] = f * cl[l];
                 tt[l] = quad_cross(feet[l] - p, f) * cl[l];
                 // extra_cost_step (srbd_core.h), this lane's component, leg by leg
@@ -522,7 +628,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) b
                     term = term + (d * mc.cost_smooth) * d;
                 }
                 {  // x / y lanes only, as a select
-                    float vv = fabsf(xy) - mc.mu * fz;
+                    float vv = fabsf(xy) - kc.mu() * fz;
                     vv = vv > 0.0f ? vv : 0.0f;
                     const float cone = (vv * mc.cost_cone) * vv;
                     term = c < 2 ? term + cone : term;
@@ -533,7 +639,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) b
             const float temp = (tf[0] + tf[1]) + (tf[2] + tf[3]);
             const float temp2 = (tt[0] + tt[1]) + (tt[2] + tt[3]);
             dep = temp2;  // the next step's scalar loads issue from here on (step_ptr)
-            quad_rigid_body(mc, L, temp, temp2, dt, p, v, r, w);
+            quad_rigid_body(kc, L, temp, temp2, dt, p, v, r, w);
         }
         // tracking cost (NMPC:451), accumulated per component lane
         const float ep = p - rp, ev = v - rv, er_ = r - rr, ew = w - rw;
@@ -582,13 +688,16 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) b
 // gait depends on is environment e's: in[e]'s leg phases, frequency set, seed and counter (the JAX streams:
 // jax_choice_index on in[e]'s key).  Injected frequencies: row k of environment e at ga_freq_arr[e ldn + k] (k < ldn;
 // mc.ga_freq, one context's pointer, is not read).  Left out: the in-launch draws.
-template <int KIND, int HT>
+// ENVT: as in batch_rollout_kernel; fz_ns, the gravity share per stance count, is the environment's too.
+template <int KIND, int HT, bool ENVT = false>
 __global__ void __launch_bounds__(512) batch_rollout_ga_kernel(const ModelConst mc, const StepInput* __restrict__ in_arr,
                                                                const float* __restrict__ noise_arr,
                                                                float* __restrict__ costs_arr,
                                                                float* __restrict__ recs_arr, int rec_stride,
-                                                               const float* __restrict__ ga_freq_arr) {
+                                                               const float* __restrict__ ga_freq_arr,
+                                                               const EnvModel* __restrict__ envs) {
     const int env = blockIdx.y;
+    const auto kc = model_view<ENVT>(mc, envs, env);
     const StepInput* __restrict__ in = in_arr + env;
     const float* __restrict__ noise = noise_arr + (size_t)env * mc.P * mc.ldn;
     float* __restrict__ costs = costs_arr + (size_t)env * mc.ldn;
@@ -616,9 +725,9 @@ __global__ void __launch_bounds__(512) batch_rollout_ga_kernel(const ModelConst 
     for (int l = 0; l < 4; ++l) seg[l] = ((float)__popc(mask[l]) + 1.0f) / (float)S;
     int cnt[4] = {-1, -1, -1, -1};
 
-    const QuadLane L = quad_lane(mc, c);
-    const float Qp = sel3(c, mc.Q[0], mc.Q[1], mc.Q[2]), Qv = sel3(c, mc.Q[3], mc.Q[4], mc.Q[5]);
-    const float Qr = sel3(c, mc.Q[6], mc.Q[7], mc.Q[8]), Qw = sel3(c, mc.Q[9], mc.Q[10], mc.Q[11]);
+    const QuadLane L = quad_lane(kc, c);
+    const float Qp = sel3(c, kc.Q(0), kc.Q(1), kc.Q(2)), Qv = sel3(c, kc.Q(3), kc.Q(4), kc.Q(5));
+    const float Qr = sel3(c, kc.Q(6), kc.Q(7), kc.Q(8)), Qw = sel3(c, kc.Q(9), kc.Q(10), kc.Q(11));
     const float* st_ = in->state;
     const float* rf = in->ref;
     const float rp = sel3(c, rf[0], rf[1], rf[2]), rv = sel3(c, rf[3], rf[4], rf[5]);
@@ -642,7 +751,7 @@ __global__ void __launch_bounds__(512) batch_rollout_ga_kernel(const ModelConst 
             cnt[l] += (int)b;
         }
         const float ns = ((cl[0] + cl[1]) + cl[2]) + cl[3];
-        const float fref = mc.fz_ns[(int)ns];
+        const float fref = kc.fz_ns((int)ns);
         float tf[4], tt[4];  // per-leg force / torque contributions, summed pairwise (integrate()'s order)
 #pragma unroll
         for (int l = 0; l < 4; ++l) {
@@ -678,15 +787,15 @@ __global__ void __launch_bounds__(512) batch_rollout_ga_kernel(const ModelConst 
                     raw = a * p1 + bb * phi + cc * p2 + d * phin;
                 }
             }
-            const float zp = clamp_cs((fref + raw) * cl[l], mc.grf_min, mc.grf_max);
+            const float zp = clamp_cs((fref + raw) * cl[l], kc.grf_min(), kc.grf_max());
             const float xy = third(raw * cl[l]);
             const float fz = qp<QP_B2>(c == 2 ? zp : xy);
-            const float fo = c == 2 ? fz : clamp_cs(xy, mc.neg_mu * fz, mc.mu * fz);
+            const float fo = c == 2 ? fz : clamp_cs(xy, kc.neg_mu() * fz, kc.mu() * fz);
             tf[l] = fo * cl[l];
             tt[l] = quad_cross(feet[l] - p, fo) * cl[l];
         }
         const float temp = (tf[0] + tf[1]) + (tf[2] + tf[3]), temp2 = (tt[0] + tt[1]) + (tt[2] + tt[3]);
-        quad_rigid_body(mc, L, temp, temp2, mc.dts[n], p, v, r, w);
+        quad_rigid_body(kc, L, temp, temp2, mc.dts[n], p, v, r, w);
         const float ep = p - rp, ev = v - rv, er_ = r - rr, ew = w - rw;
         const float tp = (ep * Qp) * ep, tv = (ev * Qv) * ev, tr = (er_ * Qr) * er_, tw = (ew * Qw) * ew;
         cost = cost + (((tp + tv) + tr) + tw);
@@ -706,19 +815,20 @@ __global__ void __launch_bounds__(512) batch_rollout_ga_kernel(const ModelConst 
 // with every wave's output stores complete, a system release by thread 0 (fence_sys) and its own publish word
 // (eflag[e], device memory, unread).  Then thread 0 counts its block; the last arriver resets the counter for the
 // next launch and stores `seq` into the host's word -- after every block's outputs, so one word publishes them all.
-template <int NT, bool STAGE>
+// ENVT (srbd_batch_set_env_params): the tail lanes' final GRFs and predicted state use envs[e] (merge_body's ENVT).
+template <int NT, bool STAGE, bool ENVT = false>
 __global__ void __launch_bounds__(NT) batch_merge_kernel(const ModelConst mc, StepInput* __restrict__ in,
                                                          const float* __restrict__ recs, int rec_stride,
                                                          const float* __restrict__ noise,
                                                          StepOutput* __restrict__ out, uint32_t* __restrict__ eflag,
                                                          uint32_t* __restrict__ count, uint32_t* __restrict__ flag,
-                                                         uint32_t seq) {
+                                                         uint32_t seq, const EnvModel* __restrict__ envs) {
     const int e = blockIdx.y;
     __shared__ MergeShared<NT> sh;
     extern __shared__ __attribute__((aligned(16))) float dsm[];
-    merge_body<NT, STAGE>(mc, in + e, recs + (size_t)e * mc.nleaf * rec_stride, mc.nleaf, rec_stride, 0,
-                          noise + (size_t)e * mc.P * mc.ldn, nullptr, out + e, 0, 0, nullptr, eflag + e, seq, 0, 1, sh,
-                          dsm);
+    merge_body<NT, STAGE, false, ENVT>(mc, in + e, recs + (size_t)e * mc.nleaf * rec_stride, mc.nleaf, rec_stride, 0,
+                                       noise + (size_t)e * mc.P * mc.ldn, nullptr, out + e, 0, 0, nullptr, eflag + e,
+                                       seq, 0, 1, sh, dsm, false, 0, nullptr, ENVT ? envs + e : nullptr);
     if (threadIdx.x == 0) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         const uint32_t old = __hip_atomic_fetch_add(count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -732,6 +842,8 @@ __global__ void __launch_bounds__(NT) batch_merge_kernel(const ModelConst mc, St
 // ------------------------------------------------------------------ launchers
 void batch_prepare() {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&batch_merge_kernel<MERGE_STAGE_THREADS, true>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)MERGE_LDS_DYN_MAX);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&batch_merge_kernel<MERGE_STAGE_THREADS, true, true>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)MERGE_LDS_DYN_MAX);
 }
 
@@ -748,7 +860,17 @@ void launch_batch_copy(const StepInput* in_host, StepInput* in, int E, size_t by
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 void launch_batch_pack(const ModelConst& mc, const float* q_feet, const srbd_batch_device_io& io, StepInput* in, int E,
-                       hipStream_t s, const srbd_batch_cem_io* cem) {
+                       hipStream_t s, const srbd_batch_cem_io* cem, const EnvModel* envs) {
+    if (envs) {
+        const int v = aligned16(io.states) && aligned16(io.refs) && aligned16(io.best_params);
+        if (cem)
+            hipLaunchKernelGGL(batch_pack_env_kernel<true>, dim3(E), dim3(64), 0, s, io, mc.H, mc.P, v, in, envs, *cem,
+                               (int)aligned16(cem->sigma));
+        else
+            hipLaunchKernelGGL(batch_pack_env_kernel<false>, dim3(E), dim3(64), 0, s, io, mc.H, mc.P, v, in, envs,
+                               srbd_batch_cem_io{nullptr, 0.0f, 0}, 0);
+        return;
+    }
     BatchPackConst pc;
     for (int i = 0; i < 12; ++i) pc.q_feet[i] = q_feet[i];
     pc.mg = mc.mg;
@@ -773,6 +895,12 @@ void launch_batch_unpack(const ModelConst& mc, const srbd_batch_device_io& io, c
                            vec);
 }
 
+void launch_batch_set_env_params(const srbd_env_params* params, const int32_t* mask, int32_t* rejected, int E,
+                                 srbd_env_params* raw, EnvModel* envs, hipStream_t s) {
+    hipLaunchKernelGGL(batch_set_env_params_kernel, dim3((E + 63) / 64), dim3(64), 0, s, params, mask, rejected, E, raw,
+                       envs);
+}
+
 void launch_batch_set_gait(const BatchGaitJob& j, StepInput* in, float* ga_freq, int E, hipStream_t s) {
     // one wave per environment for the fields alone; four when N rows are copied besides
     hipLaunchKernelGGL(batch_set_gait_kernel, dim3(E), dim3(j.io.freq_rows ? 256 : 64), 0, s, j, in, ga_freq);
@@ -790,27 +918,43 @@ void launch_batch_transpose(const ModelConst& mc, const float* src, float* noise
 }
 
 void launch_batch_rollout(const ModelConst& mc, const StepInput* in, const float* noise, float* costs, float* recs,
-                          int rec_stride, int E, hipStream_t s) {
+                          int rec_stride, int E, hipStream_t s, const EnvModel* envs) {
     const dim3 grid(mc.nleaf, E);
     const int H = mc.H, S = mc.S;
     // mc.cost_on (srbd_batch_set_cost_terms): the EXT instantiations, on the same compile-time shapes; CEM
     // (srbd_batch_create_cem): the CEMT ones, with or without EXT, as launch_rollout_t picks them
     const bool cem = mc.method == SRBD_CEM_MPPI;
-#define SRBD_BR(K, HH, SS)                                                                                        \
+    const EnvModel* const none = nullptr;
+#define SRBD_BR_(K, HH, SS, ENVT, EV)                                                                             \
     {                                                                                                             \
         if (cem && mc.cost_on)                                                                                    \
-            hipLaunchKernelGGL((batch_rollout_kernel<K, HH, SS, true, true>), grid, dim3(256), 0, s, mc, in,      \
-                               noise, costs, recs, rec_stride);                                                   \
+            hipLaunchKernelGGL((batch_rollout_kernel<K, HH, SS, true, true, ENVT>), grid, dim3(256), 0, s, mc,    \
+                               in, noise, costs, recs, rec_stride, EV);                                           \
         else if (cem)                                                                                             \
-            hipLaunchKernelGGL((batch_rollout_kernel<K, HH, SS, false, true>), grid, dim3(256), 0, s, mc, in,     \
-                               noise, costs, recs, rec_stride);                                                   \
+            hipLaunchKernelGGL((batch_rollout_kernel<K, HH, SS, false, true, ENVT>), grid, dim3(256), 0, s, mc,   \
+                               in, noise, costs, recs, rec_stride, EV);                                           \
         else if (mc.cost_on)                                                                                      \
-            hipLaunchKernelGGL((batch_rollout_kernel<K, HH, SS, true>), grid, dim3(256), 0, s, mc, in, noise,     \
-                               costs, recs, rec_stride);                                                          \
+            hipLaunchKernelGGL((batch_rollout_kernel<K, HH, SS, true, false, ENVT>), grid, dim3(256), 0, s, mc,   \
+                               in, noise, costs, recs, rec_stride, EV);                                           \
         else                                                                                                      \
-            hipLaunchKernelGGL((batch_rollout_kernel<K, HH, SS>), grid, dim3(256), 0, s, mc, in, noise, costs,    \
-                               recs, rec_stride);                                                                 \
+            hipLaunchKernelGGL((batch_rollout_kernel<K, HH, SS, false, false, ENVT>), grid, dim3(256), 0, s, mc,  \
+                               in, noise, costs, recs, rec_stride, EV);                                           \
         return;                                                                                                   \
+    }
+#define SRBD_BR(K, HH, SS) SRBD_BR_(K, HH, SS, false, none)
+#define SRBD_BRE(K, HH, SS) SRBD_BR_(K, HH, SS, true, envs)
+    if (envs) {
+        // per-environment parameters: the flagship's compile-time shape (zero-order, H 12) and the generic kernel of
+        // each parametrization -- every shape returns srbd_step's bits, so the choice only costs time
+        switch (mc.kind) {
+            case SRBD_ZERO_ORDER:
+                if (H == 12) SRBD_BRE(SRBD_ZERO_ORDER, 12, 0);
+                SRBD_BRE(SRBD_ZERO_ORDER, 0, 0);
+            case SRBD_LINEAR_SPLINE:
+                SRBD_BRE(SRBD_LINEAR_SPLINE, 0, 0);
+            default:
+                SRBD_BRE(SRBD_CUBIC_SPLINE, 0, 0);
+        }
     }
     switch (mc.kind) {  // launch_rollout's compile-time shapes
         case SRBD_ZERO_ORDER:
@@ -828,17 +972,33 @@ void launch_batch_rollout(const ModelConst& mc, const StepInput* in, const float
             SRBD_BR(SRBD_CUBIC_SPLINE, 0, 0);
     }
 #undef SRBD_BR
+#undef SRBD_BRE
+#undef SRBD_BR_
 }
 
 void launch_batch_rollout_ga(const ModelConst& mc, const StepInput* in, const float* noise, float* costs, float* recs,
-                             int rec_stride, const float* ga_freq, int E, hipStream_t s) {
+                             int rec_stride, const float* ga_freq, int E, hipStream_t s, const EnvModel* envs) {
     const dim3 grid(mc.nleaf, E);
     const int H = mc.H;
-#define SRBD_BG(K, HH)                                                                                            \
+    const EnvModel* const none = nullptr;
+#define SRBD_BG_(K, HH, ENVT, EV)                                                                                 \
     {                                                                                                             \
-        hipLaunchKernelGGL((batch_rollout_ga_kernel<K, HH>), grid, dim3(256), 0, s, mc, in, noise, costs, recs,   \
-                           rec_stride, ga_freq);                                                                  \
+        hipLaunchKernelGGL((batch_rollout_ga_kernel<K, HH, ENVT>), grid, dim3(256), 0, s, mc, in, noise, costs,   \
+                           recs, rec_stride, ga_freq, EV);                                                        \
         return;                                                                                                   \
+    }
+#define SRBD_BG(K, HH) SRBD_BG_(K, HH, false, none)
+#define SRBD_BGE(K, HH) SRBD_BG_(K, HH, true, envs)
+    if (envs) {  // as launch_batch_rollout picks them
+        switch (mc.kind) {
+            case SRBD_ZERO_ORDER:
+                if (H == 12) SRBD_BGE(SRBD_ZERO_ORDER, 12);
+                SRBD_BGE(SRBD_ZERO_ORDER, 0);
+            case SRBD_LINEAR_SPLINE:
+                SRBD_BGE(SRBD_LINEAR_SPLINE, 0);
+            default:
+                SRBD_BGE(SRBD_CUBIC_SPLINE, 0);
+        }
     }
     switch (mc.kind) {  // launch_rollout_ga's compile-time shapes
         case SRBD_ZERO_ORDER:
@@ -856,19 +1016,29 @@ void launch_batch_rollout_ga(const ModelConst& mc, const StepInput* in, const fl
             SRBD_BG(SRBD_CUBIC_SPLINE, 0);
     }
 #undef SRBD_BG
+#undef SRBD_BGE
+#undef SRBD_BG_
 }
 
 void launch_batch_merge(const ModelConst& mc, StepInput* in, const float* recs, int rec_stride, const float* noise,
                         StepOutput* out, uint32_t* eflag, uint32_t* count, uint32_t* flag, uint32_t seq, int E,
-                        hipStream_t s) {
+                        hipStream_t s, const EnvModel* envs) {
     size_t smem = 0;
     const dim3 grid(1, E);
-    if (merge_stage_fits(mc.nleaf, rec_stride, mc.P, mc.K, &smem))
+    const EnvModel* const none = nullptr;
+    const bool stage = merge_stage_fits(mc.nleaf, rec_stride, mc.P, mc.K, &smem);
+    if (stage && envs)
+        hipLaunchKernelGGL((batch_merge_kernel<MERGE_STAGE_THREADS, true, true>), grid, dim3(MERGE_STAGE_THREADS), smem,
+                           s, mc, in, recs, rec_stride, noise, out, eflag, count, flag, seq, envs);
+    else if (stage)
         hipLaunchKernelGGL((batch_merge_kernel<MERGE_STAGE_THREADS, true>), grid, dim3(MERGE_STAGE_THREADS), smem, s, mc,
-                           in, recs, rec_stride, noise, out, eflag, count, flag, seq);
+                           in, recs, rec_stride, noise, out, eflag, count, flag, seq, none);
+    else if (envs)
+        hipLaunchKernelGGL((batch_merge_kernel<MERGE_THREADS, false, true>), grid, dim3(MERGE_THREADS), smem, s, mc, in,
+                           recs, rec_stride, noise, out, eflag, count, flag, seq, envs);
     else
         hipLaunchKernelGGL((batch_merge_kernel<MERGE_THREADS, false>), grid, dim3(MERGE_THREADS), smem, s, mc, in, recs,
-                           rec_stride, noise, out, eflag, count, flag, seq);
+                           rec_stride, noise, out, eflag, count, flag, seq, none);
 }
 
 }  // namespace srbd

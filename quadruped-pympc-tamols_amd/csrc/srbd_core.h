@@ -59,6 +59,22 @@ struct ModelConst {
     // reference's jax.random stream (RNG_JAX / RNG_JAX_LEGACY, keyed by the packed key `seed`; srbd_jaxrng.h)
     int rng;
 };
+// One environment's robot and cost constants in a batch with per-environment parameters
+// (srbd_batch_set_env_params): ModelConst's fields of the same names, derived from a srbd_env_params by
+// env_model_fill below, plus the feet weights q_diag[12..23] the step input's cost_feet uses.  A batch keeps E of them
+// in device memory; a block reads its environment's through a uniform address.
+struct EnvModel {
+    float inv_m, mg, grf_min, grf_max, mu, neg_mu;
+    float inertia[9], Iinv[9];
+    float Q[12];
+    float q_feet[12];
+    float fz_ns[5];
+    float pad[3];
+};
+static_assert(sizeof(EnvModel) == 224 && sizeof(EnvModel) % 16 == 0, "EnvModel is padded to 16-byte words");
+static_assert(sizeof(srbd_env_params) == 156 && offsetof(srbd_env_params, inertia) == 20 &&
+                  offsetof(srbd_env_params, q_diag) == 56,
+              "srbd_env_params is 39 packed floats");
 SRBD_HD bool is_tail_col(const ModelConst& mc, int j) { return (mc.tailmask[j >> 5] >> (j & 31)) & 1u; }
 
 constexpr int GA_MAXCB = 33;  // chunk boundaries of S <= 32 splines
@@ -276,6 +292,34 @@ SRBD_HD void inv3(const float A[9], float out[9]) {
     }
 }
 
+// srbd_create's checks of the robot fields (a NaN fails them)
+SRBD_HD bool env_params_ok(const srbd_env_params& p) {
+    return p.grf_min >= 0.0f && p.grf_max >= p.grf_min && p.mu >= 0.0f;
+}
+// The constants derived from a robot's seven fields -- the one place they are formed: srbd_create's model
+// (build_model), the host setter and the device setter of srbd_batch_set_env_params all call it, so a record and a
+// context's ModelConst hold the same bits.  Unfused on the device as on the host; the divisions are the compiler's
+// correctly rounded ones on both.
+SRBD_HD void env_model_fill(const srbd_env_params& p, EnvModel* m) {
+#pragma clang fp contract(off)
+    m->inv_m = 1.0f / p.mass;
+    m->mg = p.mg;
+    m->grf_min = p.grf_min;
+    m->grf_max = p.grf_max;
+    m->mu = p.mu;
+    m->neg_mu = -p.mu;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) m->inertia[i] = p.inertia[i];
+    inv3(p.inertia, m->Iinv);
+#pragma unroll
+    for (int i = 0; i < 12; ++i) m->Q[i] = p.q_diag[i];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) m->q_feet[i] = p.q_diag[12 + i];
+#pragma unroll
+    for (int i = 0; i < 5; ++i) m->fz_ns[i] = p.mg / (float)i;  // the division fill_input makes per step
+    m->pad[0] = m->pad[1] = m->pad[2] = 0.0f;
+}
+
 SRBD_HD void mv3(const float M[9], const float v[3], float o[3]) {
 #pragma unroll
     for (int i = 0; i < 3; ++i) o[i] = M[3 * i] * v[0] + M[3 * i + 1] * v[1] + M[3 * i + 2] * v[2];
@@ -339,15 +383,44 @@ SRBD_HD void euler_rates(float sr, float cr, float sp, float cp, float w0, float
 }
 
 // Model constants as the rollout reads them (the KC template parameter of integrate_k / clip_leg_k / shape_leg_k).
-struct McConst {
-    const ModelConst& m;
+// KView<ModelConst> (McConst): the shared values every block gets in its kernel argument.  KView<EnvModel> (EnvConst):
+// one environment's record of a batch with per-environment parameters (srbd_batch_set_env_params), read through a
+// block-uniform address.  The rollout, the merge tail and the quad helpers take either.
+template <class M>
+struct KView {
+    const M& m;
     SRBD_HD float inv_m() const { return m.inv_m; }
+    SRBD_HD float mg() const { return m.mg; }
     SRBD_HD const float* inertia() const { return m.inertia; }
     SRBD_HD const float* Iinv() const { return m.Iinv; }
     SRBD_HD float grf_min() const { return m.grf_min; }
     SRBD_HD float grf_max() const { return m.grf_max; }
     SRBD_HD float mu() const { return m.mu; }
     SRBD_HD float neg_mu() const { return m.neg_mu; }
+    SRBD_HD float Q(int i) const { return m.Q[i]; }
+    SRBD_HD float fz_ns(int i) const { return m.fz_ns[i]; }
+};
+using McConst = KView<ModelConst>;
+using EnvConst = KView<EnvModel>;
+// EnvConst for a rollout's horizon: the five values every step uses are read from the record once, here, and kept
+// (through the reference the compiler re-reads them, two scalar loads per unrolled step: nothing tells it the record
+// is not written meanwhile); the values read once ahead of the horizon anyway -- inertia, its inverse, Q -- and the
+// per-lane fz_ns stay reads of the record.
+struct EnvRegs {
+    const EnvModel& m;
+    float inv_m_, grf_min_, grf_max_, mu_, neg_mu_;
+    SRBD_HD explicit EnvRegs(const EnvModel& e)
+        : m(e), inv_m_(e.inv_m), grf_min_(e.grf_min), grf_max_(e.grf_max), mu_(e.mu), neg_mu_(e.neg_mu) {}
+    SRBD_HD float inv_m() const { return inv_m_; }
+    SRBD_HD float mg() const { return m.mg; }
+    SRBD_HD const float* inertia() const { return m.inertia; }
+    SRBD_HD const float* Iinv() const { return m.Iinv; }
+    SRBD_HD float grf_min() const { return grf_min_; }
+    SRBD_HD float grf_max() const { return grf_max_; }
+    SRBD_HD float mu() const { return mu_; }
+    SRBD_HD float neg_mu() const { return neg_mu_; }
+    SRBD_HD float Q(int i) const { return m.Q[i]; }
+    SRBD_HD float fz_ns(int i) const { return m.fz_ns[i]; }
 };
 
 // Centroidal_Model_JAX.fd + integrate_jax (CMJ:93-174).  x: 12 evolving states, feet: 12

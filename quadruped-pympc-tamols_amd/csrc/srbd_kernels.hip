@@ -135,7 +135,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(SRBD_Q
     const bool zs = CEMT && zs_scaled(mc, in);  // CEMT: CEM kernels only carry the scaling code
 
     // lane constants
-    const QuadLane L = quad_lane(mc, c);
+    const QuadLane L = quad_lane(McConst{mc}, c);
     const float Qp = sel3(c, mc.Q[0], mc.Q[1], mc.Q[2]), Qv = sel3(c, mc.Q[3], mc.Q[4], mc.Q[5]);
     const float Qr = sel3(c, mc.Q[6], mc.Q[7], mc.Q[8]), Qw = sel3(c, mc.Q[9], mc.Q[10], mc.Q[11]);
     const float* st = in->state;
@@ -347,7 +347,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(SRBD_Q
             temp = sel3(c, sm[0], sm[1], sm[2]);
             temp2 = sel3(c, sm[3], sm[4], sm[5]);
             dep = sm[5];  // the next step's scalar loads issue from here on (step_ptr)
-            quad_rb_apply3(mc, L, quad_rb_prep(L, r, w), temp, sm[3], sm[4], sm[5], dt, p, v, r, w);
+            quad_rb_apply3(McConst{mc}, L, quad_rb_prep(L, r, w), temp, sm[3], sm[4], sm[5], dt, p, v, r, w);
         } else {
         float tf[4], tt[4];
 #pragma unroll
@@ -404,7 +404,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(SRBD_Q
         temp = (tf[0] + tf[1]) + (tf[2] + tf[3]);
         temp2 = (tt[0] + tt[1]) + (tt[2] + tt[3]);
         dep = temp2;  // the next step's scalar loads issue from here on (step_ptr)
-        quad_rigid_body(mc, L, temp, temp2, dt, p, v, r, w);
+        quad_rigid_body(McConst{mc}, L, temp, temp2, dt, p, v, r, w);
         }
         // tracking cost (NMPC:451), accumulated per component lane: cost_c += ((tp + tv) + tr) + tw,
         // the three lanes summed once after the horizon (see rollout_kernel for the same order)
@@ -492,7 +492,7 @@ __global__ void __launch_bounds__(512) rollout_ga_quad_kernel(const ModelConst m
     for (int l = 0; l < 4; ++l) seg[l] = ((float)__popc(mask[l]) + 1.0f) / (float)S;
     int cnt[4] = {-1, -1, -1, -1};
 
-    const QuadLane L = quad_lane(mc, c);
+    const QuadLane L = quad_lane(McConst{mc}, c);
     const float Qp = sel3(c, mc.Q[0], mc.Q[1], mc.Q[2]), Qv = sel3(c, mc.Q[3], mc.Q[4], mc.Q[5]);
     const float Qr = sel3(c, mc.Q[6], mc.Q[7], mc.Q[8]), Qw = sel3(c, mc.Q[9], mc.Q[10], mc.Q[11]);
     const float* st_ = in->state;
@@ -562,7 +562,7 @@ __global__ void __launch_bounds__(512) rollout_ga_quad_kernel(const ModelConst m
             tt[l] = quad_cross(feet[l] - p, fo) * cl[l];
         }
         const float temp = (tf[0] + tf[1]) + (tf[2] + tf[3]), temp2 = (tt[0] + tt[1]) + (tt[2] + tt[3]);
-        quad_rigid_body(mc, L, temp, temp2, mc.dts[n], p, v, r, w);
+        quad_rigid_body(McConst{mc}, L, temp, temp2, mc.dts[n], p, v, r, w);
         const float ep = p - rp, ev = v - rv, er_ = r - rr, ew = w - rw;
         const float tp = (ep * Qp) * ep, tv = (ev * Qv) * ev, tr = (er_ * Qr) * er_, tw = (ew * Qw) * ew;
         cost = cost + (((tp + tv) + tr) + tw);
@@ -809,7 +809,7 @@ __device__ __forceinline__ void ft_prep(const ModelConst& mc, const StepInput* i
         const int qc = tid - FT_TAIL0 < 3 ? tid - FT_TAIL0 : 2;
         float tail_pre[13];
         merge_tail_load(gin, qc, tail_pre);
-        merge_tail_lane(mc, qc, tail_pre, tsh + 40 * (tid - FT_TAIL0));
+        merge_tail_lane(mc, McConst{mc}, qc, tail_pre, tsh + 40 * (tid - FT_TAIL0));
     }
     if (tid < P) b0 = gin->best[tid];
     if (tid >= 12 && tid < 24) state_hi = gin->state[tid];

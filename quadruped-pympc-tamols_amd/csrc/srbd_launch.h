@@ -175,8 +175,13 @@ void launch_batch_copy(const StepInput* in_host, StepInput* in, int E, size_t by
 // the gait fields and sigma are left alone), and out[e] (device memory) with the costs rows into the caller's arrays.
 // cem / sigma != NULL (srbd_batch_step_cem_device): in[e].sigma from cem->sigma or the constant cem->sigma_reset, and
 // out[e].sigma into the caller's sigma rows, in the same launches
+// envs != NULL (srbd_batch_set_env_params): fzref and cost_feet from environment e's record instead of mc.mg / q_feet
 void launch_batch_pack(const ModelConst& mc, const float* q_feet, const srbd_batch_device_io& io, StepInput* in, int E,
-                       hipStream_t s, const srbd_batch_cem_io* cem = nullptr);
+                       hipStream_t s, const srbd_batch_cem_io* cem = nullptr, const EnvModel* envs = nullptr);
+// srbd_batch_set_env_params_device: the caller's device arrays (E records; mask and rejected E words or NULL) into the
+// batch's raw fields raw[E] and derived records envs[E]; one thread per environment
+void launch_batch_set_env_params(const srbd_env_params* params, const int32_t* mask, int32_t* rejected, int E,
+                                 srbd_env_params* raw, EnvModel* envs, hipStream_t s);
 void launch_batch_unpack(const ModelConst& mc, const srbd_batch_device_io& io, const StepOutput* out,
                          const float* costs, int E, hipStream_t s, float* sigma = nullptr);
 // srbd_batch_set_gait_device: the caller's io by value, the chunk boundaries ga_chunk_bounds formed on the host and the
@@ -193,18 +198,21 @@ void launch_batch_rng(const ModelConst& mc, const StepInput* in, float* noise, i
 void launch_batch_transpose(const ModelConst& mc, const float* src, float* noise, int E, hipStream_t s);
 // four-lane rollouts, one 64-sample leaf per block: costs and leaf records (no in-launch fold); mc.cost_on selects
 // the kernels with the opt-in cost terms
+// envs != NULL (srbd_batch_set_env_params, here and in the two launchers below): E per-environment records; the
+// kernels' ENVT forms read the robot's and the cost's constants from envs[e] instead of mc
 void launch_batch_rollout(const ModelConst& mc, const StepInput* in, const float* noise, float* costs, float* recs,
-                          int rec_stride, int E, hipStream_t s);
+                          int rec_stride, int E, hipStream_t s, const EnvModel* envs = nullptr);
 // the gait-adaptive four-lane rollouts, keyed by in[e]'s gait fields; ga_freq: E x ldn injected per-row frequencies
 // (read only when in[e].ga_explicit is set; padding rows zero), else may be NULL
 void launch_batch_rollout_ga(const ModelConst& mc, const StepInput* in, const float* noise, float* costs, float* recs,
-                             int rec_stride, const float* ga_freq, int E, hipStream_t s);
+                             int rec_stride, const float* ga_freq, int E, hipStream_t s,
+                             const EnvModel* envs = nullptr);
 // one block per environment folds its leaf records to the root (merge_body) and writes out[e]; the blocks count
 // themselves in *count (zero between launches: the last arriver resets it) and the last one stores `seq` in *flag.
 // eflag: E device words (each block's own publish word inside merge_body)
 void launch_batch_merge(const ModelConst& mc, StepInput* in, const float* recs, int rec_stride, const float* noise,
                         StepOutput* out, uint32_t* eflag, uint32_t* count, uint32_t* flag, uint32_t seq, int E,
-                        hipStream_t s);
+                        hipStream_t s, const EnvModel* envs = nullptr);
 
 // TAMOLS (tamols_kernel.hip)
 constexpr int TAMOLS_NQ = 19;       // nearest-neighbour queries per candidate

@@ -248,8 +248,12 @@ __device__ __forceinline__ void merge_tail_load(const IN* in, int qc, float* tai
 #pragma unroll
     for (int l = 0; l < 4; ++l) tail_pre[9 + l] = in->state[12 + 3 * l + qc];  // feet
 }
-__device__ __forceinline__ void merge_tail_lane(const ModelConst& mc, int qc, const float* tail_pre, float* row) {
-    const QuadLane L = quad_lane(mc, qc);
+// kc: the robot's constants (KView: the shared ModelConst, or the environment's record in a batch with per-environment
+// parameters); the decode coefficients and dts[0] are always the shared ones.
+template <class KC>
+__device__ __forceinline__ void merge_tail_lane(const ModelConst& mc, const KC& kc, int qc, const float* tail_pre,
+                                                float* row) {
+    const QuadLane L = quad_lane(kc, qc);
     const QuadRB rb = quad_rb_prep(L, tail_pre[7], tail_pre[8]);
     row[36] = L.Ii0;
     row[37] = L.Ii1;
@@ -265,8 +269,8 @@ __device__ __forceinline__ void merge_tail_lane(const ModelConst& mc, int qc, co
     const int iv[5] = {mc.kind, mc.H, mc.PL, mc.S, mc.fidx};
 #pragma unroll
     for (int i = 0; i < 5; ++i) row[18 + i] = __int_as_float(iv[i]);
-    const float fv[13] = {mc.fq, mc.fomq, mc.fa, mc.fb, mc.fc, mc.fd, mc.grf_min,
-                          mc.grf_max, mc.mu, mc.neg_mu, mc.inv_m, mc.dts[0], 0.0f};
+    const float fv[13] = {mc.fq,        mc.fomq, mc.fa,       mc.fb,      mc.fc,     mc.fd, kc.grf_min(),
+                          kc.grf_max(), kc.mu(), kc.neg_mu(), kc.inv_m(), mc.dts[0], 0.0f};
 #pragma unroll
     for (int i = 0; i < 13; ++i) row[23 + i] = fv[i];
 }
@@ -342,14 +346,17 @@ __device__ __forceinline__ void merge_tail_grf(int c, const float* ts, const flo
 // smem: [STAGE: records] | scale[nrec_pad] | tree levels | node keys | erow[K*ncol] (merge_smem_bytes).  prestaged
 // (STAGE): the records are already in smem.  The staged body's sums use G = MERGE_STAGE_THREADS / (ncol + 1)
 // record groups whatever NT is, so a 256-thread block merges bit for bit as the 512-thread kernel does.
-template <int NT, bool STAGE, bool SPLITX = false>
+// ENVT (batch_merge_kernel with per-environment parameters): the tail lanes take the robot's constants from `em`, this
+// block's environment record, instead of mc; nothing else of the merge reads them.
+template <int NT, bool STAGE, bool SPLITX = false, bool ENVT = false>
 __device__ __forceinline__ void merge_body(const ModelConst& mc, StepInput* __restrict__ in,
                                            const float* __restrict__ recs, int nrec, int rec_stride, int rows_in_rec,
                                            const float* __restrict__ noise, float* __restrict__ rank_out,
                                            StepOutput* __restrict__ out, int chain, int ctr_inc,
                                            uint64_t* __restrict__ dbg, uint32_t* __restrict__ flag, uint32_t seq,
                                            int split_cs, int fence_sys, MergeShared<NT>& sh, float* smem,
-                                           bool prestaged = false, int levels_up = 0, SplitXchg* xg = nullptr) {
+                                           bool prestaged = false, int levels_up = 0, SplitXchg* xg = nullptr,
+                                           const EnvModel* __restrict__ em = nullptr) {
     constexpr int NW = NT / 64;
     uint64_t* red = sh.red;
     uint64_t* elite = sh.elite;
@@ -422,7 +429,12 @@ __device__ __forceinline__ void merge_body(const ModelConst& mc, StepInput* __re
     // the predicted state's force-independent part (NMPC:752-784 via CMJ:93-174), formed while the
     // record loads are in flight
     auto tail_prep = [&]() {
-        if (tail_lane) merge_tail_lane(mc, qc, tail_pre, tail_sh[tid]);
+        if (tail_lane) {
+            if constexpr (ENVT)
+                merge_tail_lane(mc, EnvConst{*em}, qc, tail_pre, tail_sh[tid]);
+            else
+                merge_tail_lane(mc, McConst{mc}, qc, tail_pre, tail_sh[tid]);
+        }
     };
     if constexpr (STAGE) {
         constexpr int U = 8;

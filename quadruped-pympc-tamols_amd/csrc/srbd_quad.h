@@ -42,16 +42,20 @@ struct QuadLane {
     int c;
     float g, Ir0, Ir1, Ir2, Ii0, Ii1, Ii2;
 };
-__device__ __forceinline__ QuadLane quad_lane(const ModelConst& mc, int c) {
+// kc: the model constants' view (srbd_core.h KView: the shared ModelConst or one environment's EnvModel)
+template <class KC>
+__device__ __forceinline__ QuadLane quad_lane(const KC& kc, int c) {
+    const float* inertia = kc.inertia();
+    const float* Iinv = kc.Iinv();
     QuadLane L;
     L.c = c;
     L.g = c == 2 ? -9.81f : 0.0f;
-    L.Ir0 = sel3(c, mc.inertia[0], mc.inertia[3], mc.inertia[6]);
-    L.Ir1 = sel3(c, mc.inertia[1], mc.inertia[4], mc.inertia[7]);
-    L.Ir2 = sel3(c, mc.inertia[2], mc.inertia[5], mc.inertia[8]);
-    L.Ii0 = sel3(c, mc.Iinv[0], mc.Iinv[3], mc.Iinv[6]);
-    L.Ii1 = sel3(c, mc.Iinv[1], mc.Iinv[4], mc.Iinv[7]);
-    L.Ii2 = sel3(c, mc.Iinv[2], mc.Iinv[5], mc.Iinv[8]);
+    L.Ir0 = sel3(c, inertia[0], inertia[3], inertia[6]);
+    L.Ir1 = sel3(c, inertia[1], inertia[4], inertia[7]);
+    L.Ir2 = sel3(c, inertia[2], inertia[5], inertia[8]);
+    L.Ii0 = sel3(c, Iinv[0], Iinv[3], Iinv[6]);
+    L.Ii1 = sel3(c, Iinv[1], Iinv[4], Iinv[7]);
+    L.Ii2 = sel3(c, Iinv[2], Iinv[5], Iinv[8]);
     return L;
 }
 
@@ -96,9 +100,10 @@ __device__ __forceinline__ QuadRB quad_rb_prep(const QuadLane& L, float r, float
     const float a1 = L.Ii0 * qp<QP_B0>(wx) + L.Ii1 * qp<QP_B1>(wx) + L.Ii2 * qp<QP_B2>(wx);
     return QuadRB{er, R0, R1, R2, a1};
 }
-__device__ __forceinline__ void quad_rb_apply(const ModelConst& mc, const QuadLane& L, const QuadRB& q, float temp,
+template <class KC>
+__device__ __forceinline__ void quad_rb_apply(const KC& kc, const QuadLane& L, const QuadRB& q, float temp,
                                               float temp2, float dt, float& p, float& v, float& r, float& w) {
-    const float lin = mc.inv_m * temp + L.g;
+    const float lin = kc.inv_m() * temp + L.g;
     const float Rt = q.R0 * qp<QP_B0>(temp2) + q.R1 * qp<QP_B1>(temp2) + q.R2 * qp<QP_B2>(temp2);
     const float a2 = L.Ii0 * qp<QP_B0>(Rt) + L.Ii1 * qp<QP_B1>(Rt) + L.Ii2 * qp<QP_B2>(Rt);
     const float aa = -q.a1 + a2;
@@ -110,10 +115,11 @@ __device__ __forceinline__ void quad_rb_apply(const ModelConst& mc, const QuadLa
 }
 // quad_rb_apply with the torque sum's three components already on every lane (the leg-parallel force phase):
 // the same float operations, no broadcasts.
-__device__ __forceinline__ void quad_rb_apply3(const ModelConst& mc, const QuadLane& L, const QuadRB& q, float temp,
+template <class KC>
+__device__ __forceinline__ void quad_rb_apply3(const KC& kc, const QuadLane& L, const QuadRB& q, float temp,
                                                float t2x, float t2y, float t2z, float dt, float& p, float& v, float& r,
                                                float& w) {
-    const float lin = mc.inv_m * temp + L.g;
+    const float lin = kc.inv_m() * temp + L.g;
     const float Rt = q.R0 * t2x + q.R1 * t2y + q.R2 * t2z;
     const float a2 = L.Ii0 * qp<QP_B0>(Rt) + L.Ii1 * qp<QP_B1>(Rt) + L.Ii2 * qp<QP_B2>(Rt);
     const float aa = -q.a1 + a2;
@@ -123,9 +129,10 @@ __device__ __forceinline__ void quad_rb_apply3(const ModelConst& mc, const QuadL
     r = rn;
     w = wn;
 }
-__device__ __forceinline__ void quad_rigid_body(const ModelConst& mc, const QuadLane& L, float temp, float temp2,
+template <class KC>
+__device__ __forceinline__ void quad_rigid_body(const KC& kc, const QuadLane& L, float temp, float temp2,
                                                 float dt, float& p, float& v, float& r, float& w) {
-    quad_rb_apply(mc, L, quad_rb_prep(L, r, w), temp, temp2, dt, p, v, r, w);
+    quad_rb_apply(kc, L, quad_rb_prep(L, r, w), temp, temp2, dt, p, v, r, w);
 }
 
 // This lane's component of (p_i - p_com) x f_i (jnp.dot(skew(v), f), CMJ:100-101, zero terms dropped).

@@ -98,6 +98,18 @@ class BatchCemIO(C.Structure):
     _fields_ = [("sigma", _P), ("sigma_reset", _F), ("pad", _I)]
 
 
+class EnvParams(C.Structure):
+    """srbd_env_params (include/srbd_mpc.h): one environment's robot and cost parameters, 39 packed floats."""
+    _fields_ = [("mass", _F), ("mg", _F), ("grf_min", _F), ("grf_max", _F), ("mu", _F), ("inertia", _F * 9),
+                ("q_diag", _F * 24), ("reserved", _F)]
+
+
+# the same record as a numpy structured dtype (156 bytes): arrays of it go to the C calls as they are
+ENV_PARAMS_DTYPE = np.dtype([("mass", np.float32), ("mg", np.float32), ("grf_min", np.float32),
+                             ("grf_max", np.float32), ("mu", np.float32), ("inertia", np.float32, (9,)),
+                             ("q_diag", np.float32, (24,)), ("reserved", np.float32)])
+ENV_PARAMS_FLOATS = ENV_PARAMS_DTYPE.itemsize // 4
+
 MAX_FREQS = 8  # SRBD_MAX_FREQS
 
 
@@ -352,6 +364,10 @@ SIGNATURES.update({
     "srbd_batch_create_cem": (_I, [C.POINTER(SrbdConfig), _I, C.POINTER(_P)]),
     "srbd_batch_step_cem": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "srbd_batch_step_cem_device": (_I, [_P, C.POINTER(BatchDeviceIO), C.POINTER(BatchCemIO), _P]),
+    "srbd_batch_set_env_params": (_I, [_P, _P, _P]),
+    "srbd_batch_set_env_params_device": (_I, [_P, _P, _P, _P, _P]),
+    "srbd_batch_get_env_params": (_I, [_P, _P]),
+    "srbd_batch_clear_env_params": (_I, [_P]),
     # the device producers: device arrays as plain addresses, dts / lens host arrays
     "srbd_pgg_run_device": (_I, [_P, _I, _D, _P, _P, _P]),
     "srbd_pgg_contact_sequence_device": (_I, [_P, _I, _I, _DP, _IP, _I, _P, _I, _P]),
@@ -507,6 +523,61 @@ def make_config(*, num_samples, horizon, method, parametrization, num_splines=2,
     for i in range(3):
         cfg.sigma_random_sampling[i] = float(np.float32(sigma_random_sampling[i]))
     return cfg
+
+
+def make_env_params(E, cfg: SrbdConfig, *, mass=None, inertia=None, mu=None, grf_min=None, grf_max=None,
+                    q_diag=None) -> np.ndarray:
+    """E srbd_env_params records (an ``ENV_PARAMS_DTYPE`` array) for ``BatchContext.set_env_params``: every field
+    starts from ``cfg``'s value, and each keyword given replaces it with a scalar (or one inertia (9,) / (3, 3), one
+    q_diag (24,)) for every environment, or a length-E array of them.  The fields are rounded as ``make_config`` rounds
+    them: with ``mass`` given, mg = float32(float64(mass) * 9.81), and grf_max, unless given, that same product per
+    environment."""
+    E = int(E)
+    p = np.zeros(E, ENV_PARAMS_DTYPE)
+    p["mass"], p["mg"], p["grf_min"], p["grf_max"], p["mu"] = cfg.mass, cfg.mg, cfg.grf_min, cfg.grf_max, cfg.mu
+    p["inertia"] = np.array(cfg.inertia[:], np.float32)
+    p["q_diag"] = np.array(cfg.q_diag[:], np.float32)
+
+    def per_env(name, v, shape):
+        a = np.asarray(v, dtype=np.float64)
+        if shape == (9,) and a.shape[-2:] == (3, 3):
+            a = a.reshape(a.shape[:-2] + (9,))
+        if a.shape == shape:
+            a = np.broadcast_to(a, (E,) + shape)
+        if a.shape != (E,) + shape:
+            raise ValueError(f"{name} must be {shape or 'a scalar'} or ({E},) + {shape}, got {np.shape(v)}")
+        return a
+
+    if mass is not None:
+        m = per_env("mass", mass, ())
+        p["mass"] = m.astype(np.float32)
+        p["mg"] = (m * 9.81).astype(np.float32)
+        if grf_max is None:
+            p["grf_max"] = (m * 9.81).astype(np.float32)
+    if grf_max is not None:
+        p["grf_max"] = per_env("grf_max", grf_max, ()).astype(np.float32)
+    if grf_min is not None:
+        p["grf_min"] = per_env("grf_min", grf_min, ()).astype(np.float32)
+    if mu is not None:
+        p["mu"] = per_env("mu", mu, ()).astype(np.float32)
+    if inertia is not None:
+        p["inertia"] = per_env("inertia", inertia, (9,)).astype(np.float32)
+    if q_diag is not None:
+        p["q_diag"] = per_env("q_diag", q_diag, (24,)).astype(np.float32)
+    return p
+
+
+def config_with_env_params(cfg: SrbdConfig, rec) -> SrbdConfig:
+    """A copy of ``cfg`` with the seven robot and cost fields replaced by one ``ENV_PARAMS_DTYPE`` record: the
+    configuration whose plain ``Context`` an environment with these parameters equals."""
+    out = SrbdConfig.from_buffer_copy(cfg)
+    out.mass, out.mg, out.grf_min, out.grf_max, out.mu = (float(rec[k]) for k in ("mass", "mg", "grf_min", "grf_max",
+                                                                                    "mu"))
+    for i in range(9):
+        out.inertia[i] = float(rec["inertia"][i])
+    for i in range(24):
+        out.q_diag[i] = float(rec["q_diag"][i])
+    return out
 
 
 def jax_prng_key(seed: int) -> np.ndarray:
@@ -969,6 +1040,82 @@ class BatchContext:
             raise ValueError(f"r_force must have 3 entries, got shape {r.shape}")
         self.check(lib.srbd_batch_set_cost_terms(self.h, fptr(r), float(w_smooth), float(w_cone)),
                    "srbd_batch_set_cost_terms")
+
+    # ---- per-environment robot and cost parameters (srbd_batch_set_env_params, include/srbd_mpc.h)
+    def _env_records(self, params):
+        p = np.ascontiguousarray(params)
+        if p.dtype != ENV_PARAMS_DTYPE:
+            raise ValueError(f"params must be an ENV_PARAMS_DTYPE array (make_env_params), got dtype {p.dtype}")
+        if p.shape != (self.E,):
+            raise ValueError(f"params must be ({self.E},), got {p.shape}")
+        return p
+
+    def set_env_params(self, params, mask=None):
+        """srbd_batch_set_env_params: params an (E,) ``ENV_PARAMS_DTYPE`` array (``make_env_params``); mask None or (E,)
+        booleans, False keeping an environment's parameters.  Holds for every following step until changed or
+        cleared; environment e then equals a ``Context`` of ``config_with_env_params(cfg, params[e])``."""
+        p = self._env_records(params)
+        m = None
+        if mask is not None:
+            m = np.ascontiguousarray(np.asarray(mask).astype(bool), dtype=np.uint8)
+            if m.shape != (self.E,):
+                raise ValueError(f"mask must be ({self.E},), got {m.shape}")
+        self.check(lib.srbd_batch_set_env_params(self.h, p.ctypes.data, None if m is None else m.ctypes.data),
+                   "srbd_batch_set_env_params")
+
+    def check_env_params_device(self, params, mask=None, rejected=None):
+        """The argument checks of ``set_env_params_device`` (ValueError; nothing is enqueued); returns the device."""
+        import torch
+
+        E = self.E
+        dev = torch.device("cuda", self.cfg.device_id)
+        if not isinstance(params, torch.Tensor):
+            raise ValueError(f"params must be a torch tensor, got {type(params).__name__}")
+        if params.dtype == torch.uint8:
+            shape = (E, ENV_PARAMS_DTYPE.itemsize)
+        elif params.dtype == torch.float32:
+            shape = (E, ENV_PARAMS_FLOATS)
+        else:
+            raise ValueError(f"params must be torch.uint8 or torch.float32, got {params.dtype}")
+        specs = [("params", params, shape, (params.dtype,))]
+        if mask is not None:
+            specs.append(("mask", mask, (E,), (torch.int32,)))
+        if rejected is not None:
+            specs.append(("rejected", rejected, (E,), (torch.int32,)))
+        _device_tensors(specs)
+        for name, t, _, _ in specs:
+            if t.device != dev:
+                raise ValueError(f"{name} must be on {dev}, got {t.device}")
+            if t.data_ptr() % 4:
+                raise ValueError(f"{name} must be 4-byte aligned")
+        return dev
+
+    def set_env_params_device(self, params, mask=None, rejected=None, stream=None):
+        """srbd_batch_set_env_params_device: ``set_env_params`` from torch tensors of the context's device, one launch
+        enqueued on ``stream`` (None: ``torch.cuda.current_stream()``) without a host synchronisation.  params: the E
+        records as (E, 156) uint8 or (E, 39) float32 (``torch.from_numpy(make_env_params(...).view(np.float32)
+        .reshape(E, 39))``); mask None or (E,) int32 (``BatchedLoopReset``'s mask: non-zero re-draws the robot), a
+        masked-out record is not read; rejected None or (E,) int32, written 1 where a selected record fails the
+        checks (that environment keeps its parameters) and 0 elsewhere."""
+        import torch
+
+        dev = self.check_env_params_device(params, mask, rejected)
+        s = torch.cuda.current_stream(dev) if stream is None else stream
+        self.check(lib.srbd_batch_set_env_params_device(
+            self.h, params.data_ptr(), None if mask is None else mask.data_ptr(),
+            None if rejected is None else rejected.data_ptr(), C.c_void_p(s.cuda_stream or 1)),
+            "srbd_batch_set_env_params_device")
+
+    def get_env_params(self) -> np.ndarray:
+        """srbd_batch_get_env_params: every environment's parameters as set (the configuration's where never set), an
+        (E,) ``ENV_PARAMS_DTYPE`` array; waits for the last device call."""
+        out = np.zeros(self.E, ENV_PARAMS_DTYPE)
+        self.check(lib.srbd_batch_get_env_params(self.h, out.ctypes.data), "srbd_batch_get_env_params")
+        return out
+
+    def clear_env_params(self):
+        """srbd_batch_clear_env_params: every environment back to the configuration's values."""
+        self.check(lib.srbd_batch_clear_env_params(self.h), "srbd_batch_clear_env_params")
 
     def step(self, states, refs, contacts, best, noise=None, seeds=None, counters=None, want_costs=False):
         """One step of every environment: states / refs (E, 24), contacts (E, 4, >=H), best (E, P), noise None or

@@ -89,6 +89,21 @@ class Batched_Sampling_MPC:
         """srbd_batch_set_cost_terms for every environment (all 0: the reference's cost)."""
         self.context.set_cost_terms(r_force, w_smooth, w_cone)
 
+    def set_robot_parameters(self, *, mass=None, inertia=None, mu=None, grf_min=None, grf_max=None, q_diag=None,
+                             mask=None):
+        """Per-environment robot and cost parameters for every following step (srbd_batch_set_env_params): each
+        keyword a scalar or a length-E array, as ``_lib.make_env_params`` takes them; fields not given keep the
+        configuration's value.  mask None or (E,) booleans: False keeps an environment's current parameters.
+        Environment e then returns what a ``Sampling_MPC`` of that robot returns, bit for bit.  The gait-adaptive and
+        CEM classes inherit it."""
+        ctx = self.context
+        ctx.set_env_params(_lib.make_env_params(self.num_envs, ctx.cfg, mass=mass, inertia=inertia, mu=mu,
+                                                grf_min=grf_min, grf_max=grf_max, q_diag=q_diag), mask)
+
+    def clear_robot_parameters(self):
+        """Every environment back to the configuration's robot (srbd_batch_clear_env_params)."""
+        self.context.clear_env_params()
+
     def with_newkey(self):
         """Every environment's key advanced as Sampling_MPC.with_newkey advances its stream's."""
         one = self._one
