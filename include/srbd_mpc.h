@@ -1048,6 +1048,83 @@ int srbd_gait_apply_freq_device(struct srbd_pgg* d_pgg, struct srbd_frg* d_frg, 
                                 int32_t num_envs, const int32_t* d_optimize, const float* d_best_freq,
                                 void* hip_stream);
 
+/* ---- The controller interface's step of the batched loop, device-resident: the sampling branch of
+ * SRBDControllerInterface.compute_control (quadruped_pympc/interfaces/srbd_controller_interface.py:113-180, :225-229;
+ * SCI below) for every environment of a batch in one call -- the batch form of srbd_interface_step above, statement for
+ * statement: prepare_state_and_reference (SCI:118-126), then per sampling iteration with_newkey (SCI:128, NMPC:498-501),
+ * CEM's with_newsigma(sigma_cem_mppi) at iteration 0 (SCI:129-130) and the step (SCI:131-168), then the footholds from
+ * the reference (SCI:170-175), the GRFs times current_contact (SCI:225-229) and previous_contact_mpc = current_contact.
+ *   Batches: one from srbd_batch_create (MPPI or random sampling; io->gait NULL, or the gait setting of this control
+ *   step, enqueued once ahead of the iterations as srbd_batch_set_gait_device enqueues it) and one from
+ *   srbd_batch_create_cem (io->gait must be NULL; io->sigma required).  The batch's rng (srbd_batch_set_rng) selects the
+ *   key rule; the cost terms and per-environment parameters set on the batch apply as they do to any step.
+ *   Keys: keys[e] = (key[0], key[1]) with srbd_interface_io::key's meaning.  Per iteration, as srbd_interface_step:
+ *     SRBD_RNG_PHILOX        key[1] += 1 (uint64, wrapping); the step runs (key[0], key[1])
+ *     SRBD_RNG_JAX[_LEGACY]  key[0] = split(key[0])[0] in the stream's counter layout, key[1] += 1 (the call count);
+ *                            the step runs (key[0], key[1])
+ *   The prologue writes the `iterations` step keys of every environment into an array the batch owns (allocated at
+ *   create for SRBD_MAX_IFACE_ITERS rows, each row E seeds then E counters: the unit-stride arrays the step reads) and
+ *   the advanced key back to keys[e].  srbd_selftest_interface_keys runs the same function on the host.
+ *   Launches: one prologue launch (one lane per (environment, leg) runs srbd_prepare_state_device's body with
+ *   current_contact read from column 0 of contacts; the leg-0 lane of an environment runs its key schedule), then
+ *   srbd_batch_set_gait_device's launch when io->gait is given, then `iterations` times the five launches of
+ *   srbd_batch_step_device / srbd_batch_step_cem_device (iteration i reads row i of the key array; the CEM form gets
+ *   sigma_reset at i == 0 and 0 afterwards), then one epilogue launch (one lane per (environment, leg)):
+ *   grf[e][3 l + c] = (double)grf_raw[e][3 l + c] * (double)contacts[e][l][0], float64 and unfused (srbd_host.cpp's
+ *   mask line); footholds[e][3 l + c] = ref_in[e][12 + 3 l + c]; previous_contact[e][l] = contacts[e][l][0].  No
+ *   other launch or copy is enqueued.  contacts is only read, and read in stream order: the epilogue sees the column the prologue saw
+ *   as long as the caller rewrites contacts by later work on the stream (or after the call has completed), never by
+ *   work on another stream or from the host while the call is in flight.
+ *   Outputs: states / refs (prepare_state's outputs as the step stages them, float32), grf (masked, float64),
+ *   footholds, and the last iteration's srbd_batch_device_io outputs (grf_raw is its unmasked grf); best_params, sigma,
+ *   keys and previous_contact are updated in place.  Only the last iteration's outputs are returned, as the reference
+ *   keeps only the last.
+ *   Equivalence: environment e afterwards holds, byte for byte, what srbd_interface_step leaves on a context
+ *   srbd_create(cfg) with the same rng, state_in, ref_in, contact columns, key, previous contact, warm start (and
+ *   sigma_reset): state_out / ref_out rounded to float32, grf, key, best_params, sigma, the last srbd_result; with
+ *   io->gait, what srbd_batch_set_gait_device + `iterations` x srbd_batch_step_device with keys advanced by the rule
+ *   above + the mask leave.  Environments are independent.
+ *   Contracts: the enqueue contract, the stream handle (NULL: the batch's own stream; hipStreamLegacy: the legacy null
+ *   stream), the event protocol and "no synchronising HIP call, no host touch of device memory" are
+ *   srbd_batch_step_device's.  The batch's event is recorded behind the epilogue as well, so a following call on
+ *   another stream, which waits on it, follows this call's stores of keys, best_params, sigma and previous_contact --
+ *   the in / out state that lives between calls; every other caller-owned array is ordered across streams by the
+ *   caller, as for srbd_batch_step_device.  Capturing the call into a HIP graph is not supported.  The arrays must not
+ *   overlap.
+ *   SRBD_E_INVALID (with a message, before anything is enqueued, nothing changed): b or io NULL; a required pointer
+ *   NULL (every pointer but gait, costs and -- off a CEM batch -- sigma); iterations outside 1..SRBD_MAX_IFACE_ITERS;
+ *   contact_stride < H; params_per_leg < 1 or 4 * params_per_leg != P; on a CEM batch sigma NULL, sigma_reset not
+ *   positive and finite, or gait given; gait together with active cost terms; and every refusal srbd_batch_set_gait_device
+ *   and the step make.
+ *   srbd_selftest_interface_keys: the key schedule on the host, for n keys: keys_io (n x 2, in / out) advanced
+ *   `iterations` times by the rule of `rng` (SRBD_RNG_*); step_keys (iterations x n x 2) receives the (seed, counter)
+ *   pair each iteration's step runs.  SRBD_E_INVALID: a NULL pointer, n < 1, rng not an SRBD_RNG_* value, iterations
+ *   outside 1..SRBD_MAX_IFACE_ITERS.  No device is needed. */
+#define SRBD_MAX_IFACE_ITERS 8
+typedef struct srbd_batch_interface_io {
+    /* inputs, device memory of the batch's device */
+    const double* state_in;        /* E x 24, srbd_prepare_state's layout */
+    const double* ref_in;          /* E x 24 */
+    const float*  contacts;        /* E x 4 x contact_stride; first H columns used; column 0 = current_contact */
+    int32_t contact_stride, iterations;   /* iterations = num_sampling_iterations, 1..SRBD_MAX_IFACE_ITERS */
+    int32_t params_per_leg, pad;
+    const srbd_batch_gait_io* gait;       /* host struct of device pointers, or NULL (plain / CEM batch) */
+    /* state, in / out, device memory, caller-owned */
+    uint64_t* keys;                /* E x 2, srbd_interface_io::key's meaning for the batch's rng */
+    float*    previous_contact;    /* E x 4: previous_contact_mpc; ones at start; out: this call's current_contact */
+    float*    best_params;         /* E x P */
+    float*    sigma;               /* E x P, CEM batch only (else NULL) */
+    float     sigma_reset; int32_t pad2;  /* CEM: mpc_params['sigma_cem_mppi'], > 0 */
+    /* outputs */
+    float*  states; float* refs;   /* E x 24: prepare_state's outputs as the step stages them */
+    double* grf;                   /* E x 12: last iteration's GRFs times current_contact, float64 */
+    double* footholds;             /* E x 12: ref_in's feet (SCI:170-175) */
+    float* grf_raw; float* predicted_state; float* best_cost; int32_t* best_index;
+    float* best_freq; int32_t* status; float* costs;   /* the last iteration's, as srbd_batch_device_io; costs may be NULL */
+} srbd_batch_interface_io;
+int srbd_batch_interface_step_device(srbd_batch* b, const srbd_batch_interface_io* io, void* hip_stream);
+int srbd_selftest_interface_keys(uint64_t* keys_io, int32_t n, int32_t rng, int32_t iterations, uint64_t* step_keys);
+
 /* ---- Restarting single environments of the batched loop, device-resident: the episode's end of the reference's
  * simulation loop (simulation/simulation.py:773-781: on is_terminated, is_truncated or the step limit, env.reset and
  * quadrupedpympc_wrapper.reset(initial_feet_pos), which reaches WBInterface.reset, quadruped_pympc/interfaces/

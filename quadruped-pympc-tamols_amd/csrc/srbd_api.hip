@@ -2698,6 +2698,9 @@ struct srbd_batch {
     std::vector<EnvModel> h_env;
     bool env_on = false;
     bool env_host_stale = false;
+    // srbd_batch_interface_step_device: the step keys its prologue writes and its iterations' steps read,
+    // SRBD_MAX_IFACE_ITERS rows of 2 E words (row i: E seeds, then E counters)
+    uint64_t* d_iface_keys = nullptr;
 };
 
 // The internal buffers (d_in, d_noise, d_rec, d_costs, d_count, d_ga_freq) are shared by the host path and the device
@@ -2752,6 +2755,7 @@ extern "C" void srbd_batch_destroy(srbd_batch* b) {
     (void)hipFree(b->d_ga_freq);
     (void)hipFree(b->d_env_raw);
     (void)hipFree(b->d_env);
+    (void)hipFree(b->d_iface_keys);
     if (b->h_in) (void)hipHostFree(b->h_in);
     if (b->h_out) (void)hipHostFree(b->h_out);
     if (b->c.h_flag) (void)hipHostFree(b->c.h_flag);
@@ -2848,6 +2852,8 @@ static int batch_create(const srbd_config* cfg, int32_t num_envs, srbd_batch** o
         return cleanup_fail("hipMalloc", e);
     if ((e = hipMalloc((void**)&b->d_env, sizeof(EnvModel) * E)) != hipSuccess) return cleanup_fail("hipMalloc", e);
     if ((e = batch_env_reset(b)) != hipSuccess) return cleanup_fail("hipMemcpy", e);
+    if ((e = hipMalloc((void**)&b->d_iface_keys, sizeof(uint64_t) * 2 * E * SRBD_MAX_IFACE_ITERS)) != hipSuccess)
+        return cleanup_fail("hipMalloc", e);
     // the noise padding rows (n_local .. ldn) stay zero, as in a single context
     if ((e = hipMemsetAsync(b->d_noise, 0, noise_bytes, b->c.stream)) != hipSuccess ||
         (e = hipMemsetAsync(b->d_in, 0, sizeof(StepInput) * E, b->c.stream)) != hipSuccess ||
@@ -2934,7 +2940,8 @@ extern "C" int srbd_batch_set_gait(srbd_batch* b, const float* timings, float pg
 // batch_set_gait_kernel writes d_in[e]'s gait fields as fill_gait writes the staging's (the same stores,
 // srbd_gait_adapt.h) and copies the injected rows.  No synchronising call: the launch joins the device steps' event
 // protocol, so it follows the last device step's reads of d_in and d_ga_freq and the next device step follows it.
-extern "C" int srbd_batch_set_gait_device(srbd_batch* b, const srbd_batch_gait_io* io, void* hip_stream) {
+// Its refusals, which srbd_batch_interface_step_device makes too before it enqueues anything
+static int batch_gait_dev_check(srbd_batch* b, const srbd_batch_gait_io* io) {
     srbd_ctx* c = b ? &b->c : nullptr;
     if (!io) return fail(c, SRBD_E_INVALID, "srbd_batch_set_gait_device: null io");
     if (!io->optimize) return fail(c, SRBD_E_INVALID, "srbd_batch_set_gait_device: null required pointer: optimize");
@@ -2945,7 +2952,7 @@ extern "C" int srbd_batch_set_gait_device(srbd_batch* b, const srbd_batch_gait_i
     if (io->n_freq < 1 || io->n_freq > SRBD_MAX_FREQS)
         return fail(c, SRBD_E_INVALID, "n_freq must be in [1, " + std::to_string(SRBD_MAX_FREQS) + "]");
     if (!b) return fail(nullptr, SRBD_E_INVALID, "srbd_batch_set_gait_device: null batch");
-    ModelConst& mc = c->mc;
+    const ModelConst& mc = c->mc;
     if (mc.method == SRBD_CEM_MPPI)
         return fail(c, SRBD_E_INVALID,
                     "gait-adaptive CEM is not provided (the reference's branch is broken as wired, SURVEY App. B #2)");
@@ -2954,6 +2961,14 @@ extern "C" int srbd_batch_set_gait_device(srbd_batch* b, const srbd_batch_gait_i
         return fail(c, SRBD_E_INVALID,
                     "gait-adaptive sampling with the opt-in cost terms has no batch form (one context runs it on its "
                     "thread-per-sample kernel): clear the cost weights first, or use separate contexts");
+    return SRBD_OK;
+}
+
+extern "C" int srbd_batch_set_gait_device(srbd_batch* b, const srbd_batch_gait_io* io, void* hip_stream) {
+    const int rc = batch_gait_dev_check(b, io);
+    if (rc != SRBD_OK) return rc;
+    srbd_ctx* c = &b->c;
+    ModelConst& mc = c->mc;
     HIP_TRY(c, hipSetDevice(c->cfg.device_id));
     hipStream_t s = (hipStream_t)hip_stream;  // as srbd_batch_step_device reads it
     if (!s) s = c->stream;
@@ -3230,8 +3245,9 @@ extern "C" int srbd_batch_step_cem(srbd_batch* b, const float* states, const flo
 // not waited on.  No synchronising call: the event behind the last launch orders the other entry points after it.
 // srbd_batch_step_device (cem NULL, is_cem false) and srbd_batch_step_cem_device: batch_pack_cem_kernel also writes
 // d_in[e].sigma (the caller's rows or the reset constant) and batch_unpack_cem_kernel also scatters d_out[e].sigma.
-static int batch_step_dev(srbd_batch* b, const srbd_batch_device_io* io, const srbd_batch_cem_io* cem, bool is_cem,
-                          void* hip_stream) {
+// Its refusals, which srbd_batch_interface_step_device makes too before it enqueues anything
+static int batch_step_dev_check(srbd_batch* b, const srbd_batch_device_io* io, const srbd_batch_cem_io* cem,
+                                bool is_cem) {
     // the arguments first, so a bad io is named as such whatever b is (b == NULL: the calling thread's error text)
     srbd_ctx* c = b ? &b->c : nullptr;
     const std::string fn = is_cem ? "srbd_batch_step_cem_device" : "srbd_batch_step_device";
@@ -3264,6 +3280,15 @@ static int batch_step_dev(srbd_batch* b, const srbd_batch_device_io* io, const s
         return fail(c, SRBD_E_INVALID, fn + ": not a CEM batch (srbd_batch_create_cem)");
     if (io->contact_stride < mc.H)
         return fail(c, SRBD_E_INVALID, fn + ": contact_stride is smaller than the horizon");
+    return SRBD_OK;
+}
+
+static int batch_step_dev(srbd_batch* b, const srbd_batch_device_io* io, const srbd_batch_cem_io* cem, bool is_cem,
+                          void* hip_stream) {
+    const int rc = batch_step_dev_check(b, io, cem, is_cem);
+    if (rc != SRBD_OK) return rc;
+    srbd_ctx* c = &b->c;
+    const ModelConst& mc = c->mc;
     HIP_TRY(c, hipSetDevice(c->cfg.device_id));
     // NULL is the batch's own stream, so the null stream goes by its explicit handle (handed on as the null stream)
     hipStream_t s = (hipStream_t)hip_stream;
@@ -3305,4 +3330,100 @@ extern "C" int srbd_batch_step_device(srbd_batch* b, const srbd_batch_device_io*
 extern "C" int srbd_batch_step_cem_device(srbd_batch* b, const srbd_batch_device_io* io, const srbd_batch_cem_io* cem,
                                           void* hip_stream) {
     return batch_step_dev(b, io, cem, true, hip_stream);
+}
+
+// SRBDControllerInterface.compute_control's sampling branch (srbd_controller_interface.py:113-180, :225-229) for every
+// environment of a batch, enqueued on the caller's stream: srbd_interface_step (srbd_host.cpp) statement for statement.
+// The prologue launch is its prepare_state and its with_newkey of every iteration (the step keys go to d_iface_keys,
+// one row per iteration); the iterations are srbd_batch_step_device / _step_cem_device as they are, reading their row
+// (the CEM form with sigma_reset at iteration 0: with_newsigma); the epilogue launch is the mask, the footholds and
+// previous_contact_mpc.  Every refusal -- this call's, the gait setter's and the step's -- is made before the first
+// launch, so a refused call has changed nothing.  The step keys are read by the steps' pack launches only, which the
+// event protocol of the steps already orders against a call on another stream; the prologue joins it here, and the
+// event is recorded once more behind the epilogue, so a call on another stream also follows the epilogue's store of
+// previous_contact, the one caller-owned array that is state between calls.
+extern "C" int srbd_batch_interface_step_device(srbd_batch* b, const srbd_batch_interface_io* io, void* hip_stream) {
+    srbd_ctx* c = b ? &b->c : nullptr;
+    const std::string fn = "srbd_batch_interface_step_device";
+    if (!b) return fail(nullptr, SRBD_E_INVALID, fn + ": null batch");
+    if (!io) return fail(c, SRBD_E_INVALID, fn + ": null io");
+    const ModelConst& mc = c->mc;
+    const bool is_cem = mc.method == SRBD_CEM_MPPI;
+    {
+        const struct {
+            const void* p;
+            const char* name;
+        } req[] = {{io->state_in, "state_in"},
+                   {io->ref_in, "ref_in"},
+                   {io->contacts, "contacts"},
+                   {io->keys, "keys"},
+                   {io->previous_contact, "previous_contact"},
+                   {io->best_params, "best_params"},
+                   {io->states, "states"},
+                   {io->refs, "refs"},
+                   {io->grf, "grf"},
+                   {io->footholds, "footholds"},
+                   {io->grf_raw, "grf_raw"},
+                   {io->predicted_state, "predicted_state"},
+                   {io->best_cost, "best_cost"},
+                   {io->best_index, "best_index"},
+                   {io->best_freq, "best_freq"},
+                   {io->status, "status"}};
+        for (const auto& r : req)
+            if (!r.p) return fail(c, SRBD_E_INVALID, fn + ": null required pointer: " + r.name);
+    }
+    if (is_cem && !io->sigma) return fail(c, SRBD_E_INVALID, fn + ": null required pointer: sigma (a CEM batch)");
+    if (io->iterations < 1 || io->iterations > SRBD_MAX_IFACE_ITERS)
+        return fail(c, SRBD_E_INVALID, fn + ": iterations must be in [1, " + std::to_string(SRBD_MAX_IFACE_ITERS) + "]");
+    if (io->contact_stride < mc.H) return fail(c, SRBD_E_INVALID, fn + ": contact_stride is smaller than the horizon");
+    if (io->params_per_leg < 1 || (int64_t)4 * io->params_per_leg != mc.P)
+        return fail(c, SRBD_E_INVALID,
+                    fn + ": params_per_leg must be >= 1 and 4 * params_per_leg the batch's " + std::to_string(mc.P) +
+                        " parameters");
+    if (is_cem && !(io->sigma_reset > 0.0f && io->sigma_reset < INFINITY))
+        return fail(c, SRBD_E_INVALID, fn + ": sigma_reset must be positive and finite on a CEM batch");
+    if (is_cem && io->gait)
+        return fail(c, SRBD_E_INVALID, fn + ": gait on a CEM batch (gait-adaptive CEM is not provided)");
+    if (io->gait && mc.cost_on)
+        return fail(c, SRBD_E_INVALID,
+                    fn + ": gait together with active cost terms (gait-adaptive sampling with the opt-in cost terms "
+                         "has no batch form)");
+    int rc;
+    if (io->gait && (rc = batch_gait_dev_check(b, io->gait)) != SRBD_OK) return rc;
+    srbd_batch_device_io sio = {};
+    sio.states = io->states, sio.refs = io->refs, sio.contacts = io->contacts;
+    sio.seeds = b->d_iface_keys, sio.counters = b->d_iface_keys + b->E;
+    sio.contact_stride = io->contact_stride;
+    sio.best_params = io->best_params;
+    sio.grf = io->grf_raw, sio.predicted_state = io->predicted_state, sio.best_cost = io->best_cost;
+    sio.best_index = io->best_index, sio.best_freq = io->best_freq, sio.status = io->status, sio.costs = io->costs;
+    srbd_batch_cem_io cem = {io->sigma, io->sigma_reset, 0};
+    if ((rc = batch_step_dev_check(b, &sio, is_cem ? &cem : nullptr, is_cem)) != SRBD_OK) return rc;
+    HIP_TRY(c, hipSetDevice(c->cfg.device_id));
+    hipStream_t s = (hipStream_t)hip_stream;  // as srbd_batch_step_device reads it
+    if (!s) s = c->stream;
+    else if (s == hipStreamLegacy) s = nullptr;
+    // the previous device call on another stream may still read d_iface_keys
+    if (b->dev_pending && b->dev_stream != s) HIP_TRY(c, hipStreamWaitEvent(s, b->dev_done, 0));
+    launch_iface_prologue(*io, mc.rng, mc.P, b->d_iface_keys, b->E, s);
+    HIP_TRY(c, hipGetLastError());  // the steps below record the event behind their launches
+    // the explicit handle again for the calls below: NULL would mean the batch's own stream to them
+    void* const hs = s ? (void*)s : (void*)hipStreamLegacy;
+    if (io->gait && (rc = srbd_batch_set_gait_device(b, io->gait, hs)) != SRBD_OK) return rc;
+    for (int it = 0; it < io->iterations; ++it) {
+        sio.seeds = b->d_iface_keys + 2 * (size_t)it * b->E;
+        sio.counters = sio.seeds + b->E;
+        cem.sigma_reset = it == 0 ? io->sigma_reset : 0.0f;
+        if ((rc = batch_step_dev(b, &sio, is_cem ? &cem : nullptr, is_cem, hs)) != SRBD_OK) return rc;
+    }
+    launch_iface_epilogue(*io, b->E, s);
+    // the event again, behind the epilogue: previous_contact lives between calls, so a following call on another
+    // stream, which waits on the event, must see the epilogue's store of it and not only the last step
+    const hipError_t le = hipGetLastError();
+    const hipError_t re = hipEventRecord(b->dev_done, s);
+    b->dev_stream = s;
+    b->dev_pending = re == hipSuccess;
+    HIP_TRY(c, le);
+    HIP_TRY(c, re);
+    return SRBD_OK;
 }

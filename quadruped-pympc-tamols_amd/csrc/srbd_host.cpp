@@ -16,6 +16,7 @@
 #include "../../include/srbd_mpc.h"
 #include "srbd_frg.h"
 #include "srbd_gait_adapt.h"
+#include "srbd_iface.h"
 #include "srbd_jaxrng.h"
 #include "srbd_reset.h"
 #include "srbd_stc.h"
@@ -594,5 +595,25 @@ extern "C" int srbd_interface_step(srbd_ctx* ctx, srbd_interface_io* io, const f
     }
     for (int l = 0; l < 4; ++l)
         for (int c = 0; c < 3; ++c) io->grf[3 * l + c] = (double)out->grf[3 * l + c] * io->current_contact[l];
+    return SRBD_OK;
+}
+
+// The key schedule of srbd_batch_interface_step_device's prologue kernel on the host (srbd_iface.h: the same function
+// the kernel runs; it is also the schedule of srbd_interface_step above), for the CPU tests.
+extern "C" int srbd_selftest_interface_keys(uint64_t* keys_io, int32_t n, int32_t rng, int32_t iterations,
+                                            uint64_t* step_keys) {
+    if (!keys_io || !step_keys || n < 1 || iterations < 1 || iterations > srbd::IFACE_MAX_ITERS) return SRBD_E_INVALID;
+    if (rng != SRBD_RNG_PHILOX && rng != SRBD_RNG_JAX && rng != SRBD_RNG_JAX_LEGACY) return SRBD_E_INVALID;
+    for (int32_t e = 0; e < n; ++e) {
+        uint64_t k0 = keys_io[2 * (size_t)e], k1 = keys_io[2 * (size_t)e + 1];
+        for (int32_t i = 0; i < iterations; ++i) {
+            srbd::iface_next_key(rng, k0, k1);
+            uint64_t* o = step_keys + 2 * ((size_t)i * n + e);
+            o[0] = k0;
+            o[1] = k1;
+        }
+        keys_io[2 * (size_t)e] = k0;
+        keys_io[2 * (size_t)e + 1] = k1;
+    }
     return SRBD_OK;
 }

@@ -374,6 +374,15 @@ struct LoopResetJob {
     float* rows[4];
     int32_t num_params, n_rows;
 };
+// The controller interface's step of a batch (srbd_batch_interface_step_device; srbd_producers.hip
+// iface_prologue_kernel, iface_epilogue_kernel), one lane per (environment, leg) each.  Prologue: prepare_state with
+// the current contact from column 0 of io.contacts, and environment e's io.iterations step keys (rule `rng`,
+// srbd_iface.h) into step_keys -- IFACE_MAX_ITERS rows of 2 E words, row i = E seeds then E counters -- with the
+// advanced key back in io.keys.  Epilogue: io.grf = io.grf_raw x current contact (float64), io.footholds from
+// io.ref_in, io.previous_contact = current contact.
+void launch_iface_prologue(const srbd_batch_interface_io& io, int rng, int num_params, uint64_t* step_keys, int E,
+                           hipStream_t s);
+void launch_iface_epilogue(const srbd_batch_interface_io& io, int E, hipStream_t s);
 // srbd_api.hip: the calling thread's error text (srbd_last_error(NULL)) for an entry point that has no handle.
 int fail_global(int code, const char* message);
 

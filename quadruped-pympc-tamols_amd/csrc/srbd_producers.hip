@@ -35,6 +35,11 @@
 // same job with the gate's four fields, the same grid, the kernel's gated instantiation.
 // loop_reset_kernel (srbd_loop_reset_device) restarts the environments a mask names (srbd_reset.h; simulation/
 // simulation.py:773-781, wb_interface.py:469-484): one wave per environment, see the kernel.
+// iface_prologue_kernel and iface_epilogue_kernel are the two launches srbd_batch_interface_step_device (srbd_api.hip)
+// puts around its sampling iterations (SCI = quadruped_pympc/interfaces/srbd_controller_interface.py:113-180,
+// :225-229): prepare_state through the device function prepare_state_kernel runs and the key schedule of
+// srbd_iface.h ahead of them; the GRFs times the current contact, the footholds and previous_contact_mpc behind them.
+// One lane per (environment, leg), no cross-lane traffic.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -45,6 +50,7 @@
 #include "../../include/srbd_mpc.h"
 #include "srbd_frg.h"
 #include "srbd_gait_adapt.h"
+#include "srbd_iface.h"
 #include "srbd_launch.h"
 #include "srbd_reset.h"
 #include "srbd_stc.h"
@@ -138,8 +144,35 @@ __global__ void __launch_bounds__(PROD_BLOCK) pgg_contact_sequence_kernel(srbd_p
     if (ini0 != (ini0 != 0)) g->init[l] = 1;
 }
 
-// Lane (e, l) copies the base entries 3 l .. 3 l + 2 and foot l of state and reference, and zeroes leg l's warm start
-// when it lifts off.
+// One leg's srbd_prepare_state: lane (e, l) copies the base entries 3 l .. 3 l + 2 and foot l of state and reference,
+// and zeroes leg l's warm start when it lifts off.  cur, prev: the leg's current and previous contact flags (the
+// previous one is read only for a swing leg with a warm start).
+__device__ __forceinline__ void prepare_state_leg(int e, int l, const float* __restrict__ cur,
+                                                  const float* __restrict__ prev,
+                                                  const double* __restrict__ state_in,
+                                                  const double* __restrict__ ref_in, int params_per_leg,
+                                                  int num_params, float* __restrict__ best_params,
+                                                  float* __restrict__ states, float* __restrict__ refs) {
+    const double* __restrict__ si = state_in + 24 * (size_t)e;
+    const double* __restrict__ ri = ref_in + 24 * (size_t)e;
+    float* __restrict__ so = states + 24 * (size_t)e;
+    float* __restrict__ ro = refs + 24 * (size_t)e;
+    const bool swing = (double)*cur == 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int b = 3 * l + k, f = 12 + 3 * l + k;
+        so[b] = (float)si[b];
+        ro[b] = (float)ri[b];
+        const double rf = ri[f];
+        so[f] = (float)(swing ? rf : si[f]);
+        ro[f] = (float)rf;
+    }
+    if (best_params && swing && (double)*prev == 1.0) {
+        float* __restrict__ bp = best_params + (size_t)e * num_params + (size_t)l * params_per_leg;
+        for (int j = 0; j < params_per_leg; ++j) bp[j] = 0.0f;
+    }
+}
+
 __global__ void __launch_bounds__(PROD_BLOCK) prepare_state_kernel(int E, const double* __restrict__ state_in,
                                                                    const double* __restrict__ ref_in,
                                                                    const float* __restrict__ current_contact,
@@ -150,25 +183,66 @@ __global__ void __launch_bounds__(PROD_BLOCK) prepare_state_kernel(int E, const 
                                                                    float* __restrict__ refs) {
     const int t = blockIdx.x * PROD_BLOCK + threadIdx.x;
     if (t >= 4 * E) return;
+    prepare_state_leg(t >> 2, t & 3, current_contact + t, previous_contact + t, state_in, ref_in, params_per_leg,
+                      num_params, best_params, states, refs);
+}
+
+// srbd_batch_interface_step_device's prologue (include/srbd_mpc.h; SCI:118-128): lane (e, l) runs prepare_state_leg
+// with the current contact read from column 0 of the contact sequence, and lane (e, 0) runs environment e's key
+// schedule (srbd_iface.h): keys[e] advanced `iterations` times, iteration i's (seed, counter) stored at step_keys
+// [i][0][e] and [i][1][e] -- the unit-stride seeds / counters rows iteration i's step reads -- and the advanced key
+// written back.  One lane is one environment's key, so every access here is a vector load or store.  No lane reads a
+// word another lane of the launch writes: previous_contact and contacts are only read, best_params is written per
+// leg, the key words per environment.
+struct IfaceJob {
+    const double *state_in, *ref_in;
+    const float *contacts, *previous_contact;
+    float *best_params, *states, *refs;
+    uint64_t *keys, *step_keys;
+    int32_t contact_stride, iterations, params_per_leg, num_params, rng;
+};
+__global__ void __launch_bounds__(PROD_BLOCK) iface_prologue_kernel(int E, const IfaceJob j) {
+    const int t = blockIdx.x * PROD_BLOCK + threadIdx.x;
+    if (t >= 4 * E) return;
     const int e = t >> 2, l = t & 3;
-    const double* __restrict__ si = state_in + 24 * (size_t)e;
-    const double* __restrict__ ri = ref_in + 24 * (size_t)e;
-    float* __restrict__ so = states + 24 * (size_t)e;
-    float* __restrict__ ro = refs + 24 * (size_t)e;
-    const bool swing = (double)current_contact[t] == 0.0;
+    prepare_state_leg(e, l, j.contacts + (size_t)t * j.contact_stride, j.previous_contact + t, j.state_in, j.ref_in,
+                      j.params_per_leg, j.num_params, j.best_params, j.states, j.refs);
+    if (l == 0) {
+        uint64_t k0 = j.keys[2 * (size_t)e], k1 = j.keys[2 * (size_t)e + 1];
+        for (int i = 0; i < j.iterations; ++i) {
+            iface_next_key(j.rng, k0, k1);
+            uint64_t* __restrict__ row = j.step_keys + 2 * (size_t)i * E;
+            row[e] = k0;
+            row[(size_t)E + e] = k1;
+        }
+        j.keys[2 * (size_t)e] = k0;
+        j.keys[2 * (size_t)e + 1] = k1;
+    }
+}
+
+// Its epilogue (SCI:170-175, :225-229, and previous_contact_mpc = current_contact): lane (e, l) masks leg l's GRFs of
+// the last iteration with the leg's current contact -- the float64 product of srbd_host.cpp's mask line, one rounding
+// and no fused operation -- copies the leg's reference foothold and stores the contact as the next call's previous
+// one.  The contact is read from the caller's sequence again: nothing between the prologue and here writes it.
+__global__ void __launch_bounds__(PROD_BLOCK) iface_epilogue_kernel(int E, const float* __restrict__ grf_raw,
+                                                                    const float* __restrict__ contacts,
+                                                                    int contact_stride,
+                                                                    const double* __restrict__ ref_in,
+                                                                    double* __restrict__ grf,
+                                                                    double* __restrict__ footholds,
+                                                                    float* __restrict__ previous_contact) {
+#pragma clang fp contract(off)
+    const int t = blockIdx.x * PROD_BLOCK + threadIdx.x;
+    if (t >= 4 * E) return;
+    const int e = t >> 2, l = t & 3;
+    const float cur = contacts[(size_t)t * contact_stride];
+    const double cd = (double)cur;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const int b = 3 * l + k, f = 12 + 3 * l + k;
-        so[b] = (float)si[b];
-        ro[b] = (float)ri[b];
-        const double rf = ri[f];
-        so[f] = (float)(swing ? rf : si[f]);
-        ro[f] = (float)rf;
+    for (int c = 0; c < 3; ++c) {
+        grf[3 * (size_t)t + c] = (double)grf_raw[3 * (size_t)t + c] * cd;
+        footholds[3 * (size_t)t + c] = ref_in[24 * (size_t)e + 12 + 3 * l + c];
     }
-    if (best_params && swing && (double)previous_contact[t] == 1.0) {
-        float* __restrict__ bp = best_params + (size_t)e * num_params + (size_t)l * params_per_leg;
-        for (int j = 0; j < params_per_leg; ++j) bp[j] = 0.0f;
-    }
+    previous_contact[t] = cur;
 }
 
 // The arrays of one srbd_frg_step_device call (srbd_frg_batch_io) and the values formed on the host.
@@ -529,6 +603,23 @@ extern "C" int srbd_prepare_state_device(int32_t num_envs, const double* d_state
                        num_envs, d_state_in, d_ref_in, d_current_contact, d_previous_contact, params_per_leg,
                        num_params, d_best_params, d_states, d_refs);
     return launch_status();
+}
+
+// srbd_batch_interface_step_device (srbd_api.hip, which owns the batch) enqueues its two launches through these.
+void srbd::launch_iface_prologue(const srbd_batch_interface_io& io, int rng, int num_params, uint64_t* step_keys, int E,
+                                 hipStream_t s) {
+    IfaceJob j = {};
+    j.state_in = io.state_in, j.ref_in = io.ref_in;
+    j.contacts = io.contacts, j.previous_contact = io.previous_contact;
+    j.best_params = io.best_params, j.states = io.states, j.refs = io.refs;
+    j.keys = io.keys, j.step_keys = step_keys;
+    j.contact_stride = io.contact_stride, j.iterations = io.iterations;
+    j.params_per_leg = io.params_per_leg, j.num_params = num_params, j.rng = rng;
+    hipLaunchKernelGGL(iface_prologue_kernel, dim3(blocks_of(E)), dim3(PROD_BLOCK), 0, s, E, j);
+}
+void srbd::launch_iface_epilogue(const srbd_batch_interface_io& io, int E, hipStream_t s) {
+    hipLaunchKernelGGL(iface_epilogue_kernel, dim3(blocks_of(E)), dim3(PROD_BLOCK), 0, s, E, io.grf_raw, io.contacts,
+                       io.contact_stride, io.ref_in, io.grf, io.footholds, io.previous_contact);
 }
 
 extern "C" int srbd_frg_step_device(srbd_frg* d_frg, int32_t num_envs, const srbd_frg_batch_io* io, void* hip_stream) {

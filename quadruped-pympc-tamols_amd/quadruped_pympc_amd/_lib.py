@@ -122,6 +122,21 @@ class BatchGaitIO(C.Structure):
     ]
 
 
+MAX_IFACE_ITERS = 8  # SRBD_MAX_IFACE_ITERS
+
+
+class BatchInterfaceIO(C.Structure):
+    """srbd_batch_interface_io (include/srbd_mpc.h): the device arrays of one srbd_batch_interface_step_device call."""
+    _fields_ = [
+        ("state_in", _P), ("ref_in", _P), ("contacts", _P), ("contact_stride", _I), ("iterations", _I),
+        ("params_per_leg", _I), ("pad", _I), ("gait", C.POINTER(BatchGaitIO)),
+        ("keys", _P), ("previous_contact", _P), ("best_params", _P), ("sigma", _P), ("sigma_reset", _F), ("pad2", _I),
+        ("states", _P), ("refs", _P), ("grf", _P), ("footholds", _P),
+        ("grf_raw", _P), ("predicted_state", _P), ("best_cost", _P), ("best_index", _P), ("best_freq", _P),
+        ("status", _P), ("costs", _P),
+    ]
+
+
 class TamolsBatchIO(C.Structure):
     """srbd_tamols_batch_io (include/srbd_mpc.h): the device arrays of one srbd_tamols_batch_device call."""
     _fields_ = [
@@ -389,6 +404,9 @@ SIGNATURES.update({
                              C.POINTER(SrbdTerrainEst), C.POINTER(SrbdVfa), C.POINTER(SrbdPgg), C.POINTER(SrbdFrg),
                              C.POINTER(SrbdStc), C.POINTER(SrbdTerrainEst), C.POINTER(SrbdVfa), _IP, _FP, _I]),
     "srbd_loop_reset_device": (_I, [_I, C.POINTER(SrbdLoopResetIo), _P]),
+    # the controller interface's step of a batch, and the host twin of its key schedule
+    "srbd_batch_interface_step_device": (_I, [_P, C.POINTER(BatchInterfaceIO), _P]),
+    "srbd_selftest_interface_keys": (_I, [_P, _I, _I, _I, _P]),
 })
 
 # srbd_time_launch kinds (include/srbd_mpc.h)
@@ -600,6 +618,18 @@ def pack_key(key) -> int:
     """The `seed` argument of srbd_step in a JAX stream mode: key[0] << 32 | key[1]."""
     k = np.asarray(key, np.uint32).reshape(2)
     return (int(k[0]) << 32) | int(k[1])
+
+
+def interface_keys_host(keys, rng, iterations: int):
+    """srbd_selftest_interface_keys: the key schedule of ``srbd_batch_interface_step_device`` on the host.  keys (n, 2)
+    uint64 -- (seed, counter) for 'philox', (packed JAX key, call count) for 'jax' / 'jax_legacy' -- advanced
+    ``iterations`` times -> (the advanced keys (n, 2), the step keys (iterations, n, 2) each iteration's step runs)."""
+    k = np.array(keys, dtype=np.uint64).reshape(-1, 2)
+    code = RNG_CODES[rng] if isinstance(rng, str) else int(rng)
+    steps = np.zeros((max(int(iterations), 0), k.shape[0], 2), np.uint64)
+    check(lib.srbd_selftest_interface_keys(k.ctypes.data, int(k.shape[0]), code, int(iterations), steps.ctypes.data),
+          None, "srbd_selftest_interface_keys")
+    return k, steps
 
 
 def num_params(cfg: SrbdConfig) -> int:
@@ -1000,6 +1030,19 @@ class BatchContext:
         not."""
         import torch
 
+        io = self.make_gait_io(optimize, available, pgg_dt, duty, pgg=pgg, timings=timings,
+                               nominal_freqs=nominal_freqs, freq_rows=freq_rows)
+        s = torch.cuda.current_stream(torch.device("cuda", self.cfg.device_id)) if stream is None else stream
+        # the null stream by its explicit handle, as in step_device
+        self.check(lib.srbd_batch_set_gait_device(self.h, C.byref(io), C.c_void_p(s.cuda_stream or 1)),
+                   "srbd_batch_set_gait_device")
+
+    def make_gait_io(self, optimize, available, pgg_dt: float, duty: float, *, pgg=None, timings=None,
+                     nominal_freqs=None, freq_rows=None) -> BatchGaitIO:
+        """The argument checks of ``set_gait_device`` (ValueError; nothing is enqueued) and its ``BatchGaitIO``, which
+        ``interface_step_device`` takes as ``gait_io``.  The struct holds raw addresses: keep the tensors alive."""
+        import torch
+
         E = self.E
         dev = torch.device("cuda", self.cfg.device_id)
         av = np.ascontiguousarray(available, dtype=np.float32).reshape(-1)
@@ -1027,10 +1070,7 @@ class BatchContext:
         io = BatchGaitIO(pgg=ptr(pgg), timings=ptr(timings), nominal_freqs=ptr(nominal_freqs), optimize=ptr(optimize),
                          freq_rows=ptr(freq_rows), available=(_F * MAX_FREQS)(*av.tolist()), n_freq=int(av.size),
                          pgg_dt=float(pgg_dt), duty_factor=float(duty), pad=0)
-        s = torch.cuda.current_stream(dev) if stream is None else stream
-        # the null stream by its explicit handle, as in step_device
-        self.check(lib.srbd_batch_set_gait_device(self.h, C.byref(io), C.c_void_p(s.cuda_stream or 1)),
-                   "srbd_batch_set_gait_device")
+        return io
 
     def set_cost_terms(self, r_force=(0.0, 0.0, 0.0), w_smooth: float = 0.0, w_cone: float = 0.0):
         """srbd_batch_set_cost_terms: the opt-in force regularisation / GRF smoothing / cone-violation terms for every
@@ -1229,6 +1269,71 @@ class BatchContext:
         # torch's default stream is the null stream, handle 0, which the C call reads as "the batch's own stream":
         # hand it on by its explicit handle (hipStreamLegacy)
         enqueue(io, C.c_void_p(s.cuda_stream or 1))
+        return out
+
+    def interface_step_device(self, state_in, ref_in, contacts, keys, previous_contact, best, *, iterations: int = 1,
+                              sigma=None, sigma_reset: float = 0.0, gait_io=None, want_costs=False, stream=None):
+        """srbd_batch_interface_step_device: ``SRBDControllerInterface.compute_control``'s sampling branch for every
+        environment, enqueued on ``stream`` (None: ``torch.cuda.current_stream()``) without a host synchronisation:
+        prepare_state, per sampling iteration the key schedule (and CEM's sigma reset at the first) and the device
+        step, then the contact mask.  Torch tensors of the context's device, contiguous:
+
+        state_in, ref_in (E, 24) float64; contacts (E, 4, >=H) float32, column 0 the current contact; keys (E, 2) int64
+        or uint64, in / out -- (seed, counter) for 'philox', (packed JAX key, call count) for the JAX streams;
+        previous_contact (E, 4) float32, in / out; best (E, P) float32, in / out; sigma (E, P) float32, in / out, a
+        CEM context only, with sigma_reset > 0 the constant the first iteration starts from; gait_io None or a
+        ``BatchGaitIO`` (``set_gait_device``'s arguments; not with a CEM context).
+
+        Returns a dict of freshly allocated tensors: states, refs (E, 24) float32 (prepare_state's outputs), grf
+        (E, 12) float64 masked, footholds (E, 12) float64, and the last iteration's grf_raw (E, 12), predicted_state
+        (E, 24), best_cost, best_freq (E,) float32, best_index, status (E,) int32, costs (E, N) with ``want_costs``."""
+        import torch
+
+        E, H, P, N = self.E, self.cfg.horizon, self.P, self.N
+        dev = torch.device("cuda", self.cfg.device_id)
+        keyt = (torch.int64, torch.uint64) if hasattr(torch, "uint64") else (torch.int64,)
+        f32_, f64 = (torch.float32,), (torch.float64,)
+        if not isinstance(contacts, torch.Tensor) or contacts.dim() != 3 or contacts.shape[2] < H:
+            raise ValueError(f"contacts must be a torch tensor of shape ({E}, 4, >={H})")
+        specs = [("state_in", state_in, (E, 24), f64), ("ref_in", ref_in, (E, 24), f64),
+                 ("contacts", contacts, (E, 4, int(contacts.shape[2])), f32_), ("keys", keys, (E, 2), keyt),
+                 ("previous_contact", previous_contact, (E, 4), f32_), ("best", best, (E, P), f32_)]
+        if sigma is not None:
+            specs.append(("sigma", sigma, (E, P), f32_))
+        _device_tensors(specs)
+        for name, t, _, _ in specs:
+            if t.device != dev:
+                raise ValueError(f"{name} must be on {dev}, got {t.device}")
+        if not 1 <= int(iterations) <= MAX_IFACE_ITERS:
+            raise ValueError(f"iterations must be in 1..{MAX_IFACE_ITERS}, got {iterations}")
+        s = torch.cuda.current_stream(dev) if stream is None else stream
+        with torch.cuda.stream(s):  # the outputs belong to the stream that writes them
+            out = {"states": torch.empty((E, 24), dtype=torch.float32, device=dev),
+                   "refs": torch.empty((E, 24), dtype=torch.float32, device=dev),
+                   "grf": torch.empty((E, 12), dtype=torch.float64, device=dev),
+                   "footholds": torch.empty((E, 12), dtype=torch.float64, device=dev),
+                   "grf_raw": torch.empty((E, 12), dtype=torch.float32, device=dev),
+                   "predicted_state": torch.empty((E, 24), dtype=torch.float32, device=dev),
+                   "best_cost": torch.empty(E, dtype=torch.float32, device=dev),
+                   "best_index": torch.empty(E, dtype=torch.int32, device=dev),
+                   "best_freq": torch.empty(E, dtype=torch.float32, device=dev),
+                   "status": torch.empty(E, dtype=torch.int32, device=dev)}
+            if want_costs:
+                out["costs"] = torch.empty((E, N), dtype=torch.float32, device=dev)
+        io = BatchInterfaceIO(
+            state_in=state_in.data_ptr(), ref_in=ref_in.data_ptr(), contacts=contacts.data_ptr(),
+            contact_stride=int(contacts.shape[2]), iterations=int(iterations), params_per_leg=P // 4, pad=0,
+            gait=None if gait_io is None else C.pointer(gait_io), keys=keys.data_ptr(),
+            previous_contact=previous_contact.data_ptr(), best_params=best.data_ptr(),
+            sigma=None if sigma is None else sigma.data_ptr(), sigma_reset=float(sigma_reset), pad2=0,
+            states=out["states"].data_ptr(), refs=out["refs"].data_ptr(), grf=out["grf"].data_ptr(),
+            footholds=out["footholds"].data_ptr(), grf_raw=out["grf_raw"].data_ptr(),
+            predicted_state=out["predicted_state"].data_ptr(), best_cost=out["best_cost"].data_ptr(),
+            best_index=out["best_index"].data_ptr(), best_freq=out["best_freq"].data_ptr(),
+            status=out["status"].data_ptr(), costs=out["costs"].data_ptr() if want_costs else None)
+        # the null stream by its explicit handle, as in step_device
+        self.check(lib.srbd_batch_interface_step_device(self.h, C.byref(io), C.c_void_p(s.cuda_stream or 1)),
+                   "srbd_batch_interface_step_device")
         return out
 
 

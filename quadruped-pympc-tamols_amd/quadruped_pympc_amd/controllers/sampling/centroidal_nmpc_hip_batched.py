@@ -159,8 +159,10 @@ class Batched_Sampling_MPC:
         states, references (E, 24), contact_sequences (E, 4, >=H), best_control_parameters (E, P): contiguous float32
         tensors; best_control_parameters is updated in place and returned.  keys, int64 or uint64: for
         ``rng == 'philox'`` the (E, 2) (seed, counter) tensor; for the JAX streams the (E,) packed keys
-        (``_lib.pack_key``), the step number being the counter as in ``compute_control``.  Advancing JAX keys on the
-        device is not provided: split them on the host (``with_newkey``) and upload the packed keys.
+        (``_lib.pack_key``), the step number being the counter as in ``compute_control``.  This call runs one
+        sampling iteration with the keys as given; ``Batched_SRBDControllerInterface``
+        (interfaces/srbd_controller_interface_batched) advances the keys of every stream on the device and runs the
+        ``num_sampling_iterations`` iterations of a control step.
 
         Returns the single class's tuple: (GRFs (E, 12), footholds (E, 12), predicted states (E, 24), best parameters
         (E, P), best costs (E,), step frequencies (E,), costs (E, N) lazy -- fetched to the host on first use).

@@ -19,7 +19,8 @@ the first one, keys advanced between calls::
                                        sigma_reset=c.sigma_reset_value if it == 0 else None)
     grf = out[0]   # best and sigma were updated in place
 
-Advancing JAX keys on the device, gait-adaptive CEM and graph capture are not provided.
+``Batched_SRBDControllerInterface`` (interfaces/srbd_controller_interface_batched) is that loop as one device-resident
+call, the keys of every stream advanced on the device.  Gait-adaptive CEM and graph capture are not provided.
 """
 from __future__ import annotations
 
