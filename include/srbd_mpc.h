@@ -721,8 +721,8 @@ int srbd_prepare_state_device(int32_t num_envs, const double* d_state_in, const 
  * helpers :261-714, and the heightmap raycast of wb_interface.py:233-234) for num_envs environments in one launch,
  * device in and device out, so that generator.run -> footholds -> prepare -> srbd_batch_step_device never leaves
  * the GPU.  Stateless: no context, no allocation.
- *   Forms: terrain != NULL raycasts every leg's rows x cols patch from the one scene all environments share, centred
- *   at the leg's seed and yawed by yaws[e] (what srbd_tamols_run_terrain does per call); terrain == NULL reads the
+ *   Forms: terrain != NULL raycasts every leg's rows x cols patch from the one scene all environments share (one
+ *   scene per environment: srbd_tamols_batch_scenes_device, below), centred at the leg's seed and yawed by yaws[e] (what srbd_tamols_run_terrain does per call); terrain == NULL reads the
  *   caller's patches from `heightmaps` (what srbd_tamols_run does).  params, rows, cols, the spacings and ray_z are
  *   shared by the environments; NULL forward_vel / base_pos / contact / feet mean what they mean in srbd_tamols_run,
  *   for every environment.  contact is float32 as srbd_pgg_run_device writes it (stance iff 1.0f).
@@ -809,6 +809,70 @@ struct srbd_stc;
 int srbd_vfa_step_device(struct srbd_vfa* d_vfa, const struct srbd_stc* d_stc, srbd_terrain* terrain /* NULL: patch form */,
                          const srbd_tamols_params* params, int32_t num_envs, const srbd_tamols_batch_io* io,
                          double apex_interval, int32_t* d_mode /* E, or NULL */, void* hip_stream);
+/* One terrain scene per environment: a device-resident set of scenes and the two calls above reading, per environment,
+ * an index into it -- so one batch can sweep the ground as srbd_batch_set_env_params lets it sweep the robot, and an
+ * environment can move to another scene at reset, in one launch and with nothing on the host knowing which
+ * environment stands on which scene.
+ *   srbd_terrain_scene holds srbd_terrain_create's arguments of one scene (80 bytes, no padding).
+ *   srbd_terrain_set_create takes 1..4096 scenes and checks each as srbd_terrain_create checks its arguments; the
+ *   first scene that fails returns SRBD_E_INVALID with its index in the message, before any HIP call, and so do
+ *   scenes whose primitives or height-field points together number more than 2^31 - 1, a NULL scenes or out and a
+ *   num_scenes outside 1..4096.  On the device the set holds the scenes' primitives concatenated, their box-yaw
+ *   cos / sin pairs concatenated (formed by the function srbd_terrain_create forms them with: a scene in a set and the
+ *   same scene alone hold the same bits), the height fields concatenated, and a table of one record per scene
+ *   pointing into those arrays.  The host arrays are not kept.  The set is immutable after creation.  No device:
+ *   SRBD_E_NODEVICE; a failed allocation: SRBD_E_NOMEM; another failed HIP call: SRBD_E_HIP.
+ *   srbd_terrain_set_last_error: the set's last message; NULL: the calling thread's last failed create, or its last
+ *   call below refused for a NULL set.  srbd_terrain_set_num_scenes(NULL) is SRBD_E_INVALID,
+ *   srbd_terrain_set_destroy(NULL) a no-op.
+ *   srbd_tamols_batch_scenes_device is the terrain form of srbd_tamols_batch_device with environment e's rays cast
+ *   against scene d_scene[e].  d_scene (num_envs int32) is the caller's device memory, read in stream order: a reset
+ *   writes new indices with an ordinary operation earlier on the same stream, no entry point is needed for that and
+ *   nothing reaches the host.
+ *   Equivalence: every output of environment e (footholds, boxes, valid, seed_heights, scores, heightmaps_out, ref's
+ *   entries 12..23; ref's entries 0..11 are not written) holds the bytes srbd_tamols_batch_device writes for that
+ *   environment's inputs on a srbd_terrain created from scene d_scene[e].  Both form the yaw's cos / sin on the
+ *   device, so the libm caveat of the single call does not arise.  Environments are independent.
+ *   An index outside 0..num_scenes-1 cannot be reported from a launch: that environment runs on the empty scene (no
+ *   ground, no primitives, no height field, miss_z NaN) and its outputs are those on such a srbd_terrain; nothing is
+ *   read out of bounds.
+ *   Launch shape: srbd_tamols_batch_device's grid, block and LDS.  Block (leg, e) reads d_scene[e] once (one wave),
+ *   bounds-checks it and copies the scene's 88-byte record (or forms the empty one) next to the environment's other
+ *   arguments; from there the stages are the shared-scene kernel's.
+ *   Enqueue contract: srbd_tamols_batch_device's -- exactly one launch on hip_stream, no synchronising HIP call, no
+ *   device memory touched from the host, the stream handle read the same way; the set must outlive the launch and
+ *   live on the current device.
+ *   SRBD_E_INVALID (before any HIP call, with a message): everything the terrain form of srbd_tamols_batch_device
+ *   refuses; a NULL set or d_scene; a d_scene that is not 4-byte aligned; io->heightmaps given (the patch form has no
+ *   scenes: that is srbd_tamols_batch_device).
+ *   srbd_vfa_step_scenes_device is srbd_vfa_step_device with the same substitution: its equivalence, its launch
+ *   shape, its read-once rule for initialized[leg] and its HOLD / PASS early exit.  A block that does not search reads
+ *   neither its scene index nor the set, as it reads neither its yaw nor the terrain: an out-of-range index on a
+ *   holding or passing environment has no effect.
+ *   Out of scope: adding or replacing a scene after creation; per-environment scene origins, rows, cols or spacings;
+ *   the patch form and the single-environment calls; a per-environment error flag for bad indices. */
+typedef struct srbd_terrain_scene {
+    const srbd_terrain_prim* prims; /* nprims primitives, or NULL when nprims == 0 */
+    int32_t nprims, has_ground;
+    double ground_z;
+    const double* hfield;           /* hf_nx x hf_ny heights as in srbd_terrain_create, or NULL */
+    int32_t hf_nx, hf_ny;
+    double hf_x0, hf_y0, hf_dx, hf_dy;
+    double miss_z;
+} srbd_terrain_scene;
+typedef struct srbd_terrain_set srbd_terrain_set;
+int srbd_terrain_set_create(int32_t device_id, const srbd_terrain_scene* scenes, int32_t num_scenes,
+                            srbd_terrain_set** out);
+void srbd_terrain_set_destroy(srbd_terrain_set* set);
+const char* srbd_terrain_set_last_error(const srbd_terrain_set* set);
+int srbd_terrain_set_num_scenes(const srbd_terrain_set* set);
+int srbd_tamols_batch_scenes_device(srbd_terrain_set* set, const int32_t* d_scene /* E */,
+                                    const srbd_tamols_params* params, int32_t num_envs,
+                                    const srbd_tamols_batch_io* io, void* hip_stream);
+int srbd_vfa_step_scenes_device(struct srbd_vfa* d_vfa, const struct srbd_stc* d_stc, srbd_terrain_set* set,
+                                const int32_t* d_scene /* E */, const srbd_tamols_params* params, int32_t num_envs,
+                                const srbd_tamols_batch_io* io, double apex_interval, int32_t* d_mode /* E, or NULL */,
+                                void* hip_stream);
 /* Self-test: out_cs[2 i], out_cs[2 i + 1] = the cos and sin srbd_tamols_batch_device's kernel forms of yaws[i],
  * evaluated on the host by the same function (plain float64 operations and fma: the same bits on both sides). */
 int srbd_selftest_yaw_sincos(const double* yaws, int32_t n, double* out_cs);

@@ -269,7 +269,23 @@ struct srbd_terrain {
     std::string err;
 };
 
+// Device-resident set of scenes (opaque in the C-ABI): the scenes' primitives, box-yaw cos / sin pairs and height
+// fields concatenated, and one TerrainDev per scene whose pointers are its own slices of them (NULL for a scene
+// without primitives or without a height field, as in srbd_terrain).  Immutable after srbd_terrain_set_create.
+struct srbd_terrain_set {
+    int device = 0;
+    int num_scenes = 0;
+    srbd_terrain_prim* d_prims = nullptr;
+    double* d_cs = nullptr;
+    double* d_hf = nullptr;
+    srbd::TerrainDev* d_table = nullptr;  // num_scenes records
+    std::string err;
+};
+
 namespace srbd {
+// The error text of a call on a set (set == NULL: the thread's, what srbd_terrain_set_last_error(NULL) returns).
+int terrain_set_fail(srbd_terrain_set* set, int code, const std::string& message);
+
 // Raycast npatch patches on stream s into the scene's device output buffer (*d_out).
 int terrain_enqueue(srbd_terrain* t, const double* centers, const double* yaws, int npatch, int rows, int cols,
                     double dist_x, double dist_y, double ray_z, hipStream_t s, double** d_out);
@@ -351,6 +367,17 @@ void launch_tamols_batch(const TamolsBatchJob& j, hipStream_t s);
 // The same grid and block with the gate: block (leg, e) forms environment e's mode (srbd_vfa.h vfa_mode) and, unless it
 // is SEARCH, copies its leg's held foothold or seed and leaves before the search's first stage.
 void launch_tamols_batch_gated(const TamolsBatchJob& j, hipStream_t s);
+// One scene per environment (srbd_tamols_batch_scenes_device, srbd_vfa_step_scenes_device): the same job -- its `t` is
+// not read, use_terrain is 1 -- and behind it the set's table and the caller's E scene indices.  Block (leg, e) takes
+// table[scene[e]] as its TerrainDev, or the empty scene (nothing to hit, miss_z NaN) for an index outside
+// 0..num_scenes-1; from there the stages are launch_tamols_batch's / launch_tamols_batch_gated's, on the same grid,
+// block and LDS.
+struct TamolsBatchScenesJob : TamolsBatchJob {
+    const TerrainDev* table;
+    const int32_t* scene;
+    int32_t num_scenes;
+};
+void launch_tamols_batch_scenes(const TamolsBatchScenesJob& j, bool gated, hipStream_t s);
 
 // The per-environment reset of the loop's device state (srbd_loop_reset_device; srbd_producers.hip
 // loop_reset_kernel): the arrays of one call (include/srbd_mpc.h srbd_loop_reset_io), E entries each.  One wave per

@@ -32,7 +32,9 @@
 // srbd_tamols_batch_device, the loop's foothold search, is validated and enqueued here too; its kernel lives with the
 // single-environment one (tamols_kernel.hip tamols_batch_kernel), whose device functions it runs.  So is
 // srbd_vfa_step_device, the same search behind the reference's apex gate (srbd_vfa.h; wb_interface.py:230-246): the
-// same job with the gate's four fields, the same grid, the kernel's gated instantiation.
+// same job with the gate's four fields, the same grid, the kernel's gated instantiation.  And their forms with one
+// terrain scene per environment (srbd_tamols_batch_scenes_device, srbd_vfa_step_scenes_device): the same job again,
+// behind it the table of a srbd_terrain_set (terrain_kernel.hip) and the caller's scene indices.
 // loop_reset_kernel (srbd_loop_reset_device) restarts the environments a mask names (srbd_reset.h; simulation/
 // simulation.py:773-781, wb_interface.py:469-484): one wave per environment, see the kernel.
 // iface_prologue_kernel and iface_epilogue_kernel are the two launches srbd_batch_interface_step_device (srbd_api.hip)
@@ -748,8 +750,10 @@ extern "C" int srbd_terrain_ref_step_device(srbd_terrain_est* d_terrain, int32_t
 namespace {
 
 // What srbd_tamols_batch_device refuses, and the launch's job from its arguments (srbd_vfa_step_device adds the gate).
-int tamols_batch_job(srbd_terrain* terrain, const srbd_tamols_params* params, int32_t num_envs,
-                     const srbd_tamols_batch_io* io, TamolsBatchJob& j) {
+// terrain: the terrain form (its scene `dev`, or NULL for a launch that takes its scenes elsewhere) on device `*device`;
+// neither pointer is followed before the arguments have passed.
+int tamols_batch_job(bool terrain, const int* device, const TerrainDev* dev, const srbd_tamols_params* params,
+                     int32_t num_envs, const srbd_tamols_batch_io* io, TamolsBatchJob& j) {
     if (!params || !io || !io->seeds || !io->hips || !io->footholds || !io->boxes || !io->valid || !envs_ok(num_envs))
         return SRBD_E_INVALID;
     if (io->rows < 1 || io->cols < 1 || (int64_t)io->rows * io->cols > TAMOLS_MAXCAND) return SRBD_E_INVALID;
@@ -776,10 +780,10 @@ int tamols_batch_job(srbd_terrain* terrain, const srbd_tamols_params* params, in
     j.rows = io->rows;
     j.cols = io->cols;
     if (terrain) {
-        int dev = -1;
-        if (hipGetDevice(&dev) == hipSuccess && dev != terrain->device) return SRBD_E_INVALID;
+        int cur = -1;
+        if (hipGetDevice(&cur) == hipSuccess && cur != *device) return SRBD_E_INVALID;
         j.use_terrain = 1;
-        j.t = terrain->dev;
+        if (dev) j.t = *dev;
         j.yaws = io->yaws;
         j.hm_out = io->heightmaps_out;
         j.dist_x = io->dist_x;
@@ -799,7 +803,8 @@ int tamols_batch_job(srbd_terrain* terrain, const srbd_tamols_params* params, in
 extern "C" int srbd_tamols_batch_device(srbd_terrain* terrain, const srbd_tamols_params* params, int32_t num_envs,
                                         const srbd_tamols_batch_io* io, void* hip_stream) {
     TamolsBatchJob j;
-    const int rc = tamols_batch_job(terrain, params, num_envs, io, j);
+    const int rc = tamols_batch_job(terrain != nullptr, terrain ? &terrain->device : nullptr,
+                                    terrain ? &terrain->dev : nullptr, params, num_envs, io, j);
     if (rc != SRBD_OK) return rc;
     launch_tamols_batch(j, stream_of(hip_stream));
     return launch_status();
@@ -810,13 +815,73 @@ extern "C" int srbd_vfa_step_device(srbd_vfa* d_vfa, const srbd_stc* d_stc, srbd
                                     double apex_interval, int32_t* d_mode, void* hip_stream) {
     if (!d_vfa || !d_stc || !io || !io->contact || !std::isfinite(apex_interval)) return SRBD_E_INVALID;
     TamolsBatchJob j;
-    const int rc = tamols_batch_job(terrain, params, num_envs, io, j);
+    const int rc = tamols_batch_job(terrain != nullptr, terrain ? &terrain->device : nullptr,
+                                    terrain ? &terrain->dev : nullptr, params, num_envs, io, j);
     if (rc != SRBD_OK) return rc;
     j.vfa = d_vfa;
     j.stc = d_stc;
     j.mode = d_mode;
     j.apex_interval = apex_interval;
     launch_tamols_batch_gated(j, stream_of(hip_stream));
+    return launch_status();
+}
+
+namespace {
+
+// What the two scenes calls refuse, with a message, and the launch's job: the shared-scene job of the terrain form,
+// the set's table and the caller's indices behind it.
+int tamols_scenes_job(const char* what, srbd_terrain_set* set, const int32_t* d_scene, const srbd_tamols_params* params,
+                      int32_t num_envs, const srbd_tamols_batch_io* io, TamolsBatchScenesJob& j) {
+    const std::string w = std::string(what) + ": ";
+    if (!set) return terrain_set_fail(nullptr, SRBD_E_INVALID, w + "null set");
+    if (!d_scene) return terrain_set_fail(set, SRBD_E_INVALID, w + "null d_scene");
+    if (reinterpret_cast<uintptr_t>(d_scene) % alignof(int32_t))
+        return terrain_set_fail(set, SRBD_E_INVALID, w + "d_scene is not 4-byte aligned");
+    if (io && io->heightmaps)
+        return terrain_set_fail(set, SRBD_E_INVALID,
+                                w + "io->heightmaps given: the patch form has no scenes, it is srbd_tamols_batch_device's");
+    const int rc = tamols_batch_job(true, &set->device, nullptr, params, num_envs, io, j);
+    if (rc != SRBD_OK)
+        return terrain_set_fail(set, rc,
+                                w + "an argument the terrain form of srbd_tamols_batch_device refuses (a NULL required "
+                                    "pointer, num_envs, rows, cols, dist_x, dist_y), or the set is not on the current "
+                                    "device");
+    j.table = set->d_table;
+    j.scene = d_scene;
+    j.num_scenes = set->num_scenes;
+    return SRBD_OK;
+}
+
+}  // namespace
+
+extern "C" int srbd_tamols_batch_scenes_device(srbd_terrain_set* set, const int32_t* d_scene,
+                                               const srbd_tamols_params* params, int32_t num_envs,
+                                               const srbd_tamols_batch_io* io, void* hip_stream) {
+    TamolsBatchScenesJob j;
+    const int rc = tamols_scenes_job("srbd_tamols_batch_scenes_device", set, d_scene, params, num_envs, io, j);
+    if (rc != SRBD_OK) return rc;
+    launch_tamols_batch_scenes(j, false, stream_of(hip_stream));
+    return launch_status();
+}
+
+extern "C" int srbd_vfa_step_scenes_device(srbd_vfa* d_vfa, const srbd_stc* d_stc, srbd_terrain_set* set,
+                                           const int32_t* d_scene, const srbd_tamols_params* params, int32_t num_envs,
+                                           const srbd_tamols_batch_io* io, double apex_interval, int32_t* d_mode,
+                                           void* hip_stream) {
+    const char* what = "srbd_vfa_step_scenes_device";
+    if (!set) return terrain_set_fail(nullptr, SRBD_E_INVALID, std::string(what) + ": null set");
+    if (!d_vfa || !d_stc || !io || !io->contact || !std::isfinite(apex_interval))
+        return terrain_set_fail(set, SRBD_E_INVALID,
+                                std::string(what) + ": a NULL d_vfa, d_stc, io or io->contact, or an apex_interval that "
+                                                    "is not finite");
+    TamolsBatchScenesJob j;
+    const int rc = tamols_scenes_job(what, set, d_scene, params, num_envs, io, j);
+    if (rc != SRBD_OK) return rc;
+    j.vfa = d_vfa;
+    j.stc = d_stc;
+    j.mode = d_mode;
+    j.apex_interval = apex_interval;
+    launch_tamols_batch_scenes(j, true, stream_of(hip_stream));
     return launch_status();
 }
 

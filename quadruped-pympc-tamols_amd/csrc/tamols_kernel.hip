@@ -749,8 +749,28 @@ constexpr int TAMOLS_PARAM_DOUBLES = (int)(sizeof(srbd_tamols_params) / sizeof(d
 static_assert(sizeof(srbd_tamols_params) % sizeof(double) == 0 && offsetof(TamolsBatchJob, p) % sizeof(double) == 0 &&
                   TAMOLS_PARAM_DOUBLES <= 64,
               "the gated kernel copies the parameters as doubles, one per lane of wave 1");
-template <bool GATED>
-__global__ void __launch_bounds__(TAMOLS_BATCH_THREADS) tamols_batch_kernel(const TamolsBatchJob bj) {
+//
+// SCENES (srbd_tamols_batch_scenes_device, srbd_vfa_step_scenes_device): one scene per environment.  The job carries
+// the set's table of TerrainDev records and the caller's E scene indices; wave 3, idle while the others assemble the
+// environment's arguments, reads scene[e] -- one load, block-uniform --, bounds-checks it and copies the record's
+// eleven 8-byte words (or forms the empty scene's) into j.t, the TerrainDev slot of the LDS job the batched kernels
+// left unused, before the barrier that already ends that stage.  The patch stage then reads its scene there where
+// the shared-scene instantiations read the kernel argument; a record's pointers are the scene's own slices of the
+// set's concatenated arrays, so the cull, the field walk and the walk of the whole scene index from zero as before.
+// Behind the gate, so a HOLD or PASS block reads neither its index nor the set.  The two instantiations without
+// SCENES compile to the code they had.
+constexpr int TERRAIN_DEV_WORDS = (int)(sizeof(TerrainDev) / 8);
+static_assert(sizeof(TerrainDev) % 8 == 0 && offsetof(TerrainDev, miss_z) % 8 == 0 && TERRAIN_DEV_WORDS <= 64,
+              "the scene's record is copied as 8-byte words, one per lane of wave 3");
+typedef uint64_t __attribute__((may_alias)) record_word;
+// The body is a device function the kernels below wrap, inlined into each: written as the kernel template itself, the
+// gated SCENES instantiation crashes the compiler's optimizer (ROCm 7.2, infer-address-spaces inside the inliner's
+// call-graph walk), and the wrapped form compiles the two shared-scene kernels to the registers, scratch and LDS
+// they had.
+template <bool SCENES>
+using TamolsBatchArg = std::conditional_t<SCENES, TamolsBatchScenesJob, TamolsBatchJob>;
+template <bool GATED, bool SCENES>
+__device__ __forceinline__ void tamols_batch_body(const TamolsBatchArg<SCENES>& bj) {
     extern __shared__ double bsm[];
     __shared__ TamolsJob j;
     __shared__ int pn;
@@ -846,11 +866,29 @@ __global__ void __launch_bounds__(TAMOLS_BATCH_THREADS) tamols_batch_kernel(cons
     } else if (!bj.use_terrain && tid == 128) {
         j.lattice = 0;
     }
+    if constexpr (SCENES) {
+        if (tid >= 192 && tid < 192 + TERRAIN_DEV_WORDS) {
+            const int k = tid - 192;
+            const int32_t sid = __builtin_amdgcn_readfirstlane(bj.scene[e]);  // block-uniform; tells the compiler so
+            // an index outside the set: no ground, no primitives, no height field (all words zero), miss_z NaN
+            record_word w = k == (int)(offsetof(TerrainDev, miss_z) / 8) ? 0x7ff8000000000000ull : 0ull;
+            if ((uint32_t)sid < (uint32_t)bj.num_scenes) w = reinterpret_cast<const record_word*>(bj.table + sid)[k];
+            reinterpret_cast<record_word*>(&j.t)[k] = w;
+        }
+    }
     __syncthreads();
 
     // ---- patch -> LDS
     if (bj.use_terrain) {
-        const TerrainDev& t = bj.t;
+        // SCENES: the record out of LDS into registers.  Its pointers are generic to the compiler (the shared-scene
+        // kernels' come from the kernel argument and are known to be global memory), so the scene's loads are flat ones.
+        TerrainDev trec;
+        const TerrainDev* scene_rec = &bj.t;
+        if constexpr (SCENES) {
+            trec = j.t;
+            scene_rec = &trec;
+        }
+        const TerrainDev& t = *scene_rec;
         const int np = t.nprims;
         // the primitives that can touch this patch, culled from global memory into a compact copy (tamols_fused_kernel's
         // test); a ray's result is a maximum over primitives, so the copy's order (atomic slots) does not matter.  Past
@@ -861,7 +899,14 @@ __global__ void __launch_bounds__(TAMOLS_BATCH_THREADS) tamols_batch_kernel(cons
             const double hx = 0.5 * (double)(bj.rows - 1) * fabs(bj.dist_x), hy = 0.5 * (double)(bj.cols - 1) * fabs(bj.dist_y);
             const double rp = sqrt(hx * hx + hy * hy);
             for (int q = tid; q < np; q += T) {
-                const srbd_terrain_prim pr = t.prims[q];
+                srbd_terrain_prim pr;
+                if constexpr (SCENES) {  // field by field: the struct copy left (c, yaw) a memcpy through scratch memory
+                    const srbd_terrain_prim* g = t.prims + q;
+                    pr.type = g->type, pr.pad = g->pad, pr.cx = g->cx, pr.cy = g->cy, pr.cz = g->cz;
+                    pr.a = g->a, pr.b = g->b, pr.c = g->c, pr.yaw = g->yaw;
+                } else {
+                    pr = t.prims[q];
+                }
                 const bool box = pr.type == SRBD_PRIM_BOX;
                 const double r = box ? fabs(pr.a) + fabs(pr.b) : fabs(pr.a);
                 const double dx = pr.cx - a.seeds[3 * leg], dy = pr.cy - a.seeds[3 * leg + 1];
@@ -1003,6 +1048,11 @@ __global__ void __launch_bounds__(TAMOLS_BATCH_THREADS) tamols_batch_kernel(cons
         for (int k = 0; k < 3; ++k) bj.ref[24 * (size_t)e + 12 + 3 * leg + k] = f[k];
 }
 
+template <bool GATED, bool SCENES = false>
+__global__ void __launch_bounds__(TAMOLS_BATCH_THREADS) tamols_batch_kernel(const TamolsBatchArg<SCENES> bj) {
+    tamols_batch_body<GATED, SCENES>(bj);
+}
+
 size_t tamols_batch_lds(int rows, int cols) {
     const size_t nc = (size_t)rows * cols;
     const size_t cull = TAMOLS_BATCH_CULL * (sizeof(srbd_terrain_prim) / sizeof(double) + 2);
@@ -1018,6 +1068,15 @@ void launch_tamols_batch(const TamolsBatchJob& j, hipStream_t s) {
 void launch_tamols_batch_gated(const TamolsBatchJob& j, hipStream_t s) {
     hipLaunchKernelGGL(tamols_batch_kernel<true>, dim3(4, j.E), dim3(TAMOLS_BATCH_THREADS),
                        tamols_batch_lds(j.rows, j.cols), s, j);
+}
+
+void launch_tamols_batch_scenes(const TamolsBatchScenesJob& j, bool gated, hipStream_t s) {
+    if (gated)
+        hipLaunchKernelGGL((tamols_batch_kernel<true, true>), dim3(4, j.E), dim3(TAMOLS_BATCH_THREADS),
+                           tamols_batch_lds(j.rows, j.cols), s, j);
+    else
+        hipLaunchKernelGGL((tamols_batch_kernel<false, true>), dim3(4, j.E), dim3(TAMOLS_BATCH_THREADS),
+                           tamols_batch_lds(j.rows, j.cols), s, j);
 }
 
 }  // namespace srbd

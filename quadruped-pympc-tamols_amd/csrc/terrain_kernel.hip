@@ -8,7 +8,9 @@
 // -ffp-contract=off: the points are bit-identical to oracle/terrain_oracle.py.
 #include <math.h>
 
+#include <algorithm>
 #include <string>
+#include <vector>
 
 #include "terrain_ray.h"
 
@@ -45,6 +47,27 @@ static int terrain_fail(srbd_terrain* t, int code, const std::string& m) {
         if (_e != hipSuccess) return terrain_fail((t), SRBD_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
     } while (0)
 
+// What srbd_terrain_create refuses of a scene's arguments (NULL: nothing), before any HIP call; a scene of a set
+// (srbd_terrain_set_create) is checked by the same function.
+static const char* scene_refused(const srbd_terrain_prim* prims, int32_t nprims, const double* hfield, int32_t hf_nx,
+                                 int32_t hf_ny, double hf_dx, double hf_dy) {
+    if (nprims < 0 || (nprims > 0 && !prims)) return "bad arguments";
+    if (hfield && (hf_nx < 2 || hf_ny < 2 || !(hf_dx > 0.0) || !(hf_dy > 0.0)))
+        return "height field needs >= 2 x 2 points and positive spacing";
+    for (int q = 0; q < nprims; ++q)
+        if (prims[q].type != SRBD_PRIM_BOX && prims[q].type != SRBD_PRIM_CYLINDER) return "unknown primitive type";
+    return nullptr;
+}
+
+// The device scene's box-yaw pairs: cs[2 q], cs[2 q + 1] = cos, sin of prims[q].yaw (the host's libm).  The one place
+// they are formed, so a scene alone and the same scene in a set hold the same bits.
+static void prim_yaw_cs(const srbd_terrain_prim* prims, int32_t nprims, double* cs) {
+    for (int q = 0; q < nprims; ++q) {
+        cs[2 * q] = cos(prims[q].yaw);
+        cs[2 * q + 1] = sin(prims[q].yaw);
+    }
+}
+
 extern "C" void srbd_terrain_destroy(srbd_terrain* t) {
     if (!t) return;
     (void)hipSetDevice(t->device);
@@ -66,13 +89,10 @@ extern "C" const char* srbd_terrain_last_error(const srbd_terrain* t) {
 extern "C" int srbd_terrain_create(int32_t device_id, const srbd_terrain_prim* prims, int32_t nprims, int32_t has_ground,
                                    double ground_z, const double* hfield, int32_t hf_nx, int32_t hf_ny, double hf_x0,
                                    double hf_y0, double hf_dx, double hf_dy, double miss_z, srbd_terrain** out) {
-    if (!out || nprims < 0 || (nprims > 0 && !prims)) return terrain_fail(nullptr, SRBD_E_INVALID, "bad arguments");
+    if (!out) return terrain_fail(nullptr, SRBD_E_INVALID, "bad arguments");
+    if (const char* why = scene_refused(prims, nprims, hfield, hf_nx, hf_ny, hf_dx, hf_dy))
+        return terrain_fail(nullptr, SRBD_E_INVALID, why);
     *out = nullptr;
-    if (hfield && (hf_nx < 2 || hf_ny < 2 || !(hf_dx > 0.0) || !(hf_dy > 0.0)))
-        return terrain_fail(nullptr, SRBD_E_INVALID, "height field needs >= 2 x 2 points and positive spacing");
-    for (int q = 0; q < nprims; ++q)
-        if (prims[q].type != SRBD_PRIM_BOX && prims[q].type != SRBD_PRIM_CYLINDER)
-            return terrain_fail(nullptr, SRBD_E_INVALID, "unknown primitive type");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0 || device_id < 0 || device_id >= ndev)
         return terrain_fail(nullptr, SRBD_E_NODEVICE, "no HIP device visible (this library has no CPU fallback)");
@@ -111,10 +131,7 @@ extern "C" int srbd_terrain_create(int32_t device_id, const srbd_terrain_prim* p
     if ((e = hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking)) != hipSuccess) return bad(e);
     if (nprims > 0) {
         std::vector<double> cs(2 * (size_t)nprims);
-        for (int q = 0; q < nprims; ++q) {
-            cs[2 * q] = cos(prims[q].yaw);
-            cs[2 * q + 1] = sin(prims[q].yaw);
-        }
+        prim_yaw_cs(prims, nprims, cs.data());
         if ((e = hipMalloc((void**)&t->d_prims, sizeof(srbd_terrain_prim) * nprims)) != hipSuccess) return bad(e);
         if ((e = hipMalloc((void**)&t->d_cs, sizeof(double) * 2 * nprims)) != hipSuccess) return bad(e);
         if ((e = hipMemcpy(t->d_prims, prims, sizeof(srbd_terrain_prim) * nprims, hipMemcpyHostToDevice)) != hipSuccess)
@@ -130,6 +147,124 @@ extern "C" int srbd_terrain_create(int32_t device_id, const srbd_terrain_prim* p
     t->dev.prims = t->d_prims;
     t->dev.cs = t->d_cs;
     t->dev.hf = t->d_hf;
+    *out = t;
+    return SRBD_OK;
+}
+
+// ------------------------------------------------------------------ a set of scenes (srbd_terrain_set_*)
+static thread_local std::string g_terrain_set_error;
+
+int srbd::terrain_set_fail(srbd_terrain_set* set, int code, const std::string& m) {
+    (set ? set->err : g_terrain_set_error) = m;
+    return code;
+}
+
+extern "C" void srbd_terrain_set_destroy(srbd_terrain_set* set) {
+    if (!set) return;
+    (void)hipSetDevice(set->device);
+    (void)hipFree(set->d_prims);
+    (void)hipFree(set->d_cs);
+    (void)hipFree(set->d_hf);
+    (void)hipFree(set->d_table);
+    delete set;
+}
+
+extern "C" const char* srbd_terrain_set_last_error(const srbd_terrain_set* set) {
+    return set ? set->err.c_str() : g_terrain_set_error.c_str();
+}
+
+extern "C" int srbd_terrain_set_num_scenes(const srbd_terrain_set* set) {
+    return set ? set->num_scenes : SRBD_E_INVALID;
+}
+
+extern "C" int srbd_terrain_set_create(int32_t device_id, const srbd_terrain_scene* scenes, int32_t num_scenes,
+                                       srbd_terrain_set** out) {
+    constexpr int MAX_SCENES = 4096;
+    if (!out) return terrain_set_fail(nullptr, SRBD_E_INVALID, "srbd_terrain_set_create: null out");
+    *out = nullptr;
+    if (!scenes) return terrain_set_fail(nullptr, SRBD_E_INVALID, "srbd_terrain_set_create: null scenes");
+    if (num_scenes < 1 || num_scenes > MAX_SCENES)
+        return terrain_set_fail(nullptr, SRBD_E_INVALID, "srbd_terrain_set_create: num_scenes must be 1..4096");
+    // every scene as srbd_terrain_create checks it; the concatenated arrays are indexed with int
+    int64_t np_all = 0, nh_all = 0;
+    for (int s = 0; s < num_scenes; ++s) {
+        const srbd_terrain_scene& c = scenes[s];
+        if (const char* why = scene_refused(c.prims, c.nprims, c.hfield, c.hf_nx, c.hf_ny, c.hf_dx, c.hf_dy))
+            return terrain_set_fail(nullptr, SRBD_E_INVALID,
+                                    "srbd_terrain_set_create: scene " + std::to_string(s) + ": " + why);
+        np_all += c.nprims;
+        if (c.hfield) nh_all += (int64_t)c.hf_nx * c.hf_ny;
+        if (np_all > INT32_MAX || nh_all > INT32_MAX)
+            return terrain_set_fail(nullptr, SRBD_E_INVALID,
+                                    "srbd_terrain_set_create: scene " + std::to_string(s) +
+                                        ": the scenes' primitives or height-field points together exceed 2^31 - 1");
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0 || device_id < 0 || device_id >= ndev)
+        return terrain_set_fail(nullptr, SRBD_E_NODEVICE,
+                                "srbd_terrain_set_create: no HIP device visible (this library has no CPU fallback)");
+    srbd_terrain_set* t = new srbd_terrain_set();
+    t->device = device_id;
+    t->num_scenes = num_scenes;
+    auto bad = [&](hipError_t e) {
+        const std::string m = std::string("srbd_terrain_set_create: upload: ") + hipGetErrorString(e);
+        srbd_terrain_set_destroy(t);
+        return terrain_set_fail(nullptr, e == hipErrorOutOfMemory ? SRBD_E_NOMEM : SRBD_E_HIP, m);
+    };
+    hipError_t e;
+    if ((e = hipSetDevice(device_id)) != hipSuccess) return bad(e);
+    if (np_all > 0) {
+        if ((e = hipMalloc((void**)&t->d_prims, sizeof(srbd_terrain_prim) * (size_t)np_all)) != hipSuccess) return bad(e);
+        if ((e = hipMalloc((void**)&t->d_cs, sizeof(double) * 2 * (size_t)np_all)) != hipSuccess) return bad(e);
+    }
+    if (nh_all > 0 && (e = hipMalloc((void**)&t->d_hf, sizeof(double) * (size_t)nh_all)) != hipSuccess) return bad(e);
+    if ((e = hipMalloc((void**)&t->d_table, sizeof(TerrainDev) * (size_t)num_scenes)) != hipSuccess) return bad(e);
+    // host images of the three arrays, scene after scene, and each scene's record pointing at its own slice
+    std::vector<srbd_terrain_prim> prims((size_t)np_all);
+    std::vector<double> cs(2 * (size_t)np_all), hf((size_t)nh_all);
+    std::vector<TerrainDev> table((size_t)num_scenes);
+    size_t po = 0, ho = 0;  // the scene's first primitive and first height-field point
+    for (int s = 0; s < num_scenes; ++s) {
+        const srbd_terrain_scene& c = scenes[s];
+        TerrainDev& d = table[s];
+        d = TerrainDev{};
+        d.nprims = c.nprims;
+        d.has_ground = c.has_ground != 0;
+        d.ground_z = c.ground_z;
+        d.miss_z = c.miss_z;
+        d.hf_nx = c.hfield ? c.hf_nx : 0;
+        d.hf_ny = c.hfield ? c.hf_ny : 0;
+        d.hf_x0 = c.hf_x0;
+        d.hf_y0 = c.hf_y0;
+        d.hf_dx = c.hf_dx;
+        d.hf_dy = c.hf_dy;
+        if (c.nprims > 0) {
+            std::copy(c.prims, c.prims + c.nprims, prims.begin() + po);
+            prim_yaw_cs(c.prims, c.nprims, cs.data() + 2 * po);
+            d.prims = t->d_prims + po;
+            d.cs = t->d_cs + 2 * po;
+            po += (size_t)c.nprims;
+        }
+        if (c.hfield) {
+            const size_t n = (size_t)c.hf_nx * c.hf_ny;
+            std::copy(c.hfield, c.hfield + n, hf.begin() + ho);
+            d.hf = t->d_hf + ho;
+            ho += n;
+        }
+    }
+    if (np_all > 0) {
+        if ((e = hipMemcpy(t->d_prims, prims.data(), sizeof(srbd_terrain_prim) * prims.size(), hipMemcpyHostToDevice)) !=
+            hipSuccess)
+            return bad(e);
+        if ((e = hipMemcpy(t->d_cs, cs.data(), sizeof(double) * cs.size(), hipMemcpyHostToDevice)) != hipSuccess)
+            return bad(e);
+    }
+    if (nh_all > 0 &&
+        (e = hipMemcpy(t->d_hf, hf.data(), sizeof(double) * hf.size(), hipMemcpyHostToDevice)) != hipSuccess)
+        return bad(e);
+    if ((e = hipMemcpy(t->d_table, table.data(), sizeof(TerrainDev) * table.size(), hipMemcpyHostToDevice)) !=
+        hipSuccess)
+        return bad(e);
     *out = t;
     return SRBD_OK;
 }

@@ -312,6 +312,13 @@ class TerrainPrim(C.Structure):
                 ("yaw", _D)]
 
 
+class TerrainScene(C.Structure):
+    """srbd_terrain_scene (include/srbd_mpc.h): srbd_terrain_create's arguments of one scene of a set."""
+    _fields_ = [("prims", C.POINTER(TerrainPrim)), ("nprims", _I), ("has_ground", _I), ("ground_z", _D),
+                ("hfield", _DP), ("hf_nx", _I), ("hf_ny", _I), ("hf_x0", _D), ("hf_y0", _D), ("hf_dx", _D),
+                ("hf_dy", _D), ("miss_z", _D)]
+
+
 PRIM_BOX, PRIM_CYLINDER = 0, 1
 _U64P = C.POINTER(C.c_uint64)
 SIGNATURES.update({
@@ -399,6 +406,14 @@ SIGNATURES.update({
     "srbd_gait_apply_freq_device": (_I, [_P, _P, _P, _I, _P, _P, _P]),
     # the apex-gated foothold adaptation: srbd_tamols_batch_device behind the gate
     "srbd_vfa_step_device": (_I, [_P, _P, _P, C.POINTER(TamolsParams), _I, C.POINTER(TamolsBatchIO), _D, _P, _P]),
+    # one terrain scene per environment: the device-resident set and the two searches reading an index into it
+    "srbd_terrain_set_create": (_I, [_I, C.POINTER(TerrainScene), _I, C.POINTER(_P)]),
+    "srbd_terrain_set_destroy": (None, [_P]),
+    "srbd_terrain_set_last_error": (C.c_char_p, [_P]),
+    "srbd_terrain_set_num_scenes": (_I, [_P]),
+    "srbd_tamols_batch_scenes_device": (_I, [_P, _P, C.POINTER(TamolsParams), _I, C.POINTER(TamolsBatchIO), _P]),
+    "srbd_vfa_step_scenes_device": (_I, [_P, _P, _P, _P, C.POINTER(TamolsParams), _I, C.POINTER(TamolsBatchIO), _D,
+                                         _P, _P]),
     # the per-environment reset of the loop's state: the host call and its device form
     "srbd_loop_reset": (_I, [_I, _DP, C.POINTER(SrbdPgg), C.POINTER(SrbdFrg), C.POINTER(SrbdStc),
                              C.POINTER(SrbdTerrainEst), C.POINTER(SrbdVfa), C.POINTER(SrbdPgg), C.POINTER(SrbdFrg),
@@ -1564,9 +1579,12 @@ MAX_CAND = 320
 def _tamols_batch_enqueue(native, what, seeds, hips, params, *, terrain=None, yaws=None, heightmaps=None, rows=13,
                           cols=7, dist_x=0.04, dist_y=0.04, ray_z=10.0, forward_vel=None, base_pos=None, contact=None,
                           feet=None, ref=None, out=None, want_seed_heights=False, want_scores=False,
-                          want_heightmaps=False, stream=None, extra_inputs=lambda E: (), extra_outputs=lambda E: ()):
+                          want_heightmaps=False, stream=None, extra_inputs=lambda E: (), extra_outputs=lambda E: (),
+                          scene_ids=None):
     """What ``tamols_batch_device`` and ``vfa_step_device`` share: the checks of the search's tensors, its outputs and
-    its srbd_tamols_batch_io.  ``native(terrain_handle, params, E, io, outputs, stream)`` makes the C call ``what``;
+    its srbd_tamols_batch_io.  ``native(terrain_handle, params, E, io, outputs, stream)`` makes the C call ``what``
+    (when ``terrain`` is a GpuTerrainSet, ``native`` gets the ``scene_ids`` pointer as a seventh argument and makes the
+    scenes call);
     ``extra_inputs(E)`` yields further (name, tensor, shape, dtypes) to check, ``extra_outputs(E)`` further
     (name, shape, dtypes) outputs, always allocated when not given in ``out``."""
     import torch
@@ -1578,8 +1596,16 @@ def _tamols_batch_enqueue(native, what, seeds, hips, params, *, terrain=None, ya
         raise ValueError("params must be a TamolsParams")
     if (terrain is None) == (heightmaps is None):
         raise ValueError("give either terrain (with yaws) or heightmaps")
+    is_set = hasattr(terrain, "num_scenes")  # a GpuTerrainSet: one scene per environment
+    if is_set and scene_ids is None:
+        raise ValueError("a terrain set needs scene_ids, the (E,) int32 scene index of every environment")
+    if scene_ids is not None and not is_set:
+        raise ValueError("scene_ids belong to a terrain set (GpuTerrainSet), not to " +
+                         ("heightmaps: the patch form has no scenes" if terrain is None else "a single GpuTerrain"))
     f64, f32, i32 = (torch.float64,), (torch.float32,), (torch.int32,)
     specs = [("seeds", seeds, (E, 4, 3), f64), ("hips", hips, (E, 4, 3), f64)]
+    if is_set:
+        specs.append(("scene_ids", scene_ids, (E,), i32))
     if terrain is None:
         if not isinstance(heightmaps, torch.Tensor) or heightmaps.dim() != 5:
             raise ValueError(f"heightmaps must be a torch tensor of shape ({E}, 4, rows, cols, 3)")
@@ -1614,6 +1640,8 @@ def _tamols_batch_enqueue(native, what, seeds, hips, params, *, terrain=None, ya
             raise ValueError(f"unknown output {name!r}")
         specs.append((f"out[{name!r}]", t, *shapes[name]))
     dev = _device_tensors(specs)
+    if is_set and dev.index != terrain.device_id:
+        raise ValueError(f"scene_ids must be on the set's device cuda:{terrain.device_id}, got {dev}")
     wanted = ["footholds", "boxes", "valid"] + [n for n, w in (("seed_heights", want_seed_heights),
                                                                  ("scores", want_scores),
                                                                  ("heightmaps", want_heightmaps)) if w]
@@ -1636,9 +1664,11 @@ def _tamols_batch_enqueue(native, what, seeds, hips, params, *, terrain=None, ya
                            footholds=ptr(o["footholds"]), boxes=ptr(o["boxes"]), valid=ptr(o["valid"]),
                            seed_heights=ptr(o.get("seed_heights")), scores=ptr(o.get("scores")),
                            heightmaps_out=ptr(o.get("heightmaps")), ref=ptr(ref))
+        if is_set:
+            return native(terrain.h, C.byref(params), E, C.byref(io), o, s, scene_ids.data_ptr())
         return native(None if terrain is None else terrain.h, C.byref(params), E, C.byref(io), o, s)
 
-    return _enqueue(dev, stream, alloc, call, what)
+    return _enqueue(dev, stream, alloc, call, what.replace("_device", "_scenes_device") if is_set else what)
 
 
 
@@ -1646,7 +1676,7 @@ def _tamols_batch_enqueue(native, what, seeds, hips, params, *, terrain=None, ya
 def tamols_batch_device(seeds, hips, params, *, terrain=None, yaws=None, heightmaps=None, rows=13, cols=7,
                         dist_x=0.04, dist_y=0.04, ray_z=10.0, forward_vel=None, base_pos=None, contact=None, feet=None,
                         ref=None, out=None, want_seed_heights=False, want_scores=False, want_heightmaps=False,
-                        stream=None):
+                        stream=None, scene_ids=None):
     """srbd_tamols_batch_device: the TAMOLS foothold search of every environment, one launch enqueued on ``stream``
     (None: torch's current stream) without a host synchronisation.  seeds / hips (E, 4, 3) float64, ``params`` a
     TamolsParams.  Terrain form: ``terrain`` a GpuTerrain on the tensors' device and ``yaws`` (E,) float64; the
@@ -1656,13 +1686,22 @@ def tamols_batch_device(seeds, hips, params, *, terrain=None, yaws=None, heightm
     float64: its entries 12..23 receive the footholds.  ``out``: a dict of preallocated outputs (any of footholds
     (E, 4, 3), boxes (E, 4, 2, 3), valid (E, 4) int32, seed_heights (E, 4), scores (E, 4, rows * cols), heightmaps
     (E, 4, rows, cols, 3)); absent footholds / boxes / valid are allocated, the other three only when asked for by
-    their ``want_`` flag.  Returns the dict of the tensors written."""
+    their ``want_`` flag.  Returns the dict of the tensors written.
+    One scene per environment (srbd_tamols_batch_scenes_device): ``terrain`` a GpuTerrainSet and ``scene_ids`` an
+    (E,) contiguous int32 tensor on the set's device -- environment e casts its rays against scene ``scene_ids[e]``,
+    read in stream order (rewrite it with a torch operation on the same stream, as at a reset); an index outside the
+    set gives that environment the empty scene.  Host tensors and int64 are refused, not converted."""
+    def native(th, p, E, io, o, s, ids=None):
+        if ids is not None:
+            return lib.srbd_tamols_batch_scenes_device(th, ids, p, E, io, s)
+        return lib.srbd_tamols_batch_device(th, p, E, io, s)
+
     return _tamols_batch_enqueue(
-        lambda th, p, E, io, o, s: lib.srbd_tamols_batch_device(th, p, E, io, s), "srbd_tamols_batch_device", seeds,
+        native, "srbd_tamols_batch_device", seeds,
         hips, params, terrain=terrain, yaws=yaws, heightmaps=heightmaps, rows=rows, cols=cols, dist_x=dist_x,
         dist_y=dist_y, ray_z=ray_z, forward_vel=forward_vel, base_pos=base_pos, contact=contact, feet=feet, ref=ref,
         out=out, want_seed_heights=want_seed_heights, want_scores=want_scores, want_heightmaps=want_heightmaps,
-        stream=stream)
+        stream=stream, scene_ids=scene_ids)
 
 
 VFA_BYTES = C.sizeof(SrbdVfa)
@@ -1676,7 +1715,8 @@ def vfa_step_device(vfa, stc, seeds, hips, params, contact, *, apex_interval: fl
     searched since its last full stance searches; one that has, holds its footholds until the next full stance; every
     other one returns its seeds.  Returns ``tamols_batch_device``'s dict plus ``mode`` (E,) int32 (VFA_SEARCH /
     VFA_HOLD / VFA_PASS; ``out['mode']`` to preallocate); seed_heights, scores and heightmaps rows are written for
-    searching environments only."""
+    searching environments only.  With ``terrain`` a GpuTerrainSet and ``scene_ids`` (srbd_vfa_step_scenes_device) a
+    searching environment searches on its own scene; the others read neither their index nor the set."""
     import math
 
     import torch
@@ -1687,10 +1727,15 @@ def vfa_step_device(vfa, stc, seeds, hips, params, contact, *, apex_interval: fl
     if not math.isfinite(interval):
         raise ValueError(f"apex_interval must be finite, got {apex_interval}")
     u8, i32 = (torch.uint8,), (torch.int32,)
+
+    def native(th, p, E, io, o, s, ids=None):
+        if ids is not None:
+            return lib.srbd_vfa_step_scenes_device(vfa.data_ptr(), stc.data_ptr(), th, ids, p, E, io, interval,
+                                                   o["mode"].data_ptr(), s)
+        return lib.srbd_vfa_step_device(vfa.data_ptr(), stc.data_ptr(), th, p, E, io, interval, o["mode"].data_ptr(), s)
+
     return _tamols_batch_enqueue(
-        lambda th, p, E, io, o, s: lib.srbd_vfa_step_device(vfa.data_ptr(), stc.data_ptr(), th, p, E, io, interval,
-                                                            o["mode"].data_ptr(), s),
-        "srbd_vfa_step_device", seeds, hips, params, contact=contact,
+        native, "srbd_vfa_step_device", seeds, hips, params, contact=contact,
         extra_inputs=lambda E: (("vfa", vfa, (E, VFA_BYTES), u8), ("stc", stc, (E, STC_BYTES), u8)),
         extra_outputs=lambda E: (("mode", (E,), i32),), **kw)
 

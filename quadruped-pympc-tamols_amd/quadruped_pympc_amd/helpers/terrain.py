@@ -98,24 +98,31 @@ def stepping_stones_scene(radius=0.15, spacing=0.40, per_row=3, top=0.05, gap=-0
     return dict(prims=prims, has_ground=True, ground_z=gap)
 
 
+def _scene_arrays(prims, hfield):
+    """The C arrays of one scene's keyword arguments: (TerrainPrim array, count, height field or None, nx, ny, x0, y0,
+    dx, dy), as ``srbd_terrain_create`` and ``srbd_terrain_scene`` take them."""
+    prims = list(prims)
+    arr = (_lib.TerrainPrim * max(1, len(prims)))()
+    for i, p in enumerate(prims):
+        arr[i] = _lib.TerrainPrim(int(p["type"]), 0, float(p["cx"]), float(p["cy"]), float(p["cz"]),
+                                  float(p["a"]), float(p.get("b", 0.0)), float(p["c"]), float(p.get("yaw", 0.0)))
+    hf = None
+    nx = ny = 0
+    x0 = y0 = dx = dy = 0.0
+    if hfield is not None:
+        hf = np.ascontiguousarray(hfield["z"], dtype=np.float64)
+        nx, ny = hf.shape
+        x0, y0, dx, dy = (float(hfield[k]) for k in ("x0", "y0", "dx", "dy"))
+    return arr, len(prims), hf, nx, ny, x0, y0, dx, dy
+
+
 class GpuTerrain:
     """A device-resident scene (``srbd_terrain``); ``patches`` casts one vertical ray per patch point."""
 
     def __init__(self, prims=(), has_ground=True, ground_z=0.0, hfield=None, miss_z=float("nan"), device_id=0):
-        prims = list(prims)
-        arr = (_lib.TerrainPrim * max(1, len(prims)))()
-        for i, p in enumerate(prims):
-            arr[i] = _lib.TerrainPrim(int(p["type"]), 0, float(p["cx"]), float(p["cy"]), float(p["cz"]),
-                                      float(p["a"]), float(p.get("b", 0.0)), float(p["c"]), float(p.get("yaw", 0.0)))
-        hf = None
-        nx = ny = 0
-        x0 = y0 = dx = dy = 0.0
-        if hfield is not None:
-            hf = np.ascontiguousarray(hfield["z"], dtype=np.float64)
-            nx, ny = hf.shape
-            x0, y0, dx, dy = (float(hfield[k]) for k in ("x0", "y0", "dx", "dy"))
+        arr, nprims, hf, nx, ny, x0, y0, dx, dy = _scene_arrays(prims, hfield)
         h = C.c_void_p()
-        rc = _lib.lib.srbd_terrain_create(int(device_id), arr, len(prims), int(bool(has_ground)), float(ground_z),
+        rc = _lib.lib.srbd_terrain_create(int(device_id), arr, nprims, int(bool(has_ground)), float(ground_z),
                                           _lib.dptr(hf), nx, ny, x0, y0, dx, dy, float(miss_z), C.byref(h))
         if rc != _lib.OK:
             msg = _lib.lib.srbd_terrain_last_error(None)
@@ -141,6 +148,47 @@ class GpuTerrain:
     def close(self):
         if getattr(self, "h", None):
             _lib.lib.srbd_terrain_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class GpuTerrainSet:
+    """A device-resident, immutable set of scenes (``srbd_terrain_set``) for the batched searches with one scene per
+    environment: ``tamols_batch_device`` / ``vfa_step_device`` (and ``BatchedVisualFootholdAdaptation``) take it as
+    ``terrain`` together with ``scene_ids``, the (E,) int32 device tensor of every environment's scene index.
+    ``scenes``: a sequence of the keyword dicts ``GpuTerrain`` takes (prims, has_ground, ground_z, hfield, miss_z)."""
+
+    def __init__(self, scenes, device_id=0):
+        scenes = [dict(s) for s in scenes]
+        for i, s in enumerate(scenes):
+            unknown = set(s) - {"prims", "has_ground", "ground_z", "hfield", "miss_z"}
+            if unknown:
+                raise ValueError(f"scene {i}: unknown keys {sorted(unknown)}")
+        arr = (_lib.TerrainScene * max(1, len(scenes)))()
+        keep = []  # the scenes' arrays, alive until the call has copied them
+        for i, s in enumerate(scenes):
+            prims, nprims, hf, nx, ny, x0, y0, dx, dy = _scene_arrays(s.get("prims", ()), s.get("hfield"))
+            keep.append((prims, hf))
+            arr[i] = _lib.TerrainScene(C.cast(prims, C.POINTER(_lib.TerrainPrim)) if nprims else None, nprims,
+                                       int(bool(s.get("has_ground", True))), float(s.get("ground_z", 0.0)),
+                                       _lib.dptr(hf), nx, ny, x0, y0, dx, dy, float(s.get("miss_z", float("nan"))))
+        h = C.c_void_p()
+        rc = _lib.lib.srbd_terrain_set_create(int(device_id), arr, len(scenes), C.byref(h))
+        if rc != _lib.OK:
+            msg = _lib.lib.srbd_terrain_set_last_error(None)
+            raise RuntimeError(f"srbd_terrain_set_create failed ({rc}): {msg.decode() if msg else ''}")
+        self.h = h
+        self.device_id = int(device_id)
+        self.num_scenes = len(scenes)
+
+    def close(self):
+        if getattr(self, "h", None):
+            _lib.lib.srbd_terrain_set_destroy(self.h)
             self.h = None
 
     def __del__(self):

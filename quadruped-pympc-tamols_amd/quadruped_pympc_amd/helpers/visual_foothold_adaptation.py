@@ -406,7 +406,8 @@ class BatchedVisualFootholdAdaptation:
             state.view(torch.int32)[:, o:o + 4].zero_()
 
     def step_device(self, seeds, hips, forward_vel, base_position, current_contact, current_feet_pos, *, stc,
-                    terrain=None, yaws=None, heightmaps=None, ref=None, apex_interval=0.01, stream=None, **patch):
+                    terrain=None, yaws=None, heightmaps=None, ref=None, apex_interval=0.01, stream=None, scene_ids=None,
+                    **patch):
         """The reference's gated adaptation (wb_interface.py:232-246) of every environment, one launch enqueued on
         ``stream`` (``srbd_vfa_step_device``); nothing is synchronised.  The arguments are
         ``compute_adaptation_device``'s, ``current_contact`` required; ``stc`` is the
@@ -417,7 +418,7 @@ class BatchedVisualFootholdAdaptation:
         (E, 4, 3), boxes (E, 4, 2, 3), valid (E, 4) int32, mode (E,) int32 of ``_lib.VFA_SEARCH`` / ``VFA_HOLD`` /
         ``VFA_PASS``); a leg whose last search found no candidate returns valid 0 with the box of its last feasible
         search (NaN if none).  ``ref``'s feet receive the footholds.  ``mode`` is allocated once and rewritten by
-        every call."""
+        every call.  ``terrain`` a GpuTerrainSet with ``scene_ids``: a searching environment searches on its own scene."""
         if getattr(seeds, "shape", (0,))[0] != self.num_envs:
             raise ValueError(f"seeds must hold {self.num_envs} environments, got {tuple(getattr(seeds, 'shape', ()))}")
         given = dict(patch.pop("out", None) or {})
@@ -426,18 +427,21 @@ class BatchedVisualFootholdAdaptation:
         out = _lib.vfa_step_device(self.state, getattr(stc, "state", stc), seeds, hips, self._params(), current_contact,
                                    apex_interval=apex_interval, terrain=terrain, yaws=yaws, heightmaps=heightmaps,
                                    forward_vel=forward_vel, base_pos=base_position, feet=current_feet_pos, ref=ref,
-                                   stream=stream, out=given, **patch)
+                                   stream=stream, out=given, scene_ids=scene_ids, **patch)
         self._mode = out["mode"]
         return out["footholds"], out["boxes"], out["valid"], out["mode"]
 
     def compute_adaptation_device(self, seeds, hips, forward_vel, base_position, current_contact, current_feet_pos, *,
-                                  terrain=None, yaws=None, heightmaps=None, ref=None, stream=None, **patch):
+                                  terrain=None, yaws=None, heightmaps=None, ref=None, stream=None, scene_ids=None,
+                                  **patch):
         """One search per environment, enqueued on ``stream`` (None: torch's current stream); nothing is synchronised.
         seeds / hips (E, 4, 3) float64 device tensors (legs FL FR RL RR); forward_vel / base_position (E, 3) float64,
         current_contact (E, 4) float32 as the device gait generator writes it, current_feet_pos (E, 4, 3) float64, each
         of them or None as in ``compute_adaptation``.  Either ``terrain`` (a GpuTerrain) with ``yaws`` (E,) -- the
         patches are raycast around the seeds; ``patch`` may give rows, cols, dist_x, dist_y, ray_z -- or ``heightmaps``
-        (E, 4, rows, cols, 3).  ``ref`` (E, 24) float64: the reference ``prepare_state_and_reference_device`` takes,
+        (E, 4, rows, cols, 3).  One scene per environment: ``terrain`` a GpuTerrainSet and ``scene_ids`` the (E,) int32
+        device tensor of the environments' scene indices, read in stream order (``scene_ids[done] = ...`` at a reset is
+        an ordinary tensor operation on the same stream).  ``ref`` (E, 24) float64: the reference ``prepare_state_and_reference_device`` takes,
         whose feet (entries 12..23) receive the footholds.  Returns (footholds (E, 4, 3), boxes (E, 4, 2, 3) -- NaN
         for a leg without a feasible candidate, whose foothold is the seed at its terrain height --, valid (E, 4)
         int32)."""
@@ -445,5 +449,5 @@ class BatchedVisualFootholdAdaptation:
             raise ValueError(f"seeds must hold {self.num_envs} environments, got {tuple(getattr(seeds, 'shape', ()))}")
         out = _lib.tamols_batch_device(seeds, hips, self._params(), terrain=terrain, yaws=yaws, heightmaps=heightmaps,
                                        forward_vel=forward_vel, base_pos=base_position, contact=current_contact,
-                                       feet=current_feet_pos, ref=ref, stream=stream, **patch)
+                                       feet=current_feet_pos, ref=ref, stream=stream, scene_ids=scene_ids, **patch)
         return out["footholds"], out["boxes"], out["valid"]

@@ -14,6 +14,15 @@ is inside them); the sequential kind is wall time, each call waiting for its out
 per kind; the median block is reported, per call and per environment, in us.  One run on one box.
 
   python scripts/batch_foothold_timing.py [--envs 1 16 256 1024 4096] [--out profiles/batch_foothold.json]
+
+--scenes: one scene per environment instead (srbd_tamols_batch_scenes_device) -> profiles/batch_foothold_scenes.json.
+At E = 1024 (--envs to change), alternating blocks of the same 100 back-to-back calls on the same inputs:
+
+  shared          srbd_tamols_batch_device on the stepping-stones GpuTerrain (batch_terrain above)
+  scenes_1        the scenes call on a set of that one scene, every index 0
+  scenes_8        the scenes call on a set of 8 variants of the course (stone spacing, radius and top), round-robin
+
+  python scripts/batch_foothold_timing.py --scenes [--envs 1024] [--out profiles/batch_foothold_scenes.json]
 """
 from __future__ import annotations
 
@@ -31,10 +40,11 @@ sys.path[:0] = [os.path.join(ROOT, "quadruped-pympc-tamols_amd"), ROOT]
 import torch  # noqa: E402  (torch first: one HIP runtime per process)
 
 from quadruped_pympc_amd import _lib, config  # noqa: E402
-from quadruped_pympc_amd.helpers.terrain import GpuTerrain  # noqa: E402
+from quadruped_pympc_amd.helpers.terrain import GpuTerrain, GpuTerrainSet, stepping_stones_scene  # noqa: E402
 from quadruped_pympc_amd.helpers.visual_foothold_adaptation import TamolsSearch, tamols_params_struct  # noqa: E402
 
 OUT = os.path.join(ROOT, "profiles", "batch_foothold.json")
+OUT_SCENES = os.path.join(ROOT, "profiles", "batch_foothold_scenes.json")
 CALLS, WARMUP, BLOCKS = 100, 10, 3
 FEET = np.array([[0.62, 0.13, 0.0], [0.62, -0.13, 0.0], [0.24, 0.13, 0.0], [0.24, -0.13, 0.0]])
 
@@ -94,14 +104,80 @@ def measure(E, terrain, search, p):
     return row
 
 
+def measure_scenes(E, p):
+    inp = inputs(E)
+    d = {k: torch.from_numpy(np.ascontiguousarray(v)).cuda() for k, v in inp.items()}
+    stream = torch.cuda.Stream()
+    common = dict(forward_vel=d["vel"], base_pos=d["base"], contact=d["contact"], feet=d["feet"], stream=stream)
+    variants = [stepping_stones_scene(spacing=0.40 + 0.01 * k, radius=0.15 - 0.005 * k, top=0.05 + 0.005 * k)
+                for k in range(8)]
+    terrain, one, eight = GpuTerrain(**variants[0]), GpuTerrainSet(variants[:1]), GpuTerrainSet(variants)
+    ids = {1: torch.zeros(E, dtype=torch.int32, device="cuda"),
+           8: (torch.arange(E, device="cuda") % 8).to(torch.int32).contiguous()}
+    forms = dict(shared=dict(terrain=terrain), scenes_1=dict(terrain=one, scene_ids=ids[1]),
+                 scenes_8=dict(terrain=eight, scene_ids=ids[8]))
+    first = _lib.tamols_batch_device(d["seeds"], d["hips"], p, yaws=d["yaws"], **forms["shared"], **common)
+    stream.synchronize()
+    out = {k: first[k] for k in ("footholds", "boxes", "valid")}
+
+    def batch(n, kind):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record(stream)
+        for _ in range(n):
+            _lib.tamols_batch_device(d["seeds"], d["hips"], p, yaws=d["yaws"], out=out, **forms[kind], **common)
+        t1.record(stream)
+        stream.synchronize()
+        return t0.elapsed_time(t1) * 1e3 / n  # us per call
+
+    try:
+        for kind in forms:
+            batch(WARMUP, kind)
+        s = {kind: [] for kind in forms}
+        for _ in range(BLOCKS):
+            for kind in forms:
+                s[kind].append(batch(CALLS, kind))
+    finally:
+        for t in (terrain, one, eight):
+            t.close()
+    row = {"num_envs": E}
+    for k, v in s.items():
+        m = float(np.median(v))
+        row[k] = {"us_per_call": round(m, 2), "us_per_env": round(m / E, 3), "blocks": [round(x, 2) for x in v]}
+    return row
+
+
+def main_scenes(args, p):
+    rows = [measure_scenes(E, p) for E in (args.envs or [1024])]
+    doc = {"workload": {"robot": "go2", "rows": 13, "cols": 7, "scene": "stepping_stones",
+                        "scenes_8": "8 variants of the course (spacing, radius, top), assigned round-robin"},
+           "device": torch.cuda.get_device_name(0), "calls": CALLS, "warmup": WARMUP, "blocks": BLOCKS,
+           "note": "one run on one box; device time between events around back-to-back calls, median block",
+           "rows": rows}
+    print(f"{'E':>6} {'shared/call':>12} {'scenes S=1':>11} {'scenes S=8':>11}   (us)")
+    for r in rows:
+        print(f"{r['num_envs']:>6} {r['shared']['us_per_call']:>12} {r['scenes_1']['us_per_call']:>11} "
+              f"{r['scenes_8']['us_per_call']:>11}")
+    out = args.out or OUT_SCENES
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(doc, f, indent=1)
+        f.write("\n")
+    print(json.dumps({"written": os.path.relpath(out, ROOT)}))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--envs", type=int, nargs="*", default=[1, 16, 256, 1024, 4096])
-    ap.add_argument("--out", default=OUT)
+    ap.add_argument("--envs", type=int, nargs="*", default=None)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--scenes", action="store_true", help="time the one-scene-per-environment call instead")
     args = ap.parse_args()
     p = dict(config.simulation_params["tamols_params"])
     p["h_des"] = 0.25
     p = tamols_params_struct(p, "go2")
+    if args.scenes:
+        return main_scenes(args, p)
+    args.envs = args.envs or [1, 16, 256, 1024, 4096]
+    args.out = args.out or OUT
     terrain, search = GpuTerrain.stepping_stones(), TamolsSearch(0)
     try:
         rows = [measure(E, terrain, search, p) for E in args.envs]
