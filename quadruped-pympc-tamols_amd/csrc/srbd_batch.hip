@@ -6,12 +6,11 @@
 // srbd_step's bit for bit.
 //   batch_copy_kernel       the E step inputs, host-mapped staging -> device
 //   batch_rng_kernel        rng_items per environment, keyed by in[e]'s seed and counter
-//   batch_transpose_kernel  injected noise (row-major) -> SoA per environment
-//   batch_rollout_kernel    rollout_quad_kernel's plain form (MPPI / random sampling) and, with EXT, its form with
-//                           the opt-in cost terms: one 64-sample leaf per 256-thread block, leaf records only (no
-//                           in-launch fold, merge or draws: with E x nleaf blocks in flight the tail those forms
-//                           shorten is amortised); with CEMT its CEM form (srbd_batch_create_cem): sigma scaling
-//                           and the K smallest keys of every leaf
+//   batch_transpose_kernel  injected noise (row-major) -> SoA per environment (transpose_tile)
+//   batch_rollout_kernel    rollout_quad_kernel's horizon (MPPI / random sampling, CEM, the opt-in cost terms), with
+//                           that kernel's template parameter order: one 64-sample leaf per 256-thread block, leaf
+//                           records only (no in-launch fold, merge or draws: with E x nleaf blocks in flight the tail
+//                           those forms shorten is amortised)
 //   batch_rollout_ga_kernel rollout_ga_quad_kernel (gait-adaptive sampling), the same block and record layout
 //   batch_merge_kernel      one block per environment: merge_body over its leaf records -> out[e]; the last block to
 //                           finish publishes the step's sequence word
@@ -58,121 +57,15 @@ struct BatchPackConst {
     float mg;
     int H, P;
 };
-__global__ void __launch_bounds__(64) batch_pack_kernel(const srbd_batch_device_io io, const BatchPackConst pc, int vec,
-                                                        StepInput* __restrict__ in_arr) {
+// m: where mg and q_feet come from -- the batch's BatchPackConst, or with ENVT (srbd_batch_set_env_params)
+// environment e's record envs[e], as fill_input forms fzref and cost_feet from that record on the host.
+template <bool CEM, bool ENVT>
+__device__ __forceinline__ void batch_pack_body(const srbd_batch_device_io& io, int H, int P,
+                                                const std::conditional_t<ENVT, EnvModel, BatchPackConst>& m, int vec,
+                                                StepInput* in_arr, const srbd_batch_cem_io& cem, int svec) {
 #pragma clang fp contract(off)
     const int e = blockIdx.x, tid = threadIdx.x;
     StepInput* __restrict__ in = in_arr + e;
-    const float* __restrict__ st = io.states + 24 * (size_t)e;
-    const float* __restrict__ rf = io.refs + 24 * (size_t)e;
-    const float* __restrict__ bp = io.best_params + (size_t)e * pc.P;
-    static_assert(offsetof(StepInput, state) == 0 && offsetof(StepInput, ref) == 96, "state | ref head the input");
-    if (vec) {
-        if (tid < 12)
-            reinterpret_cast<float4*>(in)[tid] =
-                tid < 6 ? reinterpret_cast<const float4*>(st)[tid] : reinterpret_cast<const float4*>(rf)[tid - 6];
-        for (int i = tid; i < pc.P / 4; i += 64)
-            reinterpret_cast<float4*>(in->best)[i] = reinterpret_cast<const float4*>(bp)[i];
-    } else {
-        if (tid < 48) reinterpret_cast<float*>(in)[tid] = tid < 24 ? st[tid] : rf[tid - 24];
-        for (int i = tid; i < pc.P; i += 64) in->best[i] = bp[i];
-    }
-    if (tid < MAXH) {  // column n of the four legs
-        const int n = tid;
-        const float* __restrict__ ct = io.contacts + (size_t)e * 4 * io.contact_stride + n;
-        float c[4];
-#pragma unroll
-        for (int l = 0; l < 4; ++l) {
-            c[l] = n < pc.H ? ct[(size_t)l * io.contact_stride] : 0.0f;
-            in->contact[l][n] = c[l];
-        }
-        if (n < pc.H) in->fzref[n] = pc.mg / (((c[0] + c[1]) + c[2]) + c[3]);  // inf when no leg is in stance
-    } else if (tid == MAXH) {
-        float cf = 0.0f;
-#pragma unroll
-        for (int i = 12; i < 24; ++i) {
-            const float d = st[i] - rf[i];
-            cf = cf + (d * pc.q_feet[i - 12]) * d;
-        }
-        in->cost_feet = cf;
-        const uint64_t seed = io.seeds[e], counter = io.counters[e];
-        in->seed_lo = (uint32_t)seed;
-        in->seed_hi = (uint32_t)(seed >> 32);
-        in->ctr_lo = (uint32_t)counter;
-        in->ctr_hi = (uint32_t)(counter >> 32);
-        in->noise_scaled = io.noise ? 1 : 0;
-    }
-}
-// batch_pack_kernel restated with sigma (a sibling, so that kernel keeps its code and registers)
-__global__ void __launch_bounds__(64) batch_pack_cem_kernel(const srbd_batch_device_io io, const BatchPackConst pc,
-                                                            int vec, StepInput* __restrict__ in_arr,
-                                                            const srbd_batch_cem_io cem, int svec) {
-#pragma clang fp contract(off)
-    const int e = blockIdx.x, tid = threadIdx.x;
-    StepInput* __restrict__ in = in_arr + e;
-    if (cem.sigma_reset > 0.0f) {
-        for (int i = tid; i < pc.P; i += 64) in->sigma[i] = cem.sigma_reset;
-    } else {
-        const float* __restrict__ sp = cem.sigma + (size_t)e * pc.P;
-        if (svec)
-            for (int i = tid; i < pc.P / 4; i += 64)
-                reinterpret_cast<float4*>(in->sigma)[i] = reinterpret_cast<const float4*>(sp)[i];
-        else
-            for (int i = tid; i < pc.P; i += 64) in->sigma[i] = sp[i];
-    }
-    const float* __restrict__ st = io.states + 24 * (size_t)e;
-    const float* __restrict__ rf = io.refs + 24 * (size_t)e;
-    const float* __restrict__ bp = io.best_params + (size_t)e * pc.P;
-    static_assert(offsetof(StepInput, state) == 0 && offsetof(StepInput, ref) == 96, "state | ref head the input");
-    if (vec) {
-        if (tid < 12)
-            reinterpret_cast<float4*>(in)[tid] =
-                tid < 6 ? reinterpret_cast<const float4*>(st)[tid] : reinterpret_cast<const float4*>(rf)[tid - 6];
-        for (int i = tid; i < pc.P / 4; i += 64)
-            reinterpret_cast<float4*>(in->best)[i] = reinterpret_cast<const float4*>(bp)[i];
-    } else {
-        if (tid < 48) reinterpret_cast<float*>(in)[tid] = tid < 24 ? st[tid] : rf[tid - 24];
-        for (int i = tid; i < pc.P; i += 64) in->best[i] = bp[i];
-    }
-    if (tid < MAXH) {  // column n of the four legs
-        const int n = tid;
-        const float* __restrict__ ct = io.contacts + (size_t)e * 4 * io.contact_stride + n;
-        float c[4];
-#pragma unroll
-        for (int l = 0; l < 4; ++l) {
-            c[l] = n < pc.H ? ct[(size_t)l * io.contact_stride] : 0.0f;
-            in->contact[l][n] = c[l];
-        }
-        if (n < pc.H) in->fzref[n] = pc.mg / (((c[0] + c[1]) + c[2]) + c[3]);  // inf when no leg is in stance
-    } else if (tid == MAXH) {
-        float cf = 0.0f;
-#pragma unroll
-        for (int i = 12; i < 24; ++i) {
-            const float d = st[i] - rf[i];
-            cf = cf + (d * pc.q_feet[i - 12]) * d;
-        }
-        in->cost_feet = cf;
-        const uint64_t seed = io.seeds[e], counter = io.counters[e];
-        in->seed_lo = (uint32_t)seed;
-        in->seed_hi = (uint32_t)(seed >> 32);
-        in->ctr_lo = (uint32_t)counter;
-        in->ctr_hi = (uint32_t)(counter >> 32);
-        in->noise_scaled = io.noise ? 1 : 0;
-    }
-}
-
-// batch_pack_kernel / batch_pack_cem_kernel restated for a batch with per-environment parameters
-// (srbd_batch_set_env_params): fzref from envs[e].mg and cost_feet from envs[e].q_feet, as fill_input forms them from
-// that environment's record on the host; everything else is those kernels' (siblings again, so they keep their code).
-template <bool CEM>
-__global__ void __launch_bounds__(64) batch_pack_env_kernel(const srbd_batch_device_io io, int H, int P, int vec,
-                                                            StepInput* __restrict__ in_arr,
-                                                            const EnvModel* __restrict__ envs,
-                                                            const srbd_batch_cem_io cem, int svec) {
-#pragma clang fp contract(off)
-    const int e = blockIdx.x, tid = threadIdx.x;
-    StepInput* __restrict__ in = in_arr + e;
-    const EnvModel* __restrict__ em = envs + e;
     if constexpr (CEM) {
         if (cem.sigma_reset > 0.0f) {
             for (int i = tid; i < P; i += 64) in->sigma[i] = cem.sigma_reset;
@@ -188,6 +81,7 @@ __global__ void __launch_bounds__(64) batch_pack_env_kernel(const srbd_batch_dev
     const float* __restrict__ st = io.states + 24 * (size_t)e;
     const float* __restrict__ rf = io.refs + 24 * (size_t)e;
     const float* __restrict__ bp = io.best_params + (size_t)e * P;
+    static_assert(offsetof(StepInput, state) == 0 && offsetof(StepInput, ref) == 96, "state | ref head the input");
     if (vec) {
         if (tid < 12)
             reinterpret_cast<float4*>(in)[tid] =
@@ -207,13 +101,13 @@ __global__ void __launch_bounds__(64) batch_pack_env_kernel(const srbd_batch_dev
             c[l] = n < H ? ct[(size_t)l * io.contact_stride] : 0.0f;
             in->contact[l][n] = c[l];
         }
-        if (n < H) in->fzref[n] = em->mg / (((c[0] + c[1]) + c[2]) + c[3]);  // inf when no leg is in stance
+        if (n < H) in->fzref[n] = m.mg / (((c[0] + c[1]) + c[2]) + c[3]);  // inf when no leg is in stance
     } else if (tid == MAXH) {
         float cf = 0.0f;
 #pragma unroll
         for (int i = 12; i < 24; ++i) {
             const float d = st[i] - rf[i];
-            cf = cf + (d * em->q_feet[i - 12]) * d;
+            cf = cf + (d * m.q_feet[i - 12]) * d;
         }
         in->cost_feet = cf;
         const uint64_t seed = io.seeds[e], counter = io.counters[e];
@@ -223,6 +117,22 @@ __global__ void __launch_bounds__(64) batch_pack_env_kernel(const srbd_batch_dev
         in->ctr_hi = (uint32_t)(counter >> 32);
         in->noise_scaled = io.noise ? 1 : 0;
     }
+}
+__global__ void __launch_bounds__(64) batch_pack_kernel(const srbd_batch_device_io io, const BatchPackConst pc, int vec,
+                                                        StepInput* __restrict__ in_arr) {
+    batch_pack_body<false, false>(io, pc.H, pc.P, pc, vec, in_arr, srbd_batch_cem_io{nullptr, 0.0f, 0}, 0);
+}
+__global__ void __launch_bounds__(64) batch_pack_cem_kernel(const srbd_batch_device_io io, const BatchPackConst pc,
+                                                            int vec, StepInput* __restrict__ in_arr,
+                                                            const srbd_batch_cem_io cem, int svec) {
+    batch_pack_body<true, false>(io, pc.H, pc.P, pc, vec, in_arr, cem, svec);
+}
+template <bool CEM>
+__global__ void __launch_bounds__(64) batch_pack_env_kernel(const srbd_batch_device_io io, int H, int P, int vec,
+                                                            StepInput* __restrict__ in_arr,
+                                                            const EnvModel* __restrict__ envs,
+                                                            const srbd_batch_cem_io cem, int svec) {
+    batch_pack_body<CEM, true>(io, H, P, envs[(int)blockIdx.x], vec, in_arr, cem, svec);
 }
 
 // srbd_batch_set_env_params_device: one thread per environment.  A selected environment's record (39 floats of the
@@ -339,46 +249,25 @@ __global__ void __launch_bounds__(256) batch_rng_kernel(const ModelConst mc, con
     rng_items(mc, in + e, job, blockIdx.x * 256 + threadIdx.x, gridDim.x * 256);
 }
 
-// transpose_kernel (srbd_kernels.hip) per environment: row-major (n x P) -> SoA [P][ldn]
+// transpose_kernel with one matrix per environment on blockIdx.z
 __global__ void __launch_bounds__(256) batch_transpose_kernel(const float* __restrict__ src, int n, int P, int ldn,
                                                               float* __restrict__ dst) {
-    __shared__ float tile[32][33];
-    src += (size_t)blockIdx.z * n * P;
-    dst += (size_t)blockIdx.z * P * ldn;
-    const int bx = blockIdx.x * 32, by = blockIdx.y * 32;  // bx: rows (samples), by: params
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
-    for (int i = ty; i < 32; i += 8) {
-        const int row = bx + i, col = by + tx;
-        tile[i][tx] = (row < n && col < P) ? src[(size_t)row * P + col] : 0.0f;
-    }
-    __syncthreads();
-    for (int i = ty; i < 32; i += 8) {
-        const int col = by + i, row = bx + tx;
-        if (col < P && row < n) dst[(size_t)col * ldn + row] = tile[tx][i];
-    }
+    transpose_tile(src + (size_t)blockIdx.z * n * P, n, P, ldn, dst + (size_t)blockIdx.z * P * ldn, blockIdx.x * 32,
+                   blockIdx.y * 32);
 }
 
-// rollout_quad_kernel<KIND, HT, ST, CEMT = false, EXT = false> (srbd_kernels.hip) with the environment on
-// blockIdx.y: the leg-parallel force phase, the component-parallel rigid-body step, the tracking cost and the leaf
-// record, statement for statement, so the costs and records are that kernel's bits.  Left out: the step input by
-// value and the in-launch draws, folds and merges.
-// EXT (srbd_batch_set_cost_terms): that kernel's EXT form -- the component-parallel force phase with this lane's
-// component of extra_cost_step per leg, each step's terms pinned to their step by an empty asm on the accumulator,
-// no LDS noise stage, and for zero-order a rolling window of four prefetched slots instead of the whole horizon
-// (without the pin and the window the unrolled horizon spills: see rollout_quad_kernel).
-// CEMT (srbd_batch_create_cem): that kernel's CEMT form -- unscaled device draws multiplied
-// by sigma_j where a parameter is decoded (at use from the LDS copy `sls` in the LDS-staged zero-order form, at
-// load_slot in the other specialised shapes, at the read in the generic one; injected noise, noise_scaled = 1, is used
-// as given), the windowed slot loads of the specialised cubic shape (CWIN), and each leaf's K smallest keys in its
-// record (block_epilogue<true>).  The parameter trails and defaults to false: every statement it adds sits under
-// `if constexpr (CEMT)`, so the MPPI / random-sampling instantiations compile to the code they were (their mangled
-// names gain the argument).
+// rollout_quad_kernel<KIND, HT, ST, CEMT, EXT> (srbd_kernels.hip) with the environment on blockIdx.y and that
+// kernel's horizon restated, so the costs and records are its bits; CEMT (srbd_batch_create_cem) and EXT
+// (srbd_batch_set_cost_terms) are that kernel's forms, and the measured reasons for the pin, the slot windows and
+// CLEAD are written there.  Added here: the environment's offsets, the model view and KRE (below).  Left out: the
+// step input by value and the in-launch draws, folds and merges.  (One shared body for both kernels was tried and
+// dropped: inlined from a common function the horizon allocates more registers or spills in several instantiations
+// of either file -- DESIGN section 4.)
 // ENVT (srbd_batch_set_env_params): the robot's and the cost's constants -- inv_m, the inertia and its inverse, the
 // force bounds, mu, Q -- come from envs[env], this block's environment record, instead of mc.  The address is
 // block-uniform and the array is read-only through a restrict pointer, so the values are scalar loads made once ahead
-// of the horizon (they take the SGPRs the kernel argument's fields took).  The parameter trails and defaults to
-// false, as CEMT does: the other instantiations take a model view of mc (model_view) and compile to the code they
-// were; they are passed envs == NULL and never read it.
+// of the horizon (they take the SGPRs the kernel argument's fields took).  The other instantiations take a model view
+// of mc (model_view); they are passed envs == NULL and never read it.
 template <bool ENVT>
 __device__ __forceinline__ auto model_view(const ModelConst& mc, const EnvModel* __restrict__ envs, int env) {
     if constexpr (ENVT)
@@ -386,7 +275,7 @@ __device__ __forceinline__ auto model_view(const ModelConst& mc, const EnvModel*
     else
         return McConst{mc};
 }
-template <int KIND, int HT, int ST, bool EXT = false, bool CEMT = false, bool ENVT = false>
+template <int KIND, int HT, int ST, bool CEMT, bool EXT, bool ENVT>  // rollout_quad_kernel's order; ENVT trails
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) batch_rollout_kernel(
     const ModelConst mc, const StepInput* __restrict__ in_arr, const float* __restrict__ noise_arr,
     float* __restrict__ costs_arr, float* __restrict__ recs_arr, int rec_stride,
@@ -931,10 +820,10 @@ void launch_batch_rollout(const ModelConst& mc, const StepInput* in, const float
             hipLaunchKernelGGL((batch_rollout_kernel<K, HH, SS, true, true, ENVT>), grid, dim3(256), 0, s, mc,    \
                                in, noise, costs, recs, rec_stride, EV);                                           \
         else if (cem)                                                                                             \
-            hipLaunchKernelGGL((batch_rollout_kernel<K, HH, SS, false, true, ENVT>), grid, dim3(256), 0, s, mc,   \
+            hipLaunchKernelGGL((batch_rollout_kernel<K, HH, SS, true, false, ENVT>), grid, dim3(256), 0, s, mc,   \
                                in, noise, costs, recs, rec_stride, EV);                                           \
         else if (mc.cost_on)                                                                                      \
-            hipLaunchKernelGGL((batch_rollout_kernel<K, HH, SS, true, false, ENVT>), grid, dim3(256), 0, s, mc,   \
+            hipLaunchKernelGGL((batch_rollout_kernel<K, HH, SS, false, true, ENVT>), grid, dim3(256), 0, s, mc,   \
                                in, noise, costs, recs, rec_stride, EV);                                           \
         else                                                                                                      \
             hipLaunchKernelGGL((batch_rollout_kernel<K, HH, SS, false, false, ENVT>), grid, dim3(256), 0, s, mc,  \

@@ -802,4 +802,21 @@ __device__ __forceinline__ void ga_contact_masks(const StepInput* __restrict__ i
         }
 }
 
+// One 32 x 32 tile of injected noise, row-major (n x P) -> SoA [P][ldn], by a 256-thread block: tile (bx, by) of
+// rows (samples) x params.  transpose_kernel and batch_transpose_kernel (one matrix per blockIdx.z) call it.
+__device__ __forceinline__ void transpose_tile(const float* __restrict__ src, int n, int P, int ldn,
+                                               float* __restrict__ dst, int bx, int by) {
+    __shared__ float tile[32][33];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
+    for (int i = ty; i < 32; i += 8) {
+        const int row = bx + i, col = by + tx;
+        tile[i][tx] = (row < n && col < P) ? src[(size_t)row * P + col] : 0.0f;
+    }
+    __syncthreads();
+    for (int i = ty; i < 32; i += 8) {
+        const int col = by + i, row = bx + tx;
+        if (col < P && row < n) dst[(size_t)col * ldn + row] = tile[tx][i];
+    }
+}
+
 }  // namespace srbd

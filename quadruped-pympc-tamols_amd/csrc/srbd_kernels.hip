@@ -27,18 +27,7 @@ __global__ void __launch_bounds__(256) rng_kernel(const ModelConst mc, const Ste
 // row-major (n x P) -> SoA [P][ldn]
 __global__ void __launch_bounds__(256) transpose_kernel(const float* __restrict__ src, int n, int P, int ldn,
                                                         float* __restrict__ dst) {
-    __shared__ float tile[32][33];
-    const int bx = blockIdx.x * 32, by = blockIdx.y * 32;  // bx: rows (samples), by: params
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
-    for (int i = ty; i < 32; i += 8) {
-        const int row = bx + i, col = by + tx;
-        tile[i][tx] = (row < n && col < P) ? src[(size_t)row * P + col] : 0.0f;
-    }
-    __syncthreads();
-    for (int i = ty; i < 32; i += 8) {
-        const int col = by + i, row = bx + tx;
-        if (col < P && row < n) dst[(size_t)col * ldn + row] = tile[tx][i];
-    }
+    transpose_tile(src, n, P, ldn, dst, blockIdx.x * 32, blockIdx.y * 32);
 }
 
 
