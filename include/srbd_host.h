@@ -7,6 +7,7 @@
  *   srbd_pgg_run                     <- PeriodicGaitGenerator.run               :48-76
  *   srbd_pgg_set_phase_signal        <- PeriodicGaitGenerator.set_phase_signal  :78-87
  *   srbd_pgg_contact_sequence        <- PeriodicGaitGenerator.compute_contact_sequence :93-118
+ *   srbd_pgg_start_stop              <- PeriodicGaitGenerator.update_start_and_stop    :128-196
  *   srbd_prepare_state               <- Sampling_MPC.prepare_state_and_reference
  *                                       quadruped_pympc/controllers/sampling/centroidal_nmpc_jax.py:563-627
  *   srbd_frg_init / _compute / _update_lift_off / _update_touch_down / _mean
@@ -85,6 +86,29 @@ int srbd_pgg_set_phase_signal(srbd_pgg* g, const double phase[4], const int32_t*
  */
 int srbd_pgg_contact_sequence(srbd_pgg* g, const double* dts, const int32_t* lens, int32_t n_dts, double* out,
                               int32_t out_cap);
+/*
+ * update_start_and_stop (periodic_gait_generator.py:128-196; WBInterface.update_state_and_reference calls it at
+ * wb_interface.py:175-189 when pgg.start_and_stop_activated), statement for statement (csrc/srbd_start_stop.h, which
+ * the device forms srbd_pgg_start_stop_device and srbd_wb_update_device of srbd_mpc.h compile too).
+ * Stop condition, all of: norm(ref_lin) == 0.0; norm(ref_ang) == 0.0; norm(base_lin_vel) < 0.1; norm(base_ang_vel) <
+ * 0.1; |euler[0]| < 0.05; |euler[1]| < 0.05; the four current contacts sum to 4; and for every leg the horizontal-frame
+ * distance of foot and hip < 0.06, where a point's horizontal-frame xy is R_W2H @ (p_xy - base_xy) with cos / sin of
+ * euler[2] from csrc/yaw_sincos.h (each row two products summed left to right), the foot's y then shifted by
+ * hip_offset (- for FL and RL, + for FR and RR), and the distance sqrt(dx dx + dy dy).  A norm is sqrt((x x + y y) +
+ * z z): a command whose squares underflow counts as zero, as in NumPy.  A NaN anywhere makes the condition false.
+ *   condition holds          gait_type = SRBD_GAIT_FULL_STANCE, then srbd_pgg_reset's assignments; on every such call,
+ *                            as the reference; previous_gait_type is left alone.  Returns 1.
+ *   else, in FULL_STANCE     gait_type = previous_gait_type, then srbd_pgg_reset's assignments.  Returns 2.
+ *   otherwise                nothing is written.  Returns 0.
+ * feet and hips are 4 x 3 (z unused); ref_lin / ref_ang are the (modulated) command.  The reference's mean of the
+ * four distances is never read and is not formed.  The comparisons agree with the reference's wherever the compared
+ * quantity is further from its threshold than the rounding of cos / sin and of the sums.
+ * SRBD_E_INVALID (nothing written): a NULL pointer.
+ */
+int srbd_pgg_start_stop(srbd_pgg* g, const double* feet /* 4 x 3 */, const double* hips /* 4 x 3 */, double hip_offset,
+                        const double base_pos[3], const double euler[3], const double base_lin_vel[3],
+                        const double base_ang_vel[3], const double ref_lin[3], const double ref_ang[3],
+                        const double current_contact[4]);
 
 /*
  * prepare_state_and_reference: state_in = [position, linear_velocity, orientation, angular_velocity,
@@ -303,8 +327,9 @@ int srbd_gait_apply_freq(srbd_pgg* pgg, srbd_frg* frg /* or NULL */, srbd_stc* s
  * Stale constraint: a search that finds no candidate for a leg leaves that leg's box as it was (the reference assigns
  * footholds_constraints only for a feasible leg, :209-228), so the box returned with valid 0 is the last feasible
  * search's, or NaN if there was none.  Neither the reset nor a pass-through touches boxes or valid.
- * Out of scope: the 'height' and 'vfa' strategies, the early-stance detector, start-and-stop and inverse kinematics
- * (the per-environment masked reset of this and the loop's other state is srbd_loop_reset, below). */
+ * Out of scope: the 'height' and 'vfa' strategies, the early-stance detector and inverse kinematics (start-and-stop
+ * is the gait generator's, srbd_pgg_start_stop above, and does not touch this state;
+ * the per-environment masked reset of this and the loop's other state is srbd_loop_reset, below). */
 enum { SRBD_VFA_PASS = 0, SRBD_VFA_SEARCH = 1, SRBD_VFA_HOLD = 2 };
 typedef struct srbd_vfa {
     int32_t initialized[4]; /* 0 / 1, all four equal (16 bytes: the doubles behind them stay aligned) */
@@ -351,7 +376,8 @@ int srbd_vfa_commit(srbd_vfa* g, int32_t mode, const double seeds[12], const dou
  * header's own (within 1 ulp of the true value; srbd_selftest_atan shows it), the yaw rotation is written out where the
  * reference calls a BLAS product, and the terrain rotation is Ry(pitch) Rx(roll) written out where the reference goes
  * through scipy's quaternion.
- * Out of scope: update_start_and_stop, the early-stance detector, inverse kinematics and the kinodynamic branch. */
+ * Out of scope: the early-stance detector, inverse kinematics and the kinodynamic branch.  update_start_and_stop,
+ * which the reference runs between the modulator and the gait generator, is srbd_pgg_start_stop above. */
 typedef struct srbd_terrain_est {
     double roll, pitch, height;               /* the three filtered values, 0 after init */
     int32_t roll_activated, pitch_activated;  /* 0 and 1 after init; a switched-off angle is set to 0.0 every step */

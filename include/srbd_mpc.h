@@ -801,7 +801,8 @@ int srbd_tamols_batch_device(srbd_terrain* terrain /* NULL: patch form */, const
  *   SRBD_E_INVALID (before any HIP call): everything srbd_tamols_batch_device refuses; a NULL d_vfa, d_stc or
  *   io->contact; an apex_interval that is not finite.  A failed launch: SRBD_E_HIP, or SRBD_E_NODEVICE where no device
  *   exists.
- *   Out of scope: the 'height' and 'vfa' strategies; the early-stance detector, start-and-stop and inverse kinematics;
+ *   Out of scope: the 'height' and 'vfa' strategies; the early-stance detector and inverse kinematics (start-and-stop
+ *   is the gait generator's: srbd_pgg_start_stop_device and srbd_wb_update_device, below);
  *   compacting the searching environments into a smaller grid (their count would have to reach the host).  The
  *   per-environment masked reset of d_vfa and the loop's other device state is srbd_loop_reset_device, below. */
 struct srbd_vfa;
@@ -1247,6 +1248,128 @@ typedef struct srbd_loop_reset_io {
     int32_t num_params, n_contact_rows;
 } srbd_loop_reset_io;
 int srbd_loop_reset_device(int32_t num_envs, const srbd_loop_reset_io* io, void* hip_stream);
+
+/* ---- Start-and-stop, and the whole of WBInterface.update_state_and_reference in one launch.
+ *   srbd_pgg_start_stop_device <- PeriodicGaitGenerator.update_start_and_stop, periodic_gait_generator.py:128-196
+ *                                 (called wb_interface.py:175-189)
+ *   srbd_wb_update_device      <- WBInterface.update_state_and_reference, wb_interface.py:168-298, the visual foothold
+ *                                 adaptation (:230-246) excepted
+ *   srbd_pgg_start_stop_device: for every environment what the host call srbd_pgg_start_stop (srbd_host.h) does on a
+ *   host srbd_pgg with the same bytes, with feet[e], hips[e], base_pos[e], euler[e] (roll, pitch, yaw), base_lin_vel[e],
+ *   base_ang_vel[e], the (modulated) command ref_lin[e] / ref_ang[e] and current_contact[e] widened to double (float32
+ *   as srbd_pgg_run_device writes it).  The hip offset is read either from io->frg (the device srbd_frg array's
+ *   hip_offset field, per environment) or from *io->hip_offset (a host double shared by the environments); exactly one
+ *   of the two is given.  Afterwards d_pgg[e] holds exactly the bytes the host call leaves, and action[e] (optional)
+ *   its return value: 0 untouched, 1 stopped (full stance), 2 restored.  One quad of lanes per environment: lane l
+ *   forms leg l's two horizontal-frame points and its distance, the four verdicts are combined by quad shuffles, and
+ *   the lane that owns field l of the struct writes it (lane 0 the gait type besides).  Environments are independent:
+ *   a NaN in one makes that one's condition false and changes nothing in another.
+ *   Enqueue contract (the producers' above): exactly one launch on hip_stream, no synchronising HIP call, no device
+ *   memory touched from the host; the stream handle is read as srbd_prepare_state_device reads it (NULL and
+ *   hipStreamLegacy both select the legacy null stream); no event and no ordering rule.  Arrays must not overlap.
+ *   SRBD_E_INVALID (before any HIP call): a NULL d_pgg, io or required pointer (every pointer except frg, hip_offset
+ *   and action); both or neither of frg and hip_offset; num_envs outside 1..4096.  A failed launch: SRBD_E_HIP, or
+ *   SRBD_E_NODEVICE where no device exists. */
+typedef struct srbd_start_stop_batch_io {
+    /* inputs: device memory, float64 unless noted; E = num_envs */
+    const double* feet;               /* E x 4 x 3 */
+    const double* hips;               /* E x 4 x 3 */
+    const double* base_pos;           /* E x 3 */
+    const double* euler;              /* E x 3: roll, pitch, yaw */
+    const double* base_lin_vel;       /* E x 3 */
+    const double* base_ang_vel;       /* E x 3 */
+    const double* ref_lin;            /* E x 3: the (modulated) command */
+    const double* ref_ang;            /* E x 3 */
+    const float* current_contact;     /* E x 4 float32, as srbd_pgg_run_device writes it */
+    const struct srbd_frg* frg;       /* E, or NULL when hip_offset is given; only hip_offset is read */
+    const double* hip_offset;         /* HOST memory: one shared value, or NULL when frg is given */
+    /* output */
+    int32_t* action;                  /* E, or NULL: 0 untouched, 1 stopped, 2 restored */
+} srbd_start_stop_batch_io;
+int srbd_pgg_start_stop_device(struct srbd_pgg* d_pgg, int32_t num_envs, const srbd_start_stop_batch_io* io,
+                               void* hip_stream);
+
+/*   srbd_wb_update_device: one call, exactly one launch, that runs for every environment what these existing device
+ *   calls do, in this order -- the reference's, wb_interface.py:168-298:
+ *     1. srbd_vm_modulate_device, if SRBD_WB_VM is set in io->stages; otherwise the command passes through to lin_out /
+ *        ang_out unchanged.
+ *     2. srbd_pgg_start_stop_device, if SRBD_WB_START_STOP is set, on the modulated command and on the contact state
+ *        d_contact as the previous call left it, with the hip offset of d_frg.
+ *     3. srbd_pgg_run_device(dt) with each environment's own step frequency; its flags are discarded, as the reference
+ *        discards them.
+ *     4. srbd_pgg_contact_sequence_device into contacts (E x 4 x contact_stride float32); dts / lens are host arrays and
+ *        travel by value, as for that call.
+ *     5. the contact bookkeeping of wb_interface.py:196-199: previous_contact[e] receives the contact state; the
+ *        contact state d_contact[e] (E x 4 float32, caller-owned, all ones at start) becomes column 0 of the sequence;
+ *        current_contact receives a copy.
+ *     6. srbd_frg_step_device with that previous / current pair and pgg given (gait_type as step 2 left it): seeds and
+ *        ref[:, 12:24].
+ *     7. srbd_terrain_ref_step_device with frg given (its lift-off table, after step 6) and the modulated command:
+ *        ref[:, 0:12] and the optional terrain rows.
+ *     8. srbd_stc_touch_down_device(lookahead) into optimize, if SRBD_WB_TOUCH_DOWN is set; otherwise optimize[e] = 0 and
+ *        d_rising_edge is neither read nor written (it may then be NULL).
+ *   The visual foothold adaptation (wb_interface.py:230-246) is not part of it: srbd_vfa_step_device stays the separate
+ *   launch behind this call and rewrites ref[:, 12:24].
+ *   State: d_pgg, d_frg, d_terrain (the struct arrays of the calls above), d_contact and d_rising_edge, all device
+ *   memory, caller-owned, plain data.  The yaw the chain's calls take as `yaws` is euler[e][2].
+ *   Equivalence: after the call every state array holds the bytes, and every output the values, that the chain above
+ *   leaves -- bit for bit, NaNs position for position, for every combination of stages -- and so, through those
+ *   calls' own equivalences, what the host functions of srbd_host.h leave.  The kernel runs the same per-leg functions
+ *   (csrc/srbd_frg.h, srbd_terrain.h, srbd_gait_adapt.h, srbd_start_stop.h and the gait generator's helpers), unfused
+ *   and in the same order, through device functions it shares with the kernels of the single calls.  Lane 4 e + l is
+ *   leg l of environment e, 64 environments per 256-thread block.  What a later stage needs from an earlier one stays
+ *   in registers or crosses the quad by shuffles (the modulated command, the gait type after start-and-stop, the
+ *   leg's phase state, column 0 of the sequence, the previous contact); the intermediate arrays lin_out, ang_out,
+ *   current_contact and previous_contact are written where given and never read back.
+ *   Enqueue contract (the producers' above): exactly one launch on hip_stream, no synchronising HIP call, no device
+ *   memory touched from the host; the stream handle is read as srbd_prepare_state_device reads it; no event and no
+ *   ordering rule.  Arrays must not overlap.
+ *   SRBD_E_INVALID (before any HIP call): a NULL d_pgg, d_frg, d_terrain, d_contact, io or required pointer (every
+ *   pointer except com_pos_offset_w, lin_out, ang_out, current_contact, previous_contact, terrain and action; and
+ *   d_rising_edge when the trigger is off); num_envs outside 1..4096; horizon outside 2..SRBD_MAX_HORIZON;
+ *   contact_stride < horizon; lookahead outside 1..horizon-1 when the trigger is on; n_dts outside 1..32 or lens that
+ *   would run past n_dts before step horizon - 1; a dt, ref_z, com_height_nominal or gravity that is not finite;
+ *   gravity <= 0; a max_distance that is NaN when the modulator is on; unknown bits in stages.  A failed launch:
+ *   SRBD_E_HIP, or SRBD_E_NODEVICE where no device exists. */
+enum { SRBD_WB_VM = 1, SRBD_WB_START_STOP = 2, SRBD_WB_TOUCH_DOWN = 4 };
+typedef struct srbd_wb_update_io {
+    /* inputs: device memory, float64; E = num_envs */
+    const double* com_pos;            /* E x 3, z used */
+    const double* base_pos;           /* E x 3 */
+    const double* base_lin_vel;       /* E x 3 */
+    const double* euler;              /* E x 3: roll, pitch, yaw */
+    const double* base_ang_vel;       /* E x 3 */
+    const double* feet;               /* E x 4 x 3 */
+    const double* hips;               /* E x 4 x 3 */
+    const double* ref_lin;            /* E x 3: ref_base_lin_vel, the command */
+    const double* ref_ang;            /* E x 3: ref_base_ang_vel */
+    const double* com_pos_offset_w;   /* E x 3, or NULL */
+    /* shared by the environments */
+    const double* dts;                /* HOST memory, n_dts entries: the contact sequence's time steps */
+    const int32_t* lens;              /* HOST memory, n_dts entries: dts[j] holds for the steps i < lens[j] */
+    double dt;                        /* simulation_dt of srbd_pgg_run_device */
+    double max_distance;              /* the modulator's; the reference's value is 0.2 */
+    double com_height_nominal, gravity; /* srbd_frg_step_device's */
+    double ref_z;                     /* srbd_terrain_ref_step_device's */
+    /* outputs: device memory */
+    double* lin_out;                  /* E x 3 or NULL: the modulated command */
+    double* ang_out;                  /* E x 3 or NULL */
+    float* contacts;                  /* E x 4 x contact_stride float32: columns 0..horizon-1 written */
+    float* current_contact;           /* E x 4 float32 or NULL: a copy of the new contact state */
+    float* previous_contact;          /* E x 4 float32 or NULL: the contact state as it was found */
+    double* seeds;                    /* E x 4 x 3 */
+    double* ref;                      /* E x 24: every entry written */
+    double* terrain;                  /* E x 3 or NULL: roll, pitch, height */
+    int32_t* optimize;                /* E */
+    int32_t* action;                  /* E or NULL: start-and-stop's 0 / 1 / 2 (0 when that stage is off) */
+    int32_t n_dts, horizon, contact_stride, lookahead;
+    int32_t stages;                   /* SRBD_WB_* bits */
+    int32_t pad;                      /* 0: the sixth word, so that no padding is left to chance */
+} srbd_wb_update_io;
+struct srbd_terrain_est;
+int srbd_wb_update_device(struct srbd_pgg* d_pgg, struct srbd_frg* d_frg, struct srbd_terrain_est* d_terrain,
+                          float* d_contact, int32_t* d_rising_edge, int32_t num_envs, const srbd_wb_update_io* io,
+                          void* hip_stream);
 
 /* Diagnostic: enable != 0 stamps the phases of the following TAMOLS calls; out_us[5] (may be NULL)
  * receives the last call's mean per-block durations of (patch, queries, scores, slice argmin + count)

@@ -40,6 +40,24 @@ namespace srbd {
 // STC:148-165, statement for statement.  T is the contacts' element type (double on the host, float32 on the device:
 // the values compared are 0 and 1, exact in both).  seq is 4 x stride, row l at seq + l * stride.  The caller has
 // checked 1 <= lookahead <= horizon - 1 <= stride - 1 (the reference raises IndexError at column `lookahead`).
+// It is cut into one leg's share of the two np.all over the sequence (ga_leg_window) and the decision from the four
+// conjunctions (ga_trigger), so that a kernel whose lanes each hold one leg's row (srbd_producers.hip wb_update_kernel)
+// runs the same statements.
+template <class T>
+YAW_HD inline void ga_leg_window(const T* row, int lookahead, bool& stable, bool& next_all) {
+    for (int i = 0; i < lookahead; ++i) stable = stable && row[i] == (T)1;  // STC:158
+    next_all = next_all && row[lookahead] == (T)1;                           // STC:159
+}
+
+YAW_HD inline int32_t ga_trigger(int32_t* rising_edge, bool cur, bool prev, bool stable, bool next_all) {
+    if (cur && !prev) *rising_edge = 1;              // STC:154-155
+    if (*rising_edge != 0 && stable && !next_all) {  // STC:161-163
+        *rising_edge = 0;
+        return 1;
+    }
+    return 0;
+}
+
 template <class T>
 YAW_HD inline int32_t ga_touch_down(int32_t* rising_edge, const T* current, const T* previous, const T* seq,
                                     int stride, int lookahead) {
@@ -48,17 +66,9 @@ YAW_HD inline int32_t ga_touch_down(int32_t* rising_edge, const T* current, cons
         cur = cur && current[l] == (T)1;
         prev = prev && previous[l] == (T)1;
     }
-    if (cur && !prev) *rising_edge = 1;  // STC:154-155
     bool stable = true, next_all = true;
-    for (int l = 0; l < 4; ++l) {
-        for (int i = 0; i < lookahead; ++i) stable = stable && seq[(size_t)l * stride + i] == (T)1;  // STC:158
-        next_all = next_all && seq[(size_t)l * stride + lookahead] == (T)1;                           // STC:159
-    }
-    if (*rising_edge != 0 && stable && !next_all) {  // STC:161-163
-        *rising_edge = 0;
-        return 1;
-    }
-    return 0;
+    for (int l = 0; l < 4; ++l) ga_leg_window(seq + (size_t)l * stride, lookahead, stable, next_all);
+    return ga_trigger(rising_edge, cur, prev, stable, next_all);
 }
 
 // The three timing values of WBI:355-358 for a float32 best frequency (see the header comment).  false: a value the

@@ -19,6 +19,7 @@
 #include "srbd_iface.h"
 #include "srbd_jaxrng.h"
 #include "srbd_reset.h"
+#include "srbd_start_stop.h"
 #include "srbd_stc.h"
 #include "srbd_terrain.h"
 #include "srbd_vfa.h"
@@ -120,6 +121,28 @@ extern "C" int srbd_pgg_contact_sequence(srbd_pgg* g, const double* dts, const i
     }
     srbd_pgg_set_phase_signal(g, t_init, init_init);
     return H;
+}
+
+// PGG:128-196 through the pieces the device kernels spread over a quad (srbd_start_stop.h): four leg verdicts, the
+// conjuncts that belong to no leg, the action, then each leg's share of the rewrite.
+extern "C" int srbd_pgg_start_stop(srbd_pgg* g, const double* feet, const double* hips, double hip_offset,
+                                   const double base_pos[3], const double euler[3], const double base_lin_vel[3],
+                                   const double base_ang_vel[3], const double ref_lin[3], const double ref_ang[3],
+                                   const double current_contact[4]) {
+    if (!g || !feet || !hips || !base_pos || !euler || !base_lin_vel || !base_ang_vel || !ref_lin || !ref_ang ||
+        !current_contact)
+        return SRBD_E_INVALID;
+    double c, s;
+    srbd::yaw_sincos(euler[2], c, s);
+    bool stop = srbd::ss_quiet(ref_lin, ref_ang, base_lin_vel, base_ang_vel, euler, current_contact);
+    for (int l = 0; l < 4; ++l)
+        stop = srbd::ss_leg_close(l, feet + 3 * l, hips + 3 * l, base_pos, c, s, hip_offset) && stop;
+    const int32_t action = srbd::ss_action(stop, g->gait_type);
+    const int32_t gait = srbd::ss_next_gait(action, g->gait_type, g->previous_gait_type);
+    for (int l = 0; l < 4; ++l)
+        srbd::ss_apply_leg(l, action, gait, g->phase_offset[l], g->phase_signal[l], g->init[l]);
+    if (action != srbd::SS_UNTOUCHED) g->gait_type = gait;
+    return action;
 }
 
 // NMPC:563-627 (shift_solution off, config.py:188).

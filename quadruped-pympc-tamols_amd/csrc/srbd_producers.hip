@@ -42,6 +42,12 @@
 // :225-229): prepare_state through the device function prepare_state_kernel runs and the key schedule of
 // srbd_iface.h ahead of them; the GRFs times the current contact, the footholds and previous_contact_mpc behind them.
 // One lane per (environment, leg), no cross-lane traffic.
+// start_stop_kernel (srbd_pgg_start_stop_device) is the gait generator's start-and-stop decision (srbd_start_stop.h;
+// PGG:128-196), one quad per environment with its verdict combined by shuffles.  wb_update_kernel
+// (srbd_wb_update_device) runs the whole of WBInterface.update_state_and_reference (wb_interface.py:168-298, the
+// foothold search excepted) in one launch: the stages of vm_modulate_kernel, start_stop_kernel, pgg_run_kernel,
+// pgg_contact_sequence_kernel, frg_step_kernel, terrain_ref_step_kernel and touch_down_kernel through the device
+// functions those kernels run, what one stage hands the next kept in registers (see the kernel).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -55,6 +61,7 @@
 #include "srbd_iface.h"
 #include "srbd_launch.h"
 #include "srbd_reset.h"
+#include "srbd_start_stop.h"
 #include "srbd_stc.h"
 #include "srbd_terrain.h"
 #include "yaw_sincos.h"
@@ -114,6 +121,40 @@ struct PggSeqConst {
     int32_t n_dts, H, stride;
 };
 
+// One leg's words of a srbd_pgg, held in registers by the kernels that carry them from one stage to the next.
+struct PggLeg {
+    double ph, offset;
+    int32_t ini;
+};
+
+// One leg's srbd_pgg_contact_sequence on the leg's words `s`: row[0 .. H) written, column 0 returned.  A full-stance
+// leg gets ones and srbd_pgg_reset's words; any other is left as found, its hold stored as init != 0 (the host
+// restores the state through srbd_pgg_set_phase_signal, which stores it so).
+__device__ __forceinline__ float pgg_leg_sequence(PggLeg& s, int32_t gait, int l, double duty, double freq,
+                                                  const PggSeqConst& sc, float* __restrict__ row) {
+#pragma clang fp contract(off)
+    if (gait == SRBD_GAIT_FULL_STANCE) {  // ones, and srbd_pgg_reset (gait_offsets' row of this gait)
+        for (int i = 0; i < sc.H; ++i) row[i] = 1.0f;
+        const double off = (l == 1 || l == 2) ? 0.5 : 0.0;
+        s.offset = off;
+        s.ph = off;
+        s.ini = 0;
+        return 1.0f;
+    }
+    double ph = s.ph;
+    int32_t ini = s.ini;
+    const float first = pgg_leg_run(ph, ini, s.offset, duty, 0.0 * freq);
+    row[0] = first;
+    int j = 0;
+    for (int i = 1; i < sc.H; ++i) {
+        if (i >= sc.lens[j]) ++j;
+        if (j >= sc.n_dts) break;  // refused on the host; never an index past the arrays
+        row[i] = pgg_leg_run(ph, ini, s.offset, duty, sc.dts[j] * freq);
+    }
+    if (s.ini != (s.ini != 0)) s.ini = 1;
+    return first;
+}
+
 __global__ void __launch_bounds__(PROD_BLOCK) pgg_contact_sequence_kernel(srbd_pgg* __restrict__ pgg, int E,
                                                                           const PggSeqConst sc,
                                                                           float* __restrict__ contacts) {
@@ -122,28 +163,17 @@ __global__ void __launch_bounds__(PROD_BLOCK) pgg_contact_sequence_kernel(srbd_p
     if (t >= 4 * E) return;
     const int e = t >> 2, l = t & 3;
     srbd_pgg* g = pgg + e;
-    float* __restrict__ row = contacts + (size_t)t * sc.stride;
-    if (g->gait_type == SRBD_GAIT_FULL_STANCE) {  // ones, and srbd_pgg_reset (gait_offsets' row of this gait)
-        for (int i = 0; i < sc.H; ++i) row[i] = 1.0f;
-        const double off = (l == 1 || l == 2) ? 0.5 : 0.0;
-        g->phase_offset[l] = off;
-        g->phase_signal[l] = off;
-        g->init[l] = 0;
-        return;
+    const int32_t gait = g->gait_type;
+    PggLeg s = {g->phase_signal[l], g->phase_offset[l], g->init[l]};
+    const int32_t ini0 = s.ini;
+    pgg_leg_sequence(s, gait, l, g->duty_factor, g->step_freq, sc, contacts + (size_t)t * sc.stride);
+    if (gait == SRBD_GAIT_FULL_STANCE) {
+        g->phase_offset[l] = s.offset;
+        g->phase_signal[l] = s.ph;
+        g->init[l] = s.ini;
+    } else if (s.ini != ini0) {
+        g->init[l] = s.ini;
     }
-    double ph = g->phase_signal[l];
-    int32_t ini = g->init[l];
-    const int32_t ini0 = ini;
-    const double offset = g->phase_offset[l], duty = g->duty_factor, freq = g->step_freq;
-    row[0] = pgg_leg_run(ph, ini, offset, duty, 0.0 * freq);
-    int j = 0;
-    for (int i = 1; i < sc.H; ++i) {
-        if (i >= sc.lens[j]) ++j;
-        if (j >= sc.n_dts) break;  // refused on the host; never an index past the arrays
-        row[i] = pgg_leg_run(ph, ini, offset, duty, sc.dts[j] * freq);
-    }
-    // the state is left as found; the host restores it through srbd_pgg_set_phase_signal, which stores init != 0
-    if (ini0 != (ini0 != 0)) g->init[l] = 1;
 }
 
 // One leg's srbd_prepare_state: lane (e, l) copies the base entries 3 l .. 3 l + 2 and foot l of state and reference,
@@ -263,12 +293,14 @@ struct FrgJob {
 // rewritten by lane 0 as well, so lane 0 alone loads them and hands them to its three neighbours with a quad
 // broadcast (4 E lanes are live and a quad is one environment, so its lane 0 is live whenever the others are).  No
 // lane reads a word another lane of the launch writes.
-__global__ void __launch_bounds__(PROD_BLOCK) frg_step_kernel(srbd_frg* __restrict__ frg, int E, const FrgJob j) {
+// That step for lane l of environment g's quad, the values it reads already in hand: prev / cur the leg's contacts,
+// (c, s) cos / sin of the yaw, (bx, by) / (qx, qy) the base and the reference velocity, off com_pos_offset_w or NULL.
+// out[3] receives the leg's foothold.
+__device__ __forceinline__ void frg_leg_step(srbd_frg* g, int l, const double* base, const double* foot,
+                                             const double* hip, double prev, double cur, bool full_stance, double c,
+                                             double s, double bx, double by, double qx, double qy, double root,
+                                             const double* off, double* out) {
 #pragma clang fp contract(off)
-    const int t = blockIdx.x * PROD_BLOCK + threadIdx.x;
-    if (t >= 4 * E) return;
-    const int e = t >> 2, l = t & 3;
-    srbd_frg* g = frg + e;
     int len = 0, head = 0;
     if (l == 0) {
         len = g->hist_len;
@@ -276,30 +308,14 @@ __global__ void __launch_bounds__(PROD_BLOCK) frg_step_kernel(srbd_frg* __restri
     }
     len = __shfl(len, 0, 4);
     head = __shfl(head, 0, 4);
-    const double base[3] = {j.base_pos[3 * (size_t)e], j.base_pos[3 * (size_t)e + 1], j.base_pos[3 * (size_t)e + 2]};
-    const double* foot = j.feet + 3 * (size_t)t;
-    const double prev = (double)j.prev[t], cur = (double)j.cur[t];
-    const bool full_stance = j.pgg && j.pgg[e].gait_type == SRBD_GAIT_FULL_STANCE;
-    double c, s;
-    yaw_sincos(j.yaws[e], c, s);
     frg_leg_lift_off(g, l, prev, cur, foot, full_stance, base, c, s);
     frg_leg_touch_down(g, l, prev, cur, foot, full_stance, base, c, s);
-    const double bx = j.base_vel[3 * (size_t)e], by = j.base_vel[3 * (size_t)e + 1];
-    const double qx = j.ref_vel[3 * (size_t)e], qy = j.ref_vel[3 * (size_t)e + 1];
     const double vx = c * bx + s * by, vy = -s * bx + c * by;
     const double rx = c * qx + s * qy, ry = -s * qx + c * qy;
     double mx, my, ox, oy;
     frg_mean_with(g, len, head, vx, vy, mx, my);
-    frg_compensation(g, rx, ry, mx, my, j.root, ox, oy);
-    double out[3];
-    frg_leg_foothold(g, l, j.hips + 3 * (size_t)t, base, c, s, ox, oy, j.com_off ? j.com_off + 3 * (size_t)e : nullptr,
-                     out);
-    double* __restrict__ seed = j.seeds + 3 * (size_t)t;
-    seed[0] = out[0], seed[1] = out[1], seed[2] = out[2];
-    if (j.ref) {
-        double* __restrict__ r = j.ref + 24 * (size_t)e + 12 + 3 * l;
-        r[0] = out[0], r[1] = out[1], r[2] = out[2];
-    }
+    frg_compensation(g, rx, ry, mx, my, root, ox, oy);
+    frg_leg_foothold(g, l, hip, base, c, s, ox, oy, off, out);
     if (l == 0) {
         int len1, head1;
         const int slot = frg_ring_next(len, head, len1, head1);
@@ -307,6 +323,27 @@ __global__ void __launch_bounds__(PROD_BLOCK) frg_step_kernel(srbd_frg* __restri
         g->vel_hist[slot][1] = vy;
         g->hist_len = len1;
         g->hist_head = head1;
+    }
+}
+
+__global__ void __launch_bounds__(PROD_BLOCK) frg_step_kernel(srbd_frg* __restrict__ frg, int E, const FrgJob j) {
+#pragma clang fp contract(off)
+    const int t = blockIdx.x * PROD_BLOCK + threadIdx.x;
+    if (t >= 4 * E) return;
+    const int e = t >> 2, l = t & 3;
+    const double base[3] = {j.base_pos[3 * (size_t)e], j.base_pos[3 * (size_t)e + 1], j.base_pos[3 * (size_t)e + 2]};
+    const bool full_stance = j.pgg && j.pgg[e].gait_type == SRBD_GAIT_FULL_STANCE;
+    double c, s;
+    yaw_sincos(j.yaws[e], c, s);
+    double out[3];
+    frg_leg_step(frg + e, l, base, j.feet + 3 * (size_t)t, j.hips + 3 * (size_t)t, (double)j.prev[t], (double)j.cur[t],
+                 full_stance, c, s, j.base_vel[3 * (size_t)e], j.base_vel[3 * (size_t)e + 1], j.ref_vel[3 * (size_t)e],
+                 j.ref_vel[3 * (size_t)e + 1], j.root, j.com_off ? j.com_off + 3 * (size_t)e : nullptr, out);
+    double* __restrict__ seed = j.seeds + 3 * (size_t)t;
+    seed[0] = out[0], seed[1] = out[1], seed[2] = out[2];
+    if (j.ref) {
+        double* __restrict__ r = j.ref + 24 * (size_t)e + 12 + 3 * l;
+        r[0] = out[0], r[1] = out[1], r[2] = out[2];
     }
 }
 
@@ -380,19 +417,25 @@ struct VmJob {
 // srbd_vm_modulate of srbd_host.cpp per environment (srbd_terrain.h).  Lane (e, l) forms leg l's distance and its
 // comparison; the four comparisons are or-ed across the quad (all four lanes of a live quad are live), and lanes 0..2
 // write entry l of the two outputs.  No state.
+// The modulator's disjunction for a quad: the lane's own leg's comparison or-ed with its three neighbours'.
+__device__ __forceinline__ bool vm_quad_beyond(const double* foot, const double* hip, double max_distance) {
+    int beyond = vm_distance(foot, hip) > max_distance ? 1 : 0;
+    beyond |= __shfl_xor(beyond, 1, 4);
+    beyond |= __shfl_xor(beyond, 2, 4);
+    return beyond != 0;
+}
+
 __global__ void __launch_bounds__(PROD_BLOCK) vm_modulate_kernel(int E, const VmJob j) {
 #pragma clang fp contract(off)
     const int t = blockIdx.x * PROD_BLOCK + threadIdx.x;
     if (t >= 4 * E) return;
     const int e = t >> 2, l = t & 3;
-    int beyond = vm_distance(j.feet + 3 * (size_t)t, j.hips + 3 * (size_t)t) > j.max_distance ? 1 : 0;
-    beyond |= __shfl_xor(beyond, 1, 4);
-    beyond |= __shfl_xor(beyond, 2, 4);
+    const bool beyond = vm_quad_beyond(j.feet + 3 * (size_t)t, j.hips + 3 * (size_t)t, j.max_distance);
     if (l == 3) return;
     const double* lin = j.lin + 3 * (size_t)e;
     const bool standing = vm_standing(lin);
-    j.lin_out[3 * (size_t)e + l] = vm_entry(lin[l], standing, beyond != 0);
-    j.ang_out[3 * (size_t)e + l] = vm_entry(j.ang[3 * (size_t)e + l], standing, beyond != 0);
+    j.lin_out[3 * (size_t)e + l] = vm_entry(lin[l], standing, beyond);
+    j.ang_out[3 * (size_t)e + l] = vm_entry(j.ang[3 * (size_t)e + l], standing, beyond);
 }
 
 // The arrays of one srbd_terrain_ref_step_device call (srbd_terrain_ref_batch_io).
@@ -421,18 +464,15 @@ __device__ inline void pair_sincos(double x, int l, double& c, double& s) {
 // source lane is live).  Lane 0 alone loads the state, runs the filter and stores the three filtered words, and hands
 // them to its neighbours with a quad broadcast: no lane reads a word another lane of the launch writes.  Lane l
 // stores entries 3 l .. 3 l + 2 of the reference row.
-__global__ void __launch_bounds__(PROD_BLOCK) terrain_ref_step_kernel(srbd_terrain_est* __restrict__ terr, int E,
-                                                                      const TerrJob j) {
+// That step for lane l of an environment's quad: tg its estimator struct, foot the leg's three coordinates, (c, s)
+// cos / sin of the yaw, lin / ang the (modulated) command, terrain_row the environment's roll / pitch / height output
+// or NULL, row entries 3 l .. 3 l + 2 of its reference row.
+__device__ __forceinline__ void terr_quad(srbd_terrain_est* tg, int l, const double* base, const double* foot,
+                                          double c, double s, double ref_z, double com_z, double com_off_z,
+                                          const double* lin, const double* ang, double* __restrict__ terrain_row,
+                                          double* __restrict__ row) {
 #pragma clang fp contract(off)
-    const int t = blockIdx.x * PROD_BLOCK + threadIdx.x;
-    if (t >= 4 * E) return;
-    const int e = t >> 2, l = t & 3;
-    const double base[3] = {j.base_pos[3 * (size_t)e], j.base_pos[3 * (size_t)e + 1], j.base_pos[3 * (size_t)e + 2]};
-    const double* fp = j.frg ? j.frg[e].lift_off[l] : j.feet + 3 * (size_t)t;
-    const double foot[3] = {fp[0], fp[1], fp[2]};
-    const double yaw = j.yaws[e];
-    double c, s, rot[3];
-    pair_sincos(yaw, l, c, s);
+    double rot[3];
     terr_rotate(foot, base, c, s, rot);
     int a, b;
     terr_pair(l, a, b);
@@ -453,26 +493,230 @@ __global__ void __launch_bounds__(PROD_BLOCK) terrain_ref_step_kernel(srbd_terra
     }
     srbd_terrain_est g = {};
     if (l == 0) {
-        g = terr[e];
+        g = *tg;
         terr_filter(&g, angle, dz, foot_z);
-        terr[e].roll = g.roll;
-        terr[e].pitch = g.pitch;
-        terr[e].height = g.height;
-        if (j.terrain) {
-            double* __restrict__ o = j.terrain + 3 * (size_t)e;
-            o[0] = g.roll, o[1] = g.pitch, o[2] = g.height;
-        }
+        tg->roll = g.roll;
+        tg->pitch = g.pitch;
+        tg->height = g.height;
+        if (terrain_row) terrain_row[0] = g.roll, terrain_row[1] = g.pitch, terrain_row[2] = g.height;
     }
     const double roll = __shfl(g.roll, 0, 4), pitch = __shfl(g.pitch, 0, 4), height = __shfl(g.height, 0, 4);
     double cc, ss;  // lanes 0, 1: of the roll; lanes 2, 3: of the pitch
     pair_sincos(l < 2 ? roll : pitch, l, cc, ss);
     const double cr = __shfl(cc, 0, 4), sr = __shfl(ss, 0, 4), cp = __shfl(cc, 2, 4), sp = __shfl(ss, 2, 4);
     double out[12];
-    terr_assemble(roll, pitch, height, cr, sr, cp, sp, j.ref_z, base[2], j.com_pos[3 * (size_t)e + 2],
-                  j.com_off ? j.com_off[3 * (size_t)e + 2] : 0.0, j.lin + 3 * (size_t)e, j.ang + 3 * (size_t)e, out);
-    double* __restrict__ row = j.ref + 24 * (size_t)e + 3 * l;
+    terr_assemble(roll, pitch, height, cr, sr, cp, sp, ref_z, base[2], com_z, com_off_z, lin, ang, out);
 #pragma unroll
     for (int k = 0; k < 3; ++k) row[k] = l == 0 ? out[k] : l == 1 ? out[3 + k] : l == 2 ? out[6 + k] : out[9 + k];
+}
+
+__global__ void __launch_bounds__(PROD_BLOCK) terrain_ref_step_kernel(srbd_terrain_est* __restrict__ terr, int E,
+                                                                      const TerrJob j) {
+#pragma clang fp contract(off)
+    const int t = blockIdx.x * PROD_BLOCK + threadIdx.x;
+    if (t >= 4 * E) return;
+    const int e = t >> 2, l = t & 3;
+    const double base[3] = {j.base_pos[3 * (size_t)e], j.base_pos[3 * (size_t)e + 1], j.base_pos[3 * (size_t)e + 2]};
+    const double* fp = j.frg ? j.frg[e].lift_off[l] : j.feet + 3 * (size_t)t;
+    const double foot[3] = {fp[0], fp[1], fp[2]};
+    double c, s;
+    pair_sincos(j.yaws[e], l, c, s);
+    terr_quad(terr + e, l, base, foot, c, s, j.ref_z, j.com_pos[3 * (size_t)e + 2],
+              j.com_off ? j.com_off[3 * (size_t)e + 2] : 0.0, j.lin + 3 * (size_t)e, j.ang + 3 * (size_t)e,
+              j.terrain ? j.terrain + 3 * (size_t)e : nullptr, j.ref + 24 * (size_t)e + 3 * l);
+}
+
+// The arrays of one srbd_pgg_start_stop_device call (srbd_start_stop_batch_io).
+struct StartStopJob {
+    const double *feet, *hips, *base_pos, *euler, *lin_vel, *ang_vel, *ref_lin, *ref_ang;
+    const float* contact;
+    const srbd_frg* frg;
+    double hip_offset;
+    int32_t* action;
+};
+
+// srbd_pgg_start_stop's verdict for lane l of an environment's quad (srbd_start_stop.h): the lane forms its own leg's
+// distance and comparison, the four are and-ed across the quad, the four contact flags are gathered from the four
+// lanes, and every lane evaluates the conjuncts that belong to no leg (the same values on all four).  Returns the
+// action for the gait type found.  All four lanes of a live quad are live.
+__device__ __forceinline__ int32_t start_stop_quad(int l, const double* foot, const double* hip, const double* base,
+                                                   const double* euler, const double* lin_vel, const double* ang_vel,
+                                                   const double* ref_lin, const double* ref_ang, float contact_l,
+                                                   double c, double s, double hip_offset, int32_t gait_type) {
+#pragma clang fp contract(off)
+    double contact[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) contact[k] = (double)__shfl(contact_l, k, 4);
+    int close = ss_leg_close(l, foot, hip, base, c, s, hip_offset) ? 1 : 0;
+    close &= __shfl_xor(close, 1, 4);
+    close &= __shfl_xor(close, 2, 4);
+    const bool stop = ss_quiet(ref_lin, ref_ang, lin_vel, ang_vel, euler, contact) && close != 0;
+    return ss_action(stop, gait_type);
+}
+
+// The two gait type words of an environment, loaded by its lane 0 alone (which rewrites one of them) and handed to
+// the quad by a broadcast.
+__device__ __forceinline__ void pgg_quad_gait(const srbd_pgg* g, int l, int32_t& gait, int32_t& previous) {
+    gait = 0, previous = 0;
+    if (l == 0) {
+        gait = g->gait_type;
+        previous = g->previous_gait_type;
+    }
+    gait = __shfl(gait, 0, 4);
+    previous = __shfl(previous, 0, 4);
+}
+
+// srbd_pgg_start_stop of srbd_host.cpp per environment.  Lane (e, l) owns leg l's three words of pgg[e] and writes
+// nothing else, lane (e, 0) the gait type and action[e] besides.  No lane reads a word another lane of the launch
+// writes.
+__global__ void __launch_bounds__(PROD_BLOCK) start_stop_kernel(srbd_pgg* __restrict__ pgg, int E,
+                                                                const StartStopJob j) {
+#pragma clang fp contract(off)
+    const int t = blockIdx.x * PROD_BLOCK + threadIdx.x;
+    if (t >= 4 * E) return;
+    const int e = t >> 2, l = t & 3;
+    const size_t e3 = 3 * (size_t)e;
+    srbd_pgg* g = pgg + e;
+    int32_t gait, previous;
+    pgg_quad_gait(g, l, gait, previous);
+    double c, s;
+    pair_sincos(j.euler[e3 + 2], l, c, s);
+    const int32_t action = start_stop_quad(l, j.feet + 3 * (size_t)t, j.hips + 3 * (size_t)t, j.base_pos + e3,
+                                           j.euler + e3, j.lin_vel + e3, j.ang_vel + e3, j.ref_lin + e3, j.ref_ang + e3,
+                                           j.contact[t], c, s, j.frg ? j.frg[e].hip_offset : j.hip_offset, gait);
+    if (l == 0 && j.action) j.action[e] = action;
+    if (action == SS_UNTOUCHED) return;
+    gait = ss_next_gait(action, gait, previous);
+    ss_apply_leg(l, action, gait, g->phase_offset[l], g->phase_signal[l], g->init[l]);
+    if (l == 0) g->gait_type = gait;
+}
+
+// The arrays and shared values of one srbd_wb_update_device call (srbd_wb_update_io) with the state arrays.
+struct WbJob {
+    const double *com_pos, *base_pos, *base_vel, *euler, *ang_vel, *feet, *hips, *ref_lin, *ref_ang, *com_off;
+    double dt, max_distance, root, ref_z;  // root = sqrt(com_height_nominal / gravity)
+    double *lin_out, *ang_out;
+    float *contacts, *cur_out, *prev_out;
+    double *seeds, *ref, *terrain;
+    int32_t *optimize, *action;
+    srbd_pgg* pgg;
+    srbd_frg* frg;
+    srbd_terrain_est* terr;
+    float* contact;
+    int32_t* rising_edge;
+    int32_t lookahead, stages;
+    PggSeqConst sc;
+};
+
+// WBInterface.update_state_and_reference (WBI:168-298, the visual foothold adaptation excepted) per environment: the
+// stages of vm_modulate_kernel, start_stop_kernel, pgg_run_kernel, pgg_contact_sequence_kernel, frg_step_kernel,
+// terrain_ref_step_kernel and touch_down_kernel in that order, through the device functions those kernels run, so
+// every stage has one body and leaves the bits its own launch leaves.  Lane (e, l) is leg l of environment e, as in
+// all of them.  What a stage hands to a later one stays in registers:
+//   the modulated command       lin_m / ang_m, formed by every lane of the quad (the same values on all four)
+//   the gait type               `gait`: loaded by lane 0, broadcast, replaced by start-and-stop's verdict in every
+//                               lane's register; the sequence and the foothold generator read that register, and lane
+//                               0 stores it at the end -- no lane reads gait_type from memory after it is written
+//   the leg's phase, offset     `leg`: loaded once, rewritten by start-and-stop, run and the sequence in registers,
+//   and hold                    stored once behind the sequence
+//   the previous contact and    prev_f (the contact state as found) and cur_f (the sequence's column 0 as the lane
+//   column 0 of the sequence    itself formed it); start-and-stop gathers the quad's four prev_f by shuffles
+//   the lift-off row            lane l rereads lift_off[l] of frg[e], which no lane but itself writes (frg_leg_lift_off
+//                               just before, in program order): its own store, so no fence is needed; the terrain stage
+//                               then exchanges the rotated feet by shuffles
+// The touch-down trigger reads the lane's own row of the sequence back (the stores a few statements above it, the same
+// thread) and combines the four legs' conjunctions by shuffles; lane 0 owns rising_edge[e] and optimize[e].  The stage
+// word is a kernel argument, so every branch on it is uniform.  No LDS, no atomics; environments share nothing.
+__global__ void __launch_bounds__(PROD_BLOCK) wb_update_kernel(int E, const WbJob j) {
+#pragma clang fp contract(off)
+    const int t = blockIdx.x * PROD_BLOCK + threadIdx.x;
+    if (t >= 4 * E) return;
+    const int e = t >> 2, l = t & 3;
+    const size_t e3 = 3 * (size_t)e, t3 = 3 * (size_t)t;
+    const double base[3] = {j.base_pos[e3], j.base_pos[e3 + 1], j.base_pos[e3 + 2]};
+    const double* foot = j.feet + t3;
+    const double* hip = j.hips + t3;
+    double c, s;
+    pair_sincos(j.euler[e3 + 2], l, c, s);
+
+    // 1. the velocity modulator (WBI:168-172); switched off, `beyond` is false and vm_entry returns the command
+    const double* lin = j.ref_lin + e3;
+    const double* ang = j.ref_ang + e3;
+    const bool beyond = (j.stages & SRBD_WB_VM) ? vm_quad_beyond(foot, hip, j.max_distance) : false;
+    const bool standing = vm_standing(lin);
+    double lin_m[3], ang_m[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        lin_m[k] = vm_entry(lin[k], standing, beyond);
+        ang_m[k] = vm_entry(ang[k], standing, beyond);
+    }
+    if (l < 3) {
+        if (j.lin_out) j.lin_out[e3 + l] = l == 0 ? lin_m[0] : l == 1 ? lin_m[1] : lin_m[2];
+        if (j.ang_out) j.ang_out[e3 + l] = l == 0 ? ang_m[0] : l == 1 ? ang_m[1] : ang_m[2];
+    }
+
+    srbd_pgg* g = j.pgg + e;
+    srbd_frg* fg = j.frg + e;
+    PggLeg leg = {g->phase_signal[l], g->phase_offset[l], g->init[l]};
+    const double duty = g->duty_factor, freq = g->step_freq;
+    int32_t gait, previous_gait;
+    pgg_quad_gait(g, l, gait, previous_gait);
+    const float prev_f = j.contact[t];
+
+    // 2. start-and-stop (WBI:175-189) on the modulated command and the contact state as found
+    int32_t action = SS_UNTOUCHED;
+    if (j.stages & SRBD_WB_START_STOP) {
+        action = start_stop_quad(l, foot, hip, base, j.euler + e3, j.base_vel + e3, j.ang_vel + e3, lin_m, ang_m,
+                                 prev_f, c, s, fg->hip_offset, gait);
+        gait = ss_next_gait(action, gait, previous_gait);
+        ss_apply_leg(l, action, gait, leg.offset, leg.ph, leg.ini);
+    }
+    if (l == 0 && j.action) j.action[e] = action;
+
+    // 3., 4. run(dt) with its flags discarded and the contact sequence (WBI:191-194)
+    (void)pgg_leg_run(leg.ph, leg.ini, leg.offset, duty, j.dt * freq);
+    float* row = j.contacts + (size_t)t * j.sc.stride;
+    const float cur_f = pgg_leg_sequence(leg, gait, l, duty, freq, j.sc, row);
+    g->phase_signal[l] = leg.ph;
+    g->phase_offset[l] = leg.offset;
+    g->init[l] = leg.ini;
+    if (l == 0 && action != SS_UNTOUCHED) g->gait_type = gait;
+
+    // 5. previous_contact = current_contact, current_contact = column 0 (WBI:196-199)
+    if (j.prev_out) j.prev_out[t] = prev_f;
+    j.contact[t] = cur_f;
+    if (j.cur_out) j.cur_out[t] = cur_f;
+
+    // 6. the foothold reference generator (WBI:202-227)
+    double out[3];
+    frg_leg_step(fg, l, base, foot, hip, (double)prev_f, (double)cur_f, gait == SRBD_GAIT_FULL_STANCE, c, s,
+                 j.base_vel[e3], j.base_vel[e3 + 1], lin_m[0], lin_m[1], j.root, j.com_off ? j.com_off + e3 : nullptr,
+                 out);
+    double* __restrict__ seed = j.seeds + t3;
+    seed[0] = out[0], seed[1] = out[1], seed[2] = out[2];
+    double* __restrict__ rf = j.ref + 24 * (size_t)e + 12 + 3 * l;
+    rf[0] = out[0], rf[1] = out[1], rf[2] = out[2];
+
+    // 7. the terrain estimate on the lift-off table and the reference row (WBI:250-291)
+    const double lift[3] = {fg->lift_off[l][0], fg->lift_off[l][1], fg->lift_off[l][2]};
+    terr_quad(j.terr + e, l, base, lift, c, s, j.ref_z, j.com_pos[e3 + 2], j.com_off ? j.com_off[e3 + 2] : 0.0, lin_m,
+              ang_m, j.terrain ? j.terrain + e3 : nullptr, j.ref + 24 * (size_t)e + 3 * l);
+
+    // 8. the touch-down trigger (WBI:295-300)
+    if (j.stages & SRBD_WB_TOUCH_DOWN) {
+        bool stable = true, next_all = true;
+        ga_leg_window(row, j.lookahead, stable, next_all);
+        int bits = (cur_f == 1.0f ? 1 : 0) | (prev_f == 1.0f ? 2 : 0) | (stable ? 4 : 0) | (next_all ? 8 : 0);
+        bits &= __shfl_xor(bits, 1, 4);
+        bits &= __shfl_xor(bits, 2, 4);
+        if (l == 0) {
+            int32_t edge = j.rising_edge[e];
+            j.optimize[e] = ga_trigger(&edge, (bits & 1) != 0, (bits & 2) != 0, (bits & 4) != 0, (bits & 8) != 0);
+            j.rising_edge[e] = edge;
+        }
+    } else if (l == 0) {
+        j.optimize[e] = 0;
+    }
 }
 
 // srbd_stc_touch_down of srbd_host.cpp per environment (srbd_gait_adapt.h ga_touch_down): lane e owns rising_edge[e]
@@ -560,6 +804,27 @@ unsigned blocks_of(int E) { return (unsigned)((4 * E + PROD_BLOCK - 1) / PROD_BL
 
 bool envs_ok(int32_t E) { return E >= 1 && E <= PROD_MAX_ENVS; }
 
+// The sequence call's own checks (srbd_pgg_contact_sequence_device), and its constants.
+bool pgg_seq_const(int32_t horizon, int32_t min_horizon, const double* dts, const int32_t* lens, int32_t n_dts,
+                          int32_t contact_stride, PggSeqConst& sc) {
+    if (!dts || !lens) return false;
+    if (horizon < min_horizon || horizon > SRBD_MAX_HORIZON || contact_stride < horizon) return false;
+    if (n_dts < 1 || n_dts > PROD_MAX_DTS) return false;
+    for (int i = 1, j = 0; i < horizon; ++i) {  // srbd_pgg_contact_sequence's walk: the reference's IndexError
+        if (i >= lens[j]) ++j;
+        if (j >= n_dts) return false;
+    }
+    sc = {};
+    for (int j = 0; j < n_dts; ++j) {
+        sc.dts[j] = dts[j];
+        sc.lens[j] = lens[j];
+    }
+    sc.n_dts = n_dts;
+    sc.H = horizon;
+    sc.stride = contact_stride;
+    return true;
+}
+
 }  // namespace
 
 extern "C" int srbd_pgg_run_device(srbd_pgg* d_pgg, int32_t num_envs, double dt, const double* d_step_freqs,
@@ -573,21 +838,9 @@ extern "C" int srbd_pgg_run_device(srbd_pgg* d_pgg, int32_t num_envs, double dt,
 extern "C" int srbd_pgg_contact_sequence_device(srbd_pgg* d_pgg, int32_t num_envs, int32_t horizon, const double* dts,
                                                 const int32_t* lens, int32_t n_dts, float* d_contacts,
                                                 int32_t contact_stride, void* hip_stream) {
-    if (!d_pgg || !dts || !lens || !d_contacts || !envs_ok(num_envs)) return SRBD_E_INVALID;
-    if (horizon < 1 || horizon > SRBD_MAX_HORIZON || contact_stride < horizon) return SRBD_E_INVALID;
-    if (n_dts < 1 || n_dts > PROD_MAX_DTS) return SRBD_E_INVALID;
-    for (int i = 1, j = 0; i < horizon; ++i) {  // srbd_pgg_contact_sequence's walk: the reference's IndexError
-        if (i >= lens[j]) ++j;
-        if (j >= n_dts) return SRBD_E_INVALID;
-    }
-    PggSeqConst sc = {};
-    for (int j = 0; j < n_dts; ++j) {
-        sc.dts[j] = dts[j];
-        sc.lens[j] = lens[j];
-    }
-    sc.n_dts = n_dts;
-    sc.H = horizon;
-    sc.stride = contact_stride;
+    if (!d_pgg || !d_contacts || !envs_ok(num_envs)) return SRBD_E_INVALID;
+    PggSeqConst sc;
+    if (!pgg_seq_const(horizon, 1, dts, lens, n_dts, contact_stride, sc)) return SRBD_E_INVALID;
     hipLaunchKernelGGL(pgg_contact_sequence_kernel, dim3(blocks_of(num_envs)), dim3(PROD_BLOCK), 0,
                        stream_of(hip_stream), d_pgg, num_envs, sc, d_contacts);
     return launch_status();
@@ -744,6 +997,85 @@ extern "C" int srbd_terrain_ref_step_device(srbd_terrain_est* d_terrain, int32_t
     j.terrain = io->terrain;
     hipLaunchKernelGGL(terrain_ref_step_kernel, dim3(blocks_of(num_envs)), dim3(PROD_BLOCK), 0, stream_of(hip_stream),
                        d_terrain, num_envs, j);
+    return launch_status();
+}
+
+extern "C" int srbd_pgg_start_stop_device(srbd_pgg* d_pgg, int32_t num_envs, const srbd_start_stop_batch_io* io,
+                                          void* hip_stream) {
+    if (!d_pgg || !io || !envs_ok(num_envs)) return SRBD_E_INVALID;
+    if (!io->feet || !io->hips || !io->base_pos || !io->euler || !io->base_lin_vel || !io->base_ang_vel ||
+        !io->ref_lin || !io->ref_ang || !io->current_contact)
+        return SRBD_E_INVALID;
+    if ((io->frg != nullptr) == (io->hip_offset != nullptr)) return SRBD_E_INVALID;  // exactly one of the two
+    StartStopJob j = {};
+    j.feet = io->feet;
+    j.hips = io->hips;
+    j.base_pos = io->base_pos;
+    j.euler = io->euler;
+    j.lin_vel = io->base_lin_vel;
+    j.ang_vel = io->base_ang_vel;
+    j.ref_lin = io->ref_lin;
+    j.ref_ang = io->ref_ang;
+    j.contact = io->current_contact;
+    j.frg = io->frg;
+    j.hip_offset = io->hip_offset ? *io->hip_offset : 0.0;  // a host value: it travels in the kernel arguments
+    j.action = io->action;
+    hipLaunchKernelGGL(start_stop_kernel, dim3(blocks_of(num_envs)), dim3(PROD_BLOCK), 0, stream_of(hip_stream), d_pgg,
+                       num_envs, j);
+    return launch_status();
+}
+
+extern "C" int srbd_wb_update_device(srbd_pgg* d_pgg, srbd_frg* d_frg, srbd_terrain_est* d_terrain, float* d_contact,
+                                     int32_t* d_rising_edge, int32_t num_envs, const srbd_wb_update_io* io,
+                                     void* hip_stream) {
+    if (!d_pgg || !d_frg || !d_terrain || !d_contact || !io || !envs_ok(num_envs)) return SRBD_E_INVALID;
+    if (io->stages & ~(SRBD_WB_VM | SRBD_WB_START_STOP | SRBD_WB_TOUCH_DOWN)) return SRBD_E_INVALID;
+    if (!io->com_pos || !io->base_pos || !io->base_lin_vel || !io->euler || !io->base_ang_vel || !io->feet ||
+        !io->hips || !io->ref_lin || !io->ref_ang || !io->contacts || !io->seeds || !io->ref || !io->optimize)
+        return SRBD_E_INVALID;
+    WbJob j = {};
+    if (!pgg_seq_const(io->horizon, 2, io->dts, io->lens, io->n_dts, io->contact_stride, j.sc)) return SRBD_E_INVALID;
+    if (io->stages & SRBD_WB_TOUCH_DOWN) {
+        if (!d_rising_edge) return SRBD_E_INVALID;
+        if (io->lookahead < 1 || io->lookahead > io->horizon - 1) return SRBD_E_INVALID;  // the reference's IndexError
+    }
+    if (!std::isfinite(io->dt) || !std::isfinite(io->ref_z) || !std::isfinite(io->com_height_nominal) ||
+        !std::isfinite(io->gravity) || !(io->gravity > 0.0))
+        return SRBD_E_INVALID;
+    if ((io->stages & SRBD_WB_VM) && io->max_distance != io->max_distance) return SRBD_E_INVALID;
+    j.com_pos = io->com_pos;
+    j.base_pos = io->base_pos;
+    j.base_vel = io->base_lin_vel;
+    j.euler = io->euler;
+    j.ang_vel = io->base_ang_vel;
+    j.feet = io->feet;
+    j.hips = io->hips;
+    j.ref_lin = io->ref_lin;
+    j.ref_ang = io->ref_ang;
+    j.com_off = io->com_pos_offset_w;
+    j.dt = io->dt;
+    j.max_distance = io->max_distance;
+    j.root = sqrt(io->com_height_nominal / io->gravity);  // once, here: srbd_frg_step_device's value
+    j.ref_z = io->ref_z;
+    j.lin_out = io->lin_out;
+    j.ang_out = io->ang_out;
+    j.contacts = io->contacts;
+    j.cur_out = io->current_contact;
+    j.prev_out = io->previous_contact;
+    j.seeds = io->seeds;
+    j.ref = io->ref;
+    j.terrain = io->terrain;
+    j.optimize = io->optimize;
+    j.action = io->action;
+    j.pgg = d_pgg;
+    j.frg = d_frg;
+    j.terr = d_terrain;
+    j.contact = d_contact;
+    j.rising_edge = d_rising_edge;
+    j.lookahead = io->lookahead;
+    j.stages = io->stages;
+    hipLaunchKernelGGL(wb_update_kernel, dim3(blocks_of(num_envs)), dim3(PROD_BLOCK), 0, stream_of(hip_stream),
+                       num_envs, j);
     return launch_status();
 }
 

@@ -21,7 +21,8 @@
 // Stale constraint: VFA:209-222 assigns footholds_constraints[leg] only for a leg with a feasible candidate, and
 // neither reset nor get_footholds_adapted touches it, so an infeasible leg keeps the box of its last feasible search
 // (NaN here where the reference still holds None) while its foothold is the seed at its terrain height (VFA:223-228).
-// Out of scope: the 'height' and 'vfa' strategies; the early-stance detector, start-and-stop and inverse kinematics;
+// Out of scope: the 'height' and 'vfa' strategies; the early-stance detector and inverse kinematics (start-and-stop is
+// the gait generator's, srbd_start_stop.h);
 // compacting the searching environments into a smaller grid (the count would have to reach the host).  The
 // per-environment reset of this state is srbd_reset.h's.
 #pragma once

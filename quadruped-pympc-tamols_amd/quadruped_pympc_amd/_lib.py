@@ -297,6 +297,27 @@ class SrbdLoopResetIo(C.Structure):
                 ("num_params", _I), ("n_contact_rows", _I)]
 
 
+class SrbdStartStopBatchIo(C.Structure):
+    """srbd_start_stop_batch_io (include/srbd_mpc.h): the device arrays of one srbd_pgg_start_stop_device call."""
+    _fields_ = [("feet", _P), ("hips", _P), ("base_pos", _P), ("euler", _P), ("base_lin_vel", _P),
+                ("base_ang_vel", _P), ("ref_lin", _P), ("ref_ang", _P), ("current_contact", _P), ("frg", _P),
+                ("hip_offset", _DP), ("action", _P)]
+
+
+WB_VM, WB_START_STOP, WB_TOUCH_DOWN = 1, 2, 4
+
+
+class SrbdWbUpdateIo(C.Structure):
+    """srbd_wb_update_io (include/srbd_mpc.h): the arrays and shared values of one srbd_wb_update_device call."""
+    _fields_ = [("com_pos", _P), ("base_pos", _P), ("base_lin_vel", _P), ("euler", _P), ("base_ang_vel", _P),
+                ("feet", _P), ("hips", _P), ("ref_lin", _P), ("ref_ang", _P), ("com_pos_offset_w", _P),
+                ("dts", _DP), ("lens", _IP),
+                ("dt", _D), ("max_distance", _D), ("com_height_nominal", _D), ("gravity", _D), ("ref_z", _D),
+                ("lin_out", _P), ("ang_out", _P), ("contacts", _P), ("current_contact", _P), ("previous_contact", _P),
+                ("seeds", _P), ("ref", _P), ("terrain", _P), ("optimize", _P), ("action", _P),
+                ("n_dts", _I), ("horizon", _I), ("contact_stride", _I), ("lookahead", _I), ("stages", _I), ("pad", _I)]
+
+
 SHM_DOUBLES = 75
 
 
@@ -422,6 +443,10 @@ SIGNATURES.update({
     # the controller interface's step of a batch, and the host twin of its key schedule
     "srbd_batch_interface_step_device": (_I, [_P, C.POINTER(BatchInterfaceIO), _P]),
     "srbd_selftest_interface_keys": (_I, [_P, _I, _I, _I, _P]),
+    # start-and-stop (host and device) and update_state_and_reference in one launch
+    "srbd_pgg_start_stop": (_I, [C.POINTER(SrbdPgg), _DP, _DP, _D, _DP, _DP, _DP, _DP, _DP, _DP, _DP]),
+    "srbd_pgg_start_stop_device": (_I, [_P, _I, C.POINTER(SrbdStartStopBatchIo), _P]),
+    "srbd_wb_update_device": (_I, [_P, _P, _P, _P, _P, _I, C.POINTER(SrbdWbUpdateIo), _P]),
 })
 
 # srbd_time_launch kinds (include/srbd_mpc.h)
@@ -2090,3 +2115,43 @@ def loop_reset_device(mask, initial_feet=None, *, pgg=None, frg=None, stc=None, 
         return rc
 
     _enqueue(dev, stream, lambda: None, call, "srbd_loop_reset_device")
+
+
+def pgg_start_stop_device(pgg, feet, hips, base_pos, euler, base_lin_vel, base_ang_vel, ref_lin, ref_ang,
+                          current_contact, *, frg=None, hip_offset=None, out=None, stream=None):
+    """srbd_pgg_start_stop_device: ``update_start_and_stop`` (periodic_gait_generator.py:128-196) of every environment,
+    one launch enqueued on ``stream`` (None: torch's current stream) without a host synchronisation.  pgg
+    (E, PGG_BYTES) uint8: the srbd_pgg structs, rewritten in place where an environment stops or takes its gait up
+    again.  feet / hips (E, 4, 3), base_pos / euler (roll, pitch, yaw) / base_lin_vel / base_ang_vel / ref_lin /
+    ref_ang (E, 3) float64; current_contact (E, 4) float32.  Exactly one of frg (E, FRG_BYTES) uint8, whose
+    hip_offset field is read per environment, and hip_offset, one float shared by the environments.  out None
+    (allocated) or (E,) int32.  Returns the actions (E,) int32: 0 untouched, 1 stopped, 2 restored."""
+    import torch
+
+    E = _num_envs_of(pgg)
+    if (frg is None) == (hip_offset is None):
+        raise ValueError("give exactly one of frg and hip_offset")
+    f64, f32_, u8 = (torch.float64,), (torch.float32,), (torch.uint8,)
+    specs = [("pgg", pgg, (E, PGG_BYTES), u8), ("feet", feet, (E, 4, 3), f64), ("hips", hips, (E, 4, 3), f64),
+             ("base_pos", base_pos, (E, 3), f64), ("euler", euler, (E, 3), f64),
+             ("base_lin_vel", base_lin_vel, (E, 3), f64), ("base_ang_vel", base_ang_vel, (E, 3), f64),
+             ("ref_lin", ref_lin, (E, 3), f64), ("ref_ang", ref_ang, (E, 3), f64),
+             ("current_contact", current_contact, (E, 4), f32_)]
+    if frg is not None:
+        specs.append(("frg", frg, (E, FRG_BYTES), u8))
+    if out is not None:
+        specs.append(("out", out, (E,), (torch.int32,)))
+    dev = _device_tensors(specs)
+    shared = None if hip_offset is None else C.c_double(float(hip_offset))
+
+    def call(o, s):
+        io = SrbdStartStopBatchIo(feet=feet.data_ptr(), hips=hips.data_ptr(), base_pos=base_pos.data_ptr(),
+                                  euler=euler.data_ptr(), base_lin_vel=base_lin_vel.data_ptr(),
+                                  base_ang_vel=base_ang_vel.data_ptr(), ref_lin=ref_lin.data_ptr(),
+                                  ref_ang=ref_ang.data_ptr(), current_contact=current_contact.data_ptr(),
+                                  frg=None if frg is None else frg.data_ptr(),
+                                  hip_offset=None if shared is None else C.pointer(shared), action=o.data_ptr())
+        return lib.srbd_pgg_start_stop_device(pgg.data_ptr(), E, C.byref(io), s)
+
+    return _enqueue(dev, stream, lambda: torch.empty(E, dtype=torch.int32, device=dev) if out is None else out, call,
+                    "srbd_pgg_start_stop_device")

@@ -113,6 +113,29 @@ class PeriodicGaitGenerator:
         self.gait_type = self.previous_gait_type
         self.reset()
 
+    def update_start_and_stop(self, feet_pos, hip_pos, hip_offset, base_pos, base_ori_euler_xyz, base_lin_vel,
+                              base_ang_vel, ref_base_lin_vel, ref_base_ang_vel, current_contact):
+        """The reference's ``update_start_and_stop`` (PGG:128-196) in one ``srbd_pgg_start_stop`` call: full stance
+        when the robot stands still with no command, the previous gait back when it does not.  feet_pos / hip_pos:
+        a ``LegsAttr`` (FL FR RL RR) or a (4, 3) array.  Returns 0 / 1 / 2: untouched / stopped / restored (the
+        reference returns None)."""
+        def legs(p):
+            if all(hasattr(p, n) for n in ("FL", "FR", "RL", "RR")):
+                p = [p.FL, p.FR, p.RL, p.RR]
+            return np.ascontiguousarray(p, dtype=np.float64).reshape(4, 3)
+
+        def vec(v, n):
+            return np.ascontiguousarray(v, dtype=np.float64).reshape(n)
+
+        feet, hips = legs(feet_pos), legs(hip_pos)
+        args = [vec(base_pos, 3), vec(base_ori_euler_xyz, 3), vec(base_lin_vel, 3), vec(base_ang_vel, 3),
+                vec(ref_base_lin_vel, 3), vec(ref_base_ang_vel, 3), vec(current_contact, 4)]
+        action = _check(_lib.lib.srbd_pgg_start_stop(self._gp, _lib.dptr(feet), _lib.dptr(hips), float(hip_offset),
+                                                     *[_lib.dptr(a) for a in args]), "update_start_and_stop")
+        if action:
+            self.time_before_switch_freq = 0  # reset()'s
+        return action
+
 
 class BatchedPeriodicGaitGenerator:
     """``num_envs`` periodic gait generators whose state lives on the device (``srbd_pgg_run_device``,
@@ -262,3 +285,19 @@ class BatchedPeriodicGaitGenerator:
             self._seq_key = key
         return _lib.pgg_contact_sequence_device(self.state, self.horizon, self._dts, self._lens, out=out,
                                                 stream=stream)
+
+    def update_start_and_stop(self, feet_pos, hip_pos, hip_offset, base_pos, base_ori_euler_xyz, base_lin_vel,
+                              base_ang_vel, ref_base_lin_vel, ref_base_ang_vel, current_contact, out=None,
+                              stream=None):
+        """``update_start_and_stop`` of every environment (``srbd_pgg_start_stop_device``), one launch and no host
+        wait.  feet_pos / hip_pos (E, 4, 3), the five vectors and the command (E, 3) float64 tensors,
+        current_contact (E, 4) float32; hip_offset a float shared by the environments, or a
+        ``BatchedFootholdReferenceGenerator`` (or its state tensor), whose per-environment hip offsets are read.
+        Returns the actions (E,) int32: 0 untouched, 1 stopped (full stance), 2 restored."""
+        frg = getattr(hip_offset, "state", hip_offset)
+        shared = None
+        if not hasattr(frg, "data_ptr"):
+            frg, shared = None, float(hip_offset)
+        return _lib.pgg_start_stop_device(self.state, feet_pos, hip_pos, base_pos, base_ori_euler_xyz, base_lin_vel,
+                                          base_ang_vel, ref_base_lin_vel, ref_base_ang_vel, current_contact, frg=frg,
+                                          hip_offset=shared, out=out, stream=stream)
