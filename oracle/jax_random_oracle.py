@@ -220,7 +220,7 @@ def randint(key, M: int, minval: int, maxval: int, partitionable: bool = True) -
     mult = (mult * mult) % span
     off = ((hi % span) * mult + (lo % span)) & 0xFFFFFFFF  # uint32 arithmetic
     off = off % span
-    return (minval + off).astype(np.int32)
+    return (off.astype(np.int64) + int(minval)).astype(np.int32)  # off is unsigned: a negative minval needs int64
 
 
 def choice(key, a, M: int, partitionable: bool = True) -> np.ndarray:

@@ -24,6 +24,11 @@ analytic known-answer tests (``tests/test_oracle_kat.py``: free fall, static
 stance, cofactor inverse vs ``numpy.linalg.inv``, zero-noise MPPI, n_stance=0,
 spline identities) and by agreement with the independent C restatement
 ``oracle/srbd_oracle.c``.
+
+Since then the program logic is pinned: ``oracle/record_srbd_reference.py`` executes the
+reference's files under a numpy stand-in for jax and ``tests/test_srbd_reference.py`` holds this
+oracle to what they returned, within the parity tolerances.  XLA's own rounding and reduction
+order stay unobserved.
 """
 from __future__ import annotations
 

@@ -12,6 +12,11 @@ tamols_go2.npz too is the oracle's own output.
 Not written here: tamols_ref_*.npz, the reference's own TAMOLS scores and footholds.
 oracle/record_tamols_reference.py records them from a checkout of the reference
 (tests/test_tamols_reference.py, tests/test_gpu_tamols_reference.py).
+Nor srbd_ref_*.npz, prepare_state_ref.npz and pgg_ref.npz, the reference's own sampling-controller,
+state-preparation and gait-generator outputs: oracle/record_srbd_reference.py records them by executing
+the reference's files under a numpy stand-in for jax (tests/test_srbd_reference.py,
+tests/test_gpu_srbd_reference.py).  srbd_c*.npz, ga_*.npz, prepare_state.npz and pgg_sequences.npz,
+written here, are the oracle's outputs.
 
     python tests/golden/make_golden.py
 """

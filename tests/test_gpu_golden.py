@@ -13,7 +13,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-SRBD = sorted(glob.glob(os.path.join(GOLDEN, "srbd_*.npz")))
+SRBD = sorted(glob.glob(os.path.join(GOLDEN, "srbd_c*.npz")))  # the oracle's; srbd_ref_*.npz are the reference's
 GA = sorted(glob.glob(os.path.join(GOLDEN, "ga_*.npz")))
 f32 = np.float32
 

@@ -418,3 +418,27 @@ def test_device_loop_equals_host_loop(lib):
     finally:
         on_dev.close()
         on_host.close()
+
+
+def test_device_generators_match_reference_recording(lib):
+    """srbd_pgg_run_device / srbd_pgg_contact_sequence_device, E = 8 with one gait type each, against
+    tests/golden/pgg_ref.npz (the reference's numpy PeriodicGaitGenerator, recorded).  Exact equality."""
+    import os
+
+    g = dict(np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pgg_ref.npz"),
+                     allow_pickle=False))
+    E, H = 8, 12
+    params = np.stack([g[f"gait{e}_params"] for e in range(E)])
+    gen = BatchedPeriodicGaitGenerator(E, params[:, 0], params[:, 1], np.arange(E, dtype=np.int32), H)
+    runs = np.stack([g[f"gait{e}_runs"] for e in range(E)], axis=2)              # (60, 5, E, 4)
+    want = {"uniform": np.stack([g[f"gait{e}_uniform"][:, :, :H] for e in range(E)], axis=1),
+            "nonuniform": np.stack([g[f"gait{e}_nonuniform"][:, :, :H] for e in range(E)], axis=1)}
+    got_runs, got = [], {"uniform": [], "nonuniform": []}
+    for k in range(60):
+        got_runs.append([gen.run(0.002) for _ in range(5)])
+        got["uniform"].append(gen.compute_contact_sequence([0.02], [H]))
+        got["nonuniform"].append(gen.compute_contact_sequence([0.01, 0.02], [2, H]))
+    torch.cuda.synchronize()
+    np.testing.assert_array_equal(torch.stack([torch.stack(r) for r in got_runs]).cpu().numpy(), runs.astype(f32))
+    for kind in want:
+        np.testing.assert_array_equal(torch.stack(got[kind]).cpu().numpy(), want[kind].astype(f32), err_msg=kind)

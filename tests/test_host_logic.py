@@ -447,3 +447,23 @@ def test_controller_copies_own_their_staging():
         np.testing.assert_array_equal(c.master_key, _lib.jax_split(k_orig, 2)[0])
     m.with_newkey()
     np.testing.assert_array_equal(m.master_key, _lib.jax_split(k_orig, 2)[0])
+
+
+def test_pgg_matches_reference_recording():
+    """The host srbd_pgg_* functions against tests/golden/pgg_ref.npz: what the reference's numpy
+    PeriodicGaitGenerator returned (oracle/record_srbd_reference.py), all 8 gait types, 60 x 5 run(0.002, freq)
+    steps with the uniform and the [0.01, 0.02] x [2, 12] look-ahead after each group.  Exact equality."""
+    import os
+
+    g = dict(np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pgg_ref.npz"),
+                     allow_pickle=False))
+    for gait in range(8):
+        duty, freq = g[f"gait{gait}_params"]
+        pgg = PeriodicGaitGenerator(duty, freq, gait, 12)
+        for k in range(60):
+            for j in range(5):
+                np.testing.assert_array_equal(pgg.run(0.002, freq), g[f"gait{gait}_runs"][k, j])
+            np.testing.assert_array_equal(pgg.compute_contact_sequence([0.02], [12]), g[f"gait{gait}_uniform"][k])
+            np.testing.assert_array_equal(pgg.compute_contact_sequence([0.01, 0.02], [2, 12]),
+                                          g[f"gait{gait}_nonuniform"][k])
+            np.testing.assert_array_equal(pgg.phase_signal, g[f"gait{gait}_phase"][k])
