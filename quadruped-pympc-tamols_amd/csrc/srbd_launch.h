@@ -1,4 +1,5 @@
-// srbd_launch.h -- internal launchers shared by srbd_kernels.hip, tamols_kernel.hip and srbd_api.hip.
+// srbd_launch.h -- internal launchers shared by srbd_kernels.hip, tamols_kernel.hip, srbd_api.hip and
+// srbd_api_batch.hip.
 #pragma once
 
 #include <string>

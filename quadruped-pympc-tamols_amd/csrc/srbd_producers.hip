@@ -37,8 +37,9 @@
 // behind it the table of a srbd_terrain_set (terrain_kernel.hip) and the caller's scene indices.
 // loop_reset_kernel (srbd_loop_reset_device) restarts the environments a mask names (srbd_reset.h; simulation/
 // simulation.py:773-781, wb_interface.py:469-484): one wave per environment, see the kernel.
-// iface_prologue_kernel and iface_epilogue_kernel are the two launches srbd_batch_interface_step_device (srbd_api.hip)
-// puts around its sampling iterations (SCI = quadruped_pympc/interfaces/srbd_controller_interface.py:113-180,
+// iface_prologue_kernel and iface_epilogue_kernel are the two launches srbd_batch_interface_step_device
+// (srbd_api_batch.hip) puts around its sampling iterations (SCI =
+// quadruped_pympc/interfaces/srbd_controller_interface.py:113-180,
 // :225-229): prepare_state through the device function prepare_state_kernel runs and the key schedule of
 // srbd_iface.h ahead of them; the GRFs times the current contact, the footholds and previous_contact_mpc behind them.
 // One lane per (environment, leg), no cross-lane traffic.
@@ -860,7 +861,7 @@ extern "C" int srbd_prepare_state_device(int32_t num_envs, const double* d_state
     return launch_status();
 }
 
-// srbd_batch_interface_step_device (srbd_api.hip, which owns the batch) enqueues its two launches through these.
+// srbd_batch_interface_step_device (srbd_api_batch.hip, which owns the batch) enqueues its two launches through these.
 void srbd::launch_iface_prologue(const srbd_batch_interface_io& io, int rng, int num_params, uint64_t* step_keys, int E,
                                  hipStream_t s) {
     IfaceJob j = {};

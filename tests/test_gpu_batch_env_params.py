@@ -246,6 +246,44 @@ def test_device_setter_equals_host_setter(lib):
         db.close()
 
 
+def test_device_setter_on_one_stream_step_on_another(lib):
+    """The device setter joins the device calls' event protocol: a step on another stream follows the setter's
+    launch, and a setter on another stream follows the previous step's reads of the records.  Expected values: the
+    same calls on one stream, on another batch."""
+    E = 3
+    cases = env_cases(E, N=64, method="mppi", par="zero_order", H=12)
+    tp, tp2 = params_tensor(env_params(lib, cases)), params_tensor(env_params(lib, cases, shift=2))
+    seeds, counters = tdev.default_keys(E)
+    arr = tdev.arrays_of(cases)
+    cfg = product_cfg(cases[0])
+    one, two = lib.BatchContext(cfg, E), lib.BatchContext(cfg, E)
+    try:
+        one.set_env_params_device(tp)
+        want = tdev.device_step(one, arr, seeds, counters)
+        one.set_env_params_device(tp2)
+        want2 = tdev.device_step(one, arr, seeds, counters)
+        assert want["costs"].tobytes() != want2["costs"].tobytes()
+        s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+        two.set_env_params_device(tp, stream=s1)
+        tdev.assert_same(tdev.device_step(two, arr, seeds, counters, stream=s2), want, "set on s1, step on s2")
+        # and back, nothing synchronised in between: the step on s2 reads the first records, the setter on s1 follows
+        # those reads, and the next step on s2 follows the setter
+        best = tdev.dev(arr["best"])
+        ins = [tdev.dev(arr[k]) for k in ("states", "refs", "contacts")]
+        keys = [tdev.dev(seeds, torch.int64), tdev.dev(counters, torch.int64)]
+        torch.cuda.synchronize()
+        with torch.cuda.stream(s2):
+            torch.cuda._sleep(50_000_000)  # holds the step back, so an unordered setter would overtake it
+        out = two.step_device(*ins, best, *keys, want_costs=True, stream=s2)
+        two.set_env_params_device(tp2, stream=s1)
+        got2 = tdev.device_step(two, arr, seeds, counters, stream=s2)
+        tdev.assert_same(tdev.to_host(out, best), want, "step on s2, then set on s1")
+        tdev.assert_same(got2, want2, "set on s1, then step on s2")
+    finally:
+        one.close()
+        two.close()
+
+
 def test_device_setter_argument_checks(lib):
     E = 2
     cases = env_cases(E, N=64, method="mppi", par="zero_order", H=12)
