@@ -666,6 +666,70 @@ int srbd_batch_set_env_params_device(srbd_batch* b, const srbd_env_params* d_par
 int srbd_batch_get_env_params(srbd_batch* b, srbd_env_params* out);
 int srbd_batch_clear_env_params(srbd_batch* b);
 
+/* The full-horizon plan of one parameter row per environment: the trajectory a step's rollout computes for a row and
+ * drops -- every step form returns the first knot alone (grf, predicted_state), as the reference's compute_control
+ * does.  Reference lines restated: compute_rollout, centroidal_nmpc_jax.py:316-496 (caller-given contacts) and
+ * centroidal_nmpc_jax_gait_adaptive.py:326-501 (gait-adaptive sampling: the sample's own contact sequence from its
+ * step frequency, the per-leg stance counter, horizon_leg = stance steps + 1 and the negative-index wrap), with the
+ * saturation of :686-687.
+ *   One launch for all E environments on the caller's stream (plan_kernel, one thread per environment): params[e] is
+ *   decoded, shaped and integrated over the H steps from states[e] and refs[e], with the batch's current settings --
+ *   srbd_batch_set_gait[_device] (the contact flags then come from environment e's leg phases and freqs[e], the step's
+ *   best_freq output or any frequency of the set; contacts is not read), srbd_batch_set_cost_terms (the terms are
+ *   part of the costs) and srbd_batch_set_env_params (environment e's robot).  A CEM batch is served the same way:
+ *   only params matter.
+ *   states, refs : the rows the step rolled out from (prepared rows, as the step takes them).
+ *   Outputs, float32, any of them NULL when not wanted (at least one is not):
+ *     plan_states   E x H x 12  the 12 evolving states after step n (the feet are constant: states[e][12..23])
+ *     plan_grfs     E x H x 12  the forces of step n after the contact mask and the clip
+ *     plan_contacts E x 4 x H   the contact flags used (with gait-adaptive sampling the only place they are visible)
+ *     plan_run_cost E x H       (cost_x + cost_y) + cost_z accumulated up to and including step n
+ *     plan_cost     E           the row's cost: the last running cost + the feet term (+ (f - 1.3) 100 (f - 1.3) with
+ *                               gait-adaptive sampling), saturated to 1 000 000 when not finite
+ *   Equivalence: with params[e] = the step's warm start + its noise row r (for CEM as the step scales it) and, with
+ *   gait-adaptive sampling, freqs[e] = row r's frequency, plan_cost[e] is the step's costs[e][r] bit for bit: the
+ *   launch runs the functions the rollouts run, in their order, unfused.  With params = the step's new best_params,
+ *   plan_states[e][0] and plan_grfs[e][0] are predicted_state[e][0..11] and grf[e] -- bit for bit for the zero-order
+ *   parametrization; the splines' final decode evaluates step 0.0 with horizon_leg 1 (NMPC:706-710), the plan step 0
+ *   of H, the same value up to rounding; with gait-adaptive sampling only where the caller's contact column 0 equals
+ *   the sample's (the final GRFs use the caller's sequence, GA:720-796).  Environment e of the batch form equals
+ *   srbd_plan on a context created with e's configuration and settings, and srbd_batch_plan returns the device form's
+ *   bytes.
+ *   srbd_batch_plan_device: every pointer device memory of the batch's device, arrays must not overlap.  hip_stream as
+ *   srbd_batch_step_device reads it; the call makes no synchronising HIP call and no host copy, and follows that
+ *   call's ordering rule (it waits on, then records, the batch's event), so enqueued behind a step on any stream it
+ *   reads that step's outputs, and a later step is not disturbed.  Capturing the call into a HIP graph is not
+ *   supported.
+ *   srbd_batch_plan: the same arrays in host memory: upload, the launch, one wait, download.
+ *   srbd_plan: the single-context form, the same kernel at E = 1 with the context's settings (srbd_set_gait: freq is
+ *   read and contact is not; srbd_set_cost_terms, also together with srbd_set_gait); it synchronises the context's
+ *   stream.  A sharded context (world_size > 1) is refused.
+ *   SRBD_E_INVALID (with a message, before anything is enqueued): b, c or io NULL, a required pointer NULL (states,
+ *   refs, params; contacts without gait-adaptive sampling; freqs with it), every output NULL, contact_stride < H.
+ *   Out of scope: the plan from inside the step's launch, plans of rows the caller does not pass, the sharded step,
+ *   graph capture, and a batch with gait-adaptive sampling and cost terms at once (the batch refuses that combination
+ *   itself; srbd_plan on one context runs it). */
+typedef struct srbd_batch_plan_io {
+    const float* states;      /* E x 24: the rows the step rolled out from (prepared) */
+    const float* refs;        /* E x 24 */
+    const float* contacts;    /* E x 4 x contact_stride; ignored with gait-adaptive sampling */
+    const float* params;      /* E x P: any parameter rows, e.g. the step's new best_params */
+    const float* freqs;       /* E: required when gait fields are set, else ignored */
+    int32_t contact_stride, pad;
+    float* plan_states;       /* E x H x 12, or NULL */
+    float* plan_grfs;         /* E x H x 12, or NULL */
+    float* plan_contacts;     /* E x 4 x H, or NULL */
+    float* plan_run_cost;     /* E x H, or NULL */
+    float* plan_cost;         /* E, or NULL */
+} srbd_batch_plan_io;
+int srbd_batch_plan_device(srbd_batch* b, const srbd_batch_plan_io* io, void* hip_stream);
+int srbd_batch_plan(srbd_batch* b, const float* states, const float* refs, const float* contacts,
+                    int32_t contact_stride, const float* params, const float* freqs, float* plan_states,
+                    float* plan_grfs, float* plan_contacts, float* plan_run_cost, float* plan_cost);
+int srbd_plan(srbd_ctx* c, const float* state, const float* ref, const float* contact, int32_t contact_stride,
+              const float* params, float freq, float* plan_states, float* plan_grfs, float* plan_contacts,
+              float* plan_run_cost, float* plan_cost);
+
 /* The producers of the device-resident step on the device: the periodic gait generator and
  * prepare_state_and_reference (srbd_host.h: srbd_pgg_run, srbd_pgg_contact_sequence, srbd_prepare_state) for
  * num_envs environments per call, so that generator.run -> contact sequence -> prepare -> srbd_batch_step_device

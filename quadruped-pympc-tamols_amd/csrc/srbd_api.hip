@@ -423,6 +423,7 @@ extern "C" void srbd_destroy(srbd_ctx* c) {
     (void)hipFree(c->d_gtag);
     if (c->h_outt) (void)hipHostFree(c->h_outt);
     (void)hipFree(c->d_ga_freq);
+    (void)hipFree(c->d_plan);
     if (c->h_in) (void)hipHostFree(c->h_in);
     if (c->h_out) (void)hipHostFree(c->h_out);
     if (c->h_flag) (void)hipHostFree(c->h_flag);
@@ -1124,6 +1125,61 @@ extern "C" int srbd_set_cost_terms(srbd_ctx* c, const float* r_force, float w_sm
         mc.cost_cone = w_cone;
         drop_graphs(c);  // kernels take ModelConst by value: recapture
     }
+    return SRBD_OK;
+}
+
+// The full-horizon plan of one parameter row (srbd_plan.hip): srbd_batch_plan_device's kernel at E = 1 with this
+// context's settings.  The gait fields are read from the staging h_in through its device alias, where srbd_set_gait
+// wrote them (fill_input leaves them alone).  Host in, host out; synchronises the context's stream.
+extern "C" int srbd_plan(srbd_ctx* c, const float* state, const float* ref, const float* contact,
+                         int32_t contact_stride, const float* params, float freq, float* plan_states, float* plan_grfs,
+                         float* plan_contacts, float* plan_run_cost, float* plan_cost) {
+    if (!c) return fail(nullptr, SRBD_E_INVALID, "srbd_plan: null context");
+    if (!state || !ref || !params) return fail(c, SRBD_E_INVALID, "srbd_plan: null required pointer");
+    if (!plan_states && !plan_grfs && !plan_contacts && !plan_run_cost && !plan_cost)
+        return fail(c, SRBD_E_INVALID, "srbd_plan: every output is NULL");
+    const ModelConst& mc = c->mc;
+    if (c->cfg.world_size > 1)
+        return fail(c, SRBD_E_INVALID, "srbd_plan: a sharded context (world_size > 1) has no plan form");
+    if (!mc.ga && !contact) return fail(c, SRBD_E_INVALID, "srbd_plan: null required pointer: contact");
+    if (!mc.ga && contact_stride < mc.H)
+        return fail(c, SRBD_E_INVALID, "srbd_plan: contact_stride is smaller than the horizon");
+    arm_cancel(c);
+    HIP_TRY(c, hipSetDevice(c->cfg.device_id));
+    const size_t H = (size_t)mc.H, P = (size_t)mc.P;
+    // floats: state | ref | contact (stride H) | params | freq, then the five outputs on 16-byte boundaries
+    auto al = [](size_t x) { return (x + 3) & ~(size_t)3; };
+    const size_t o_ct = 48, o_pr = o_ct + 4 * H, o_fq = o_pr + P, o_ps = al(o_fq + 1), o_pg = o_ps + 12 * H,
+                 o_pc = o_pg + 12 * H, o_rc = o_pc + 4 * H, o_co = al(o_rc + H), total = o_co + 1;
+    if (!c->d_plan) HIP_TRY(c, hipMalloc((void**)&c->d_plan, sizeof(float) * total));
+    float* d = c->d_plan;
+    hipStream_t s = c->stream;
+    HIP_TRY(c, hipMemcpyAsync(d, state, sizeof(float) * 24, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(d + 24, ref, sizeof(float) * 24, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(d + o_pr, params, sizeof(float) * P, hipMemcpyHostToDevice, s));
+    if (mc.ga)
+        HIP_TRY(c, hipMemcpyAsync(d + o_fq, &freq, sizeof(float), hipMemcpyHostToDevice, s));
+    else
+        HIP_TRY(c, hipMemcpy2DAsync(d + o_ct, sizeof(float) * H, contact, sizeof(float) * (size_t)contact_stride,
+                                    sizeof(float) * H, 4, hipMemcpyHostToDevice, s));
+    PlanJob j = {};
+    j.states = d, j.refs = d + 24, j.contacts = d + o_ct, j.params = d + o_pr, j.freqs = d + o_fq;
+    j.plan_states = plan_states ? d + o_ps : nullptr, j.plan_grfs = plan_grfs ? d + o_pg : nullptr;
+    j.plan_contacts = plan_contacts ? d + o_pc : nullptr, j.plan_run_cost = plan_run_cost ? d + o_rc : nullptr;
+    j.plan_cost = plan_cost ? d + o_co : nullptr;
+    j.in_arr = c->d_in_host, j.in_single = 1;
+    j.envs = nullptr;
+    memcpy(j.q_feet, c->cfg.q_diag + 12, sizeof(j.q_feet));
+    j.mg = mc.mg;
+    j.contact_stride = (int32_t)H, j.E = 1, j.hc = plan_chunk(mc.H);
+    HIP_TRY(c, launch_plan(mc, j, s));
+    HIP_TRY(c, hipGetLastError());
+    if (plan_states) HIP_TRY(c, hipMemcpyAsync(plan_states, d + o_ps, sizeof(float) * 12 * H, hipMemcpyDeviceToHost, s));
+    if (plan_grfs) HIP_TRY(c, hipMemcpyAsync(plan_grfs, d + o_pg, sizeof(float) * 12 * H, hipMemcpyDeviceToHost, s));
+    if (plan_contacts) HIP_TRY(c, hipMemcpyAsync(plan_contacts, d + o_pc, sizeof(float) * 4 * H, hipMemcpyDeviceToHost, s));
+    if (plan_run_cost) HIP_TRY(c, hipMemcpyAsync(plan_run_cost, d + o_rc, sizeof(float) * H, hipMemcpyDeviceToHost, s));
+    if (plan_cost) HIP_TRY(c, hipMemcpyAsync(plan_cost, d + o_co, sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
     return SRBD_OK;
 }
 

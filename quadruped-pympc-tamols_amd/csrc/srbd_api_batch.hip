@@ -53,6 +53,8 @@ struct srbd_batch {
     // srbd_batch_interface_step_device: the step keys its prologue writes and its iterations' steps read,
     // SRBD_MAX_IFACE_ITERS rows of 2 E words (row i: E seeds, then E counters)
     uint64_t* d_iface_keys = nullptr;
+    // srbd_batch_plan (the host form): its device copies of the caller's arrays, allocated at the first call
+    float* d_plan = nullptr;
 };
 
 // The internal buffers (d_in, d_noise, d_rec, d_costs, d_count, d_ga_freq) are shared by the host path and the device
@@ -154,6 +156,7 @@ extern "C" void srbd_batch_destroy(srbd_batch* b) {
     (void)hipFree(b->d_env_raw);
     (void)hipFree(b->d_env);
     (void)hipFree(b->d_iface_keys);
+    (void)hipFree(b->d_plan);
     if (b->h_in) (void)hipHostFree(b->h_in);
     if (b->h_out) (void)hipHostFree(b->h_out);
     if (b->c.h_flag) (void)hipHostFree(b->c.h_flag);
@@ -759,4 +762,107 @@ extern "C" int srbd_batch_interface_step_device(srbd_batch* b, const srbd_batch_
     // the event again, behind the epilogue: previous_contact lives between calls, so a following call on another
     // stream, which waits on the event, must see the epilogue's store of it and not only the last step
     return batch_dev_end(b, s);
+}
+
+// The full-horizon plan (srbd_plan.hip): one launch over the caller's device arrays on the caller's stream, inside the
+// device steps' event protocol -- the launch reads d_in[e]'s gait fields and the environment records, which the device
+// setters write on their streams, and a plan behind a step on another stream has to follow that step's outputs.
+// Its refusals, before anything is enqueued
+static int batch_plan_check(srbd_batch* b, const srbd_batch_plan_io* io) {
+    srbd_ctx* c = b ? &b->c : nullptr;
+    const std::string fn = "srbd_batch_plan_device";
+    if (!io) return fail(c, SRBD_E_INVALID, fn + ": null io");
+    const batch_req req[] = {{io->states, "states"}, {io->refs, "refs"}, {io->params, "params"}};
+    if (const char* name = batch_first_null(req))
+        return fail(c, SRBD_E_INVALID, fn + ": null required pointer: " + name);
+    if (!io->plan_states && !io->plan_grfs && !io->plan_contacts && !io->plan_run_cost && !io->plan_cost)
+        return fail(c, SRBD_E_INVALID, fn + ": every output is NULL");
+    if (!b) return fail(nullptr, SRBD_E_INVALID, fn + ": null batch");
+    const ModelConst& mc = c->mc;
+    if (mc.ga) {
+        if (!io->freqs)
+            return fail(c, SRBD_E_INVALID,
+                        fn + ": null required pointer: freqs (gait-adaptive sampling is set: the contact sequence "
+                             "comes from each environment's step frequency)");
+    } else {
+        if (!io->contacts) return fail(c, SRBD_E_INVALID, fn + ": null required pointer: contacts");
+        if (io->contact_stride < mc.H)
+            return fail(c, SRBD_E_INVALID, fn + ": contact_stride is smaller than the horizon");
+    }
+    return SRBD_OK;
+}
+
+extern "C" int srbd_batch_plan_device(srbd_batch* b, const srbd_batch_plan_io* io, void* hip_stream) {
+    int rc = batch_plan_check(b, io);
+    if (rc != SRBD_OK) return rc;
+    srbd_ctx* c = &b->c;
+    const ModelConst& mc = c->mc;
+    hipStream_t s;
+    if ((rc = batch_dev_begin(b, hip_stream, &s)) != SRBD_OK) return rc;
+    PlanJob j = {};
+    j.states = io->states, j.refs = io->refs, j.contacts = io->contacts, j.params = io->params, j.freqs = io->freqs;
+    j.plan_states = io->plan_states, j.plan_grfs = io->plan_grfs, j.plan_contacts = io->plan_contacts;
+    j.plan_run_cost = io->plan_run_cost, j.plan_cost = io->plan_cost;
+    j.in_arr = b->d_in;
+    j.envs = b->env_on ? b->d_env : nullptr;
+    memcpy(j.q_feet, c->cfg.q_diag + 12, sizeof(j.q_feet));
+    j.mg = mc.mg;
+    j.contact_stride = io->contact_stride, j.E = b->E, j.hc = plan_chunk(mc.H), j.in_single = 0;
+    const hipError_t le = launch_plan(mc, j, s);
+    if ((rc = batch_dev_end(b, s)) != SRBD_OK) return rc;
+    HIP_TRY(c, le);
+    return SRBD_OK;
+}
+
+// The same arrays in host memory: one device buffer holds the inputs (contacts packed to stride H) and the outputs;
+// upload, the launch on the batch's stream, download, one wait.
+extern "C" int srbd_batch_plan(srbd_batch* b, const float* states, const float* refs, const float* contacts,
+                               int32_t contact_stride, const float* params, const float* freqs, float* plan_states,
+                               float* plan_grfs, float* plan_contacts, float* plan_run_cost, float* plan_cost) {
+    srbd_batch_plan_io io = {states, refs,        contacts,  params,        freqs,         contact_stride, 0,
+                             plan_states, plan_grfs, plan_contacts, plan_run_cost, plan_cost};
+    int rc = batch_plan_check(b, &io);
+    if (rc != SRBD_OK) return rc;
+    srbd_ctx* c = &b->c;
+    const ModelConst& mc = c->mc;
+    const size_t E = (size_t)b->E, H = (size_t)mc.H, P = (size_t)mc.P;
+    HIP_TRY(c, hipSetDevice(c->cfg.device_id));
+    // floats: states | refs | contacts (stride H) | params | freqs | the five outputs
+    // (every array on a 16-byte boundary, so the launch takes its 16-byte stores)
+    auto al = [](size_t x) { return (x + 3) & ~(size_t)3; };
+    const size_t o_st = 0, o_rf = o_st + 24 * E, o_ct = o_rf + 24 * E, o_pr = o_ct + 4 * H * E, o_fq = o_pr + P * E,
+                 o_ps = al(o_fq + E), o_pg = o_ps + 12 * H * E, o_pc = o_pg + 12 * H * E, o_rc = o_pc + 4 * H * E,
+                 o_co = al(o_rc + H * E), total = o_co + E;
+    if (!b->d_plan) {
+        const hipError_t e = hipMalloc((void**)&b->d_plan, sizeof(float) * total);
+        if (e != hipSuccess) {
+            b->d_plan = nullptr;
+            return fail(c, e == hipErrorOutOfMemory ? SRBD_E_NOMEM : SRBD_E_HIP,
+                        std::string("hipMalloc: ") + hipGetErrorString(e));
+        }
+    }
+    float* d = b->d_plan;
+    hipStream_t s = c->stream;
+    if (b->dev_pending && b->dev_stream != s) HIP_TRY(c, hipStreamWaitEvent(s, b->dev_done, 0));  // d_plan's last reader
+    HIP_TRY(c, hipMemcpyAsync(d + o_st, states, sizeof(float) * 24 * E, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(d + o_rf, refs, sizeof(float) * 24 * E, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(d + o_pr, params, sizeof(float) * P * E, hipMemcpyHostToDevice, s));
+    if (mc.ga)
+        HIP_TRY(c, hipMemcpyAsync(d + o_fq, freqs, sizeof(float) * E, hipMemcpyHostToDevice, s));
+    else
+        HIP_TRY(c, hipMemcpy2DAsync(d + o_ct, sizeof(float) * H, contacts, sizeof(float) * (size_t)contact_stride,
+                                    sizeof(float) * H, 4 * E, hipMemcpyHostToDevice, s));
+    srbd_batch_plan_io dio = {d + o_st, d + o_rf, d + o_ct, d + o_pr, d + o_fq, (int32_t)H, 0,
+                              plan_states ? d + o_ps : nullptr, plan_grfs ? d + o_pg : nullptr,
+                              plan_contacts ? d + o_pc : nullptr, plan_run_cost ? d + o_rc : nullptr,
+                              plan_cost ? d + o_co : nullptr};
+    if ((rc = srbd_batch_plan_device(b, &dio, nullptr)) != SRBD_OK) return rc;
+    if (plan_states) HIP_TRY(c, hipMemcpyAsync(plan_states, d + o_ps, sizeof(float) * 12 * H * E, hipMemcpyDeviceToHost, s));
+    if (plan_grfs) HIP_TRY(c, hipMemcpyAsync(plan_grfs, d + o_pg, sizeof(float) * 12 * H * E, hipMemcpyDeviceToHost, s));
+    if (plan_contacts)
+        HIP_TRY(c, hipMemcpyAsync(plan_contacts, d + o_pc, sizeof(float) * 4 * H * E, hipMemcpyDeviceToHost, s));
+    if (plan_run_cost) HIP_TRY(c, hipMemcpyAsync(plan_run_cost, d + o_rc, sizeof(float) * H * E, hipMemcpyDeviceToHost, s));
+    if (plan_cost) HIP_TRY(c, hipMemcpyAsync(plan_cost, d + o_co, sizeof(float) * E, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return SRBD_OK;
 }

@@ -81,6 +81,7 @@ struct srbd_ctx {
     bool ks = false;
     hipGraphExec_t g_dev2 = nullptr, g_dev1 = nullptr;
     float* d_ga_freq = nullptr;  // injected per-row step frequencies (gait-adaptive parity mode), ldn floats
+    float* d_plan = nullptr;     // srbd_plan: its device copies of the caller's arrays, allocated at the first call
     bool input_ready = false;
     // Armed host steps (srbd_set_armed): during a step the next one's copy, rollout and merge are queued
     // behind it, the copy kernel spinning on the host-mapped word h_go; the next srbd_step writes its

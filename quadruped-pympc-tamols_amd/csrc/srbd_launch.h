@@ -215,6 +215,26 @@ void launch_batch_merge(const ModelConst& mc, StepInput* in, const float* recs, 
                         StepOutput* out, uint32_t* eflag, uint32_t* count, uint32_t* flag, uint32_t seq, int E,
                         hipStream_t s, const EnvModel* envs = nullptr);
 
+// The full-horizon plan of one parameter row per environment (srbd_plan.hip; srbd_batch_plan_device, srbd_plan): one
+// thread per environment, PLAN_ENVS of them per block, the block's outputs staged in LDS, hc steps at a time
+// (plan_chunk(H): H itself up to PLAN_CHUNK_MAX, else the horizon in equal chunks), and written with contiguous stores.
+constexpr int PLAN_ENVS = 64;
+constexpr size_t PLAN_LDS_MAX = 140 * 1024;  // dynamic LDS of one block (the CU has 160 KB)
+constexpr int PLAN_CHUNK_MAX = 19;           // 64 environments x (29 hc + 8) floats <= PLAN_LDS_MAX
+struct PlanJob {
+    const float *states, *refs, *contacts, *params, *freqs;  // the caller's device arrays (srbd_batch_plan_io)
+    float *plan_states, *plan_grfs, *plan_contacts, *plan_run_cost, *plan_cost;  // any may be NULL
+    // gait-adaptive sampling: the StepInputs holding the gait fields, one per environment or (in_single) one for all
+    const StepInput* in_arr;
+    const EnvModel* envs;  // srbd_batch_set_env_params: E records, else NULL
+    float q_feet[12];      // q_diag[12..23] and mg of the shared configuration (read when envs == NULL)
+    float mg;
+    int32_t contact_stride, E, hc, in_single;
+};
+int plan_chunk(int H);
+// mc.ga selects the gait-adaptive form (contacts unread, freqs and in_arr read), mc.cost_on the opt-in cost terms
+hipError_t launch_plan(const ModelConst& mc, const PlanJob& j, hipStream_t s);
+
 // TAMOLS (tamols_kernel.hip)
 constexpr int TAMOLS_NQ = 19;       // nearest-neighbour queries per candidate
 constexpr int TAMOLS_MAXCAND = 320;  // rows * cols

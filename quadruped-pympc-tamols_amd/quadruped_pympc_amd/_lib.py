@@ -93,6 +93,31 @@ class BatchDeviceIO(C.Structure):
     ]
 
 
+class BatchPlanIO(C.Structure):
+    """srbd_batch_plan_io (include/srbd_mpc.h): the device arrays of one srbd_batch_plan_device call."""
+    _fields_ = [
+        ("states", _P), ("refs", _P), ("contacts", _P), ("params", _P), ("freqs", _P),
+        ("contact_stride", _I), ("pad", _I),
+        ("plan_states", _P), ("plan_grfs", _P), ("plan_contacts", _P), ("plan_run_cost", _P), ("plan_cost", _P),
+    ]
+
+
+PLAN_OUTPUTS = ("plan_states", "plan_grfs", "plan_contacts", "plan_run_cost", "plan_cost")
+
+
+def plan_shapes(E: int, H: int) -> dict:
+    """The shapes of a plan's arrays (E environments, horizon H), by name."""
+    return {"plan_states": (E, H, 12), "plan_grfs": (E, H, 12), "plan_contacts": (E, 4, H), "plan_run_cost": (E, H),
+            "plan_cost": (E,)}
+
+
+def _plan_want(want):
+    want = tuple(want)
+    if not want or any(w not in PLAN_OUTPUTS for w in want):
+        raise ValueError(f"want must name at least one of {PLAN_OUTPUTS}, got {want}")
+    return want
+
+
 class BatchCemIO(C.Structure):
     """srbd_batch_cem_io (include/srbd_mpc.h): sigma of one srbd_batch_step_cem_device call."""
     _fields_ = [("sigma", _P), ("sigma_reset", _F), ("pad", _I)]
@@ -404,6 +429,9 @@ SIGNATURES.update({
     "srbd_batch_clear_gait": (_I, [_P]),
     "srbd_batch_set_cost_terms": (_I, [_P, _FP, _F, _F]),
     "srbd_batch_step_device": (_I, [_P, C.POINTER(BatchDeviceIO), _P]),
+    "srbd_batch_plan_device": (_I, [_P, C.POINTER(BatchPlanIO), _P]),
+    "srbd_batch_plan": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "srbd_plan": (_I, [_P, _P, _P, _P, _I, _P, _F, _P, _P, _P, _P, _P]),
     "srbd_batch_create_cem": (_I, [C.POINTER(SrbdConfig), _I, C.POINTER(_P)]),
     "srbd_batch_step_cem": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "srbd_batch_step_cem_device": (_I, [_P, C.POINTER(BatchDeviceIO), C.POINTER(BatchCemIO), _P]),
@@ -922,6 +950,29 @@ class Context:
     def clear_gait(self):
         self.check(lib.srbd_clear_gait(self.h), "srbd_clear_gait")
 
+    def plan(self, state, ref, contact, params, freq: float = 0.0, want=PLAN_OUTPUTS) -> dict:
+        """srbd_plan: the full-horizon plan of one parameter row with this context's settings -- state / ref (24,),
+        contact (4, >=H) (None with gait-adaptive sampling, where ``freq`` selects the contact sequence), params (P,).
+        Returns a dict of numpy arrays named as in ``want``: plan_states (H, 12), plan_grfs (H, 12), plan_contacts
+        (4, H), plan_run_cost (H,), plan_cost ().  plan_cost is the cost a step's rollout gives a row with these
+        parameters, bit for bit."""
+        want = _plan_want(want)
+        H = self.cfg.horizon
+        st = np.ascontiguousarray(np.asarray(state, np.float32).reshape(24))
+        rf = np.ascontiguousarray(np.asarray(ref, np.float32).reshape(24))
+        pr = np.ascontiguousarray(np.asarray(params, np.float32).reshape(self.P))
+        ct, stride = None, H
+        if contact is not None:
+            ct = np.ascontiguousarray(contact, dtype=np.float32)
+            if ct.ndim != 2 or ct.shape[0] != 4 or ct.shape[1] < H:
+                raise ValueError(f"contact must be (4, >={H}), got {ct.shape}")
+            stride = int(ct.shape[1])
+        out = {k: np.empty(plan_shapes(1, H)[k][1:], np.float32) for k in want}
+        ptrs = [out[k].ctypes.data if k in out else None for k in PLAN_OUTPUTS]
+        self.check(lib.srbd_plan(self.h, st.ctypes.data, rf.ctypes.data, None if ct is None else ct.ctypes.data, stride,
+                                 pr.ctypes.data, float(freq), *ptrs), "srbd_plan")
+        return out
+
     def set_cost_terms(self, r_force=(0.0, 0.0, 0.0), w_smooth: float = 0.0, w_cone: float = 0.0):
         """srbd_set_cost_terms: opt-in force regularisation / GRF smoothing / cone-violation terms (all 0: the
         reference's cost)."""
@@ -1051,10 +1102,12 @@ class BatchContext:
                 raise ValueError(f"freq_rows must be ({E}, {self.N}), got {fr.shape}")
         self.check(lib.srbd_batch_set_gait(self.h, fptr(t), float(pgg_dt), float(duty), fptr(fs), int(fs.shape[1]),
                                            fptr(fr)), "srbd_batch_set_gait")
+        self._gait = True
 
     def clear_gait(self):
         """srbd_batch_clear_gait: back to the caller's contact sequences (best_freq 0)."""
         self.check(lib.srbd_batch_clear_gait(self.h), "srbd_batch_clear_gait")
+        self._gait = False
 
     def set_gait_device(self, optimize, available, pgg_dt: float, duty: float, *, pgg=None, timings=None,
                         nominal_freqs=None, freq_rows=None, stream=None):
@@ -1076,6 +1129,7 @@ class BatchContext:
         # the null stream by its explicit handle, as in step_device
         self.check(lib.srbd_batch_set_gait_device(self.h, C.byref(io), C.c_void_p(s.cuda_stream or 1)),
                    "srbd_batch_set_gait_device")
+        self._gait = True
 
     def make_gait_io(self, optimize, available, pgg_dt: float, duty: float, *, pgg=None, timings=None,
                      nominal_freqs=None, freq_rows=None) -> BatchGaitIO:
@@ -1311,6 +1365,89 @@ class BatchContext:
         enqueue(io, C.c_void_p(s.cuda_stream or 1))
         return out
 
+    def check_plan_device(self, states, refs, contacts, params, freqs=None):
+        """The argument checks of ``plan_device`` (ValueError; nothing is enqueued); returns the context's device."""
+        import torch
+
+        E, H, P = self.E, self.cfg.horizon, self.P
+        dev = torch.device("cuda", self.cfg.device_id)
+        gait = getattr(self, "_gait", False)
+        if gait and freqs is None:
+            raise ValueError("freqs is required while gait-adaptive sampling is set (the contact sequence comes from "
+                             "each environment's step frequency, e.g. the step's best_freq)")
+        specs = [("states", states, (E, 24)), ("refs", refs, (E, 24)), ("params", params, (E, P))]
+        if not gait or contacts is not None:
+            if not isinstance(contacts, torch.Tensor) or contacts.dim() != 3 or contacts.shape[2] < H:
+                raise ValueError(f"contacts must be a torch tensor of shape ({E}, 4, >={H})")
+            specs.append(("contacts", contacts, (E, 4, int(contacts.shape[2]))))
+        if freqs is not None:
+            specs.append(("freqs", freqs, (E,)))
+        for name, t, shape in specs:
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{name} must be a torch tensor, got {type(t).__name__}")
+            if t.dtype != torch.float32:
+                raise ValueError(f"{name} must be torch.float32, got {t.dtype}")
+            if tuple(t.shape) != shape:
+                raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
+            if not t.is_contiguous():
+                raise ValueError(f"{name} must be contiguous")
+        for name, t, _ in specs:
+            if t.device != dev:
+                raise ValueError(f"{name} must be on {dev}, got {t.device}")
+        return dev
+
+    def plan_device(self, states, refs, contacts, params, freqs=None, *, want=PLAN_OUTPUTS, stream=None) -> dict:
+        """srbd_batch_plan_device: the full-horizon plan of ``params[e]`` for every environment, one launch enqueued on
+        ``stream`` (None: ``torch.cuda.current_stream()``) without a host synchronisation.  states / refs (E, 24) the
+        prepared rows the step took, contacts (E, 4, >=H) (may be None with gait-adaptive sampling), params (E, P) any
+        parameter rows -- the step's updated ``best`` for the plan behind its outputs -- and, with gait-adaptive
+        sampling, freqs (E,) the step frequencies (the step's ``best_freq``); float32 tensors of the context's device,
+        contiguous.  Returns a dict of the tensors named in ``want``: plan_states (E, H, 12), plan_grfs (E, H, 12),
+        plan_contacts (E, 4, H), plan_run_cost (E, H), plan_cost (E,).  They are allocated once per ``want`` and
+        reused by the next call: copy what has to outlive it.  Ready in stream order, as ``step_device``'s outputs."""
+        import torch
+
+        want = _plan_want(want)
+        dev = self.check_plan_device(states, refs, contacts, params, freqs)
+        s = torch.cuda.current_stream(dev) if stream is None else stream
+        cache = self.__dict__.setdefault("_plan_out", {})
+        out = cache.get(want)
+        if out is None:
+            shapes = plan_shapes(self.E, self.cfg.horizon)
+            out = cache[want] = {k: torch.empty(shapes[k], dtype=torch.float32, device=dev) for k in want}
+        io = BatchPlanIO(states=states.data_ptr(), refs=refs.data_ptr(),
+                         contacts=None if contacts is None else contacts.data_ptr(), params=params.data_ptr(),
+                         freqs=None if freqs is None else freqs.data_ptr(),
+                         contact_stride=self.cfg.horizon if contacts is None else int(contacts.shape[2]), pad=0,
+                         **{k: out[k].data_ptr() for k in want})
+        # the null stream by its explicit handle, as in step_device
+        self.check(lib.srbd_batch_plan_device(self.h, C.byref(io), C.c_void_p(s.cuda_stream or 1)),
+                   "srbd_batch_plan_device")
+        return out
+
+    def plan(self, states, refs, contacts, params, freqs=None, want=PLAN_OUTPUTS) -> dict:
+        """srbd_batch_plan: ``plan_device`` on numpy arrays (upload, the launch, one wait, download); returns a dict
+        of fresh numpy arrays holding the device form's bytes."""
+        want = _plan_want(want)
+        E, H, P = self.E, self.cfg.horizon, self.P
+        st = np.ascontiguousarray(np.asarray(states, np.float32).reshape(E, 24))
+        rf = np.ascontiguousarray(np.asarray(refs, np.float32).reshape(E, 24))
+        pr = np.ascontiguousarray(np.asarray(params, np.float32).reshape(E, P))
+        ct, stride = None, H
+        if contacts is not None:
+            ct = np.ascontiguousarray(contacts, dtype=np.float32)
+            if ct.ndim != 3 or ct.shape[:2] != (E, 4) or ct.shape[2] < H:
+                raise ValueError(f"contacts must be ({E}, 4, >={H}), got {ct.shape}")
+            stride = int(ct.shape[2])
+        fq = None if freqs is None else np.ascontiguousarray(np.asarray(freqs, np.float32).reshape(E))
+        shapes = plan_shapes(E, H)
+        out = {k: np.empty(shapes[k], np.float32) for k in want}
+        ptrs = [out[k].ctypes.data if k in out else None for k in PLAN_OUTPUTS]
+        self.check(lib.srbd_batch_plan(self.h, st.ctypes.data, rf.ctypes.data, None if ct is None else ct.ctypes.data,
+                                       stride, pr.ctypes.data, None if fq is None else fq.ctypes.data, *ptrs),
+                   "srbd_batch_plan")
+        return out
+
     def interface_step_device(self, state_in, ref_in, contacts, keys, previous_contact, best, *, iterations: int = 1,
                               sigma=None, sigma_reset: float = 0.0, gait_io=None, want_costs=False, stream=None):
         """srbd_batch_interface_step_device: ``SRBDControllerInterface.compute_control``'s sampling branch for every
@@ -1374,6 +1511,8 @@ class BatchContext:
         # the null stream by its explicit handle, as in step_device
         self.check(lib.srbd_batch_interface_step_device(self.h, C.byref(io), C.c_void_p(s.cuda_stream or 1)),
                    "srbd_batch_interface_step_device")
+        if gait_io is not None:
+            self._gait = True
         return out
 
 

@@ -233,6 +233,14 @@ class Sampling_MPC:
                 self._ctx.set_rng(self.rng)
         return self._ctx
 
+    def compute_plan(self, state, reference, contact_sequence, best_control_parameters, step_frequency=0.0,
+                     want=_lib.PLAN_OUTPUTS):
+        """The full-horizon plan of one parameter row (``srbd_plan``): the prepared state and reference (24,) a step
+        takes, the contact sequence (4, >=H) and the parameters (P,) -> dict of plan_states, plan_grfs (H, 12),
+        plan_contacts (4, H), plan_run_cost (H,) and plan_cost, as ``Context.plan`` returns them."""
+        return self.context.plan(state, reference, contact_sequence, best_control_parameters, freq=step_frequency,
+                                 want=want)
+
     def _key_args(self, key):
         """(seed, counter) of srbd_step for a compute call's `key`."""
         if self.rng == "philox":

@@ -204,8 +204,28 @@ class Batched_Sampling_MPC:
             freq = (out["best_freq"] if self._device_step_frequencies_from_result
                     else torch.full((E,), 1.4, dtype=torch.float64, device=dev))
         self.last_device_result = out
+        self._device_best = best_control_parameters  # compute_plan_device's default row
         return (out["grf"], footholds, out["predicted_state"], best_control_parameters, out["best_cost"], freq,
                 LazyBatchCosts(ctx, self._calls, self))
+
+    def compute_plan_device(self, state, ref, contacts, best=None, freqs=None, *, want=_lib.PLAN_OUTPUTS,
+                            stream=None):
+        """The full-horizon plan of one parameter row per environment (``BatchContext.plan_device``): state, ref
+        (E, 24) the prepared rows a step takes, contacts (E, 4, >=H), best (E, P) -- None: the controller's current
+        best parameters, the tensor the last ``compute_control_device`` updated, else the host attribute uploaded --
+        and freqs (E,) with gait-adaptive sampling (None: the last device step's ``best_freq``).  Returns the dict of
+        ``plan_device``: plan_states, plan_grfs (E, H, 12), plan_contacts (E, 4, H), plan_run_cost (E, H), plan_cost
+        (E,), ready in the stream's order."""
+        import torch
+
+        if best is None:
+            best = getattr(self, "_device_best", None)
+            if best is None:
+                best = torch.from_numpy(np.ascontiguousarray(self.best_control_parameters, dtype=f32)).to(state.device)
+        last = getattr(self, "last_device_result", None)
+        if freqs is None and self._device_step_frequencies_from_result and last is not None:
+            freqs = last["best_freq"]
+        return self.context.plan_device(state, ref, contacts, best, freqs, want=want, stream=stream)
 
     def prepare_state_and_reference(self, states_current, reference_states, current_contacts, previous_contacts,
                                     mpc_frequency=100):

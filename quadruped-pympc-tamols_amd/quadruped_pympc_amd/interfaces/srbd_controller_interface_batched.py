@@ -123,8 +123,23 @@ class Batched_SRBDControllerInterface:
             else:
                 freq = torch.full((E,), 1.65 if self._cem else 1.4, dtype=torch.float64, device=dev)
         self.last_device_result = out
+        self._plan_contacts = contact_sequences  # a reference, not a copy: compute_plan_device reads it
         return (out["grf"], out["footholds"], out["predicted_state"], freq, out["best_cost"],
                 LazyBatchCosts(ctx, c._calls, c))
+
+    def compute_plan_device(self, *, want=_lib.PLAN_OUTPUTS, stream=None):
+        """The full-horizon plan of the last ``compute_control_device`` call (``BatchContext.plan_device``): the
+        updated best parameters rolled out from that call's prepared state and reference rows, with its contact rows
+        and, gait-adaptive, its ``best_freq``.  The interface holds references to those tensors and copies nothing,
+        so call it before they are overwritten.  Enqueued on ``stream`` (None: torch's current stream).  Returns the
+        dict of ``plan_device``.  RuntimeError before the first step."""
+        out = self.last_device_result
+        if out is None:
+            raise RuntimeError("compute_plan_device: no compute_control_device call yet")
+        return self.controller.context.plan_device(out["states"], out["refs"], self._plan_contacts,
+                                                   self.best_control_parameters,
+                                                   out["best_freq"] if self._gait_adaptive else None, want=want,
+                                                   stream=stream)
 
     def reset(self, mask=None):
         """``previous_contact_mpc`` back to ones (WBInterface.reset's ``current_contact = [1, 1, 1, 1]``) for every
