@@ -1252,6 +1252,56 @@ typedef struct srbd_batch_interface_io {
     float* best_freq; int32_t* status; float* costs;   /* the last iteration's, as srbd_batch_device_io; costs may be NULL */
 } srbd_batch_interface_io;
 int srbd_batch_interface_step_device(srbd_batch* b, const srbd_batch_interface_io* io, void* hip_stream);
+
+/* ---- The due mask: the three device steps for the environments whose MPC is due, and no others.  The reference does
+ * not solve on every simulation step: QuadrupedPyMPC_Wrapper.compute_actions (quadruped_pympc_wrapper.py
+ * :134) runs compute_control when step_num % round(1 / (mpc_frequency * simulation_dt)) == 0 -- a 100 Hz MPC in a
+ * 500 Hz loop solves every 5th step -- and between solves holds the last GRFs, footholds, best step frequency and
+ * predicted state.  step_num is the environment's own counter and restarts with its episode, so after per-environment
+ * resets (srbd_loop_reset_device) the environments of a batch are due on different steps.
+ *   srbd_batch_step_masked_device, srbd_batch_step_cem_masked_device and srbd_batch_interface_step_masked_device are
+ *   srbd_batch_step_device, srbd_batch_step_cem_device and srbd_batch_interface_step_device with `due`: E int32 words
+ *   in device memory of the batch's device, read in stream order; non-zero: step this environment.
+ *   Launches: the launches of the unmasked call, on the same grids, each with the mask -- the interface prologue
+ *   (prepare_state and the key schedule), the gait setter, pack, the draws or the transpose, the rollouts (every
+ *   instantiation, the per-environment-parameter and CEM ones included), the merges, unpack and the interface
+ *   epilogue.  The environment is uniform over a block (over a lane in the prologue and the epilogue), so a block of
+ *   an environment that is not due loads due[e] and returns before any other global access: its draws and rollouts do
+ *   not run.  Nothing is compacted and the due count never reaches the host.  The kernels are the unmasked calls'
+ *   (one body each, the mask a trailing argument that those calls pass as NULL).
+ *   Arrival count: the merge blocks count themselves up to E before the last one resets the counter and stores the
+ *   step's sequence word.  A block that is not due skips its merge and still takes part in the arrival count, so
+ *   behind a masked call -- with no environment due as well -- the counter is zero and the word stored, and the next
+ *   step of any kind (host srbd_batch_step included, which waits on that word) finds them as it expects.  No other
+ *   counter or word on the path is shared between blocks: the rollouts of a batch write leaf records only, and the
+ *   merge's own publish word per environment is written by its block and never read.
+ *   Equivalence, an environment with due[e] != 0: every in / out and output array holds exactly the bytes the
+ *   unmasked call leaves for that environment, for every batch kind and setting the unmasked call accepts (MPPI,
+ *   random sampling, CEM; the three parametrizations; io->gait; the cost terms; per-environment parameters; the three
+ *   key streams; 1..SRBD_MAX_IFACE_ITERS iterations).  Environments are independent, so the mask of the others does
+ *   not matter.
+ *   An environment with due[e] == 0 is neither written nor read: the caller's rows keys[e], previous_contact[e],
+ *   best_params[e], sigma[e], states[e], refs[e], grf[e], footholds[e], grf_raw[e], predicted_state[e], best_cost[e],
+ *   best_index[e], best_freq[e], status[e] and costs[e] keep their bytes, and so does the batch's own state of it that
+ *   outlives a call -- its step input with the gait fields, its injected-frequency rows and its costs row
+ *   (srbd_batch_copy_costs returns the costs of its last solve).  Its key does not advance, CEM's sigma_reset is not
+ *   applied to it, previous_contact[e] keeps the contact of its last solve (the reference's previous_contact_mpc
+ *   between solves), and none of its inputs is read: NaNs in them change nothing anywhere.  Holding the last solve is
+ *   therefore handing the same output arrays to every call.
+ *   Contracts: the enqueue contract, the stream handles, the event protocol, "no synchronising HIP call, no host
+ *   touch of device memory" and every refusal (made before anything is enqueued) are the unmasked call's.  Added:
+ *   due == NULL is SRBD_E_INVALID with a message that names the unmasked call; io and due are looked at before b, so
+ *   either is named whatever b is.
+ *   Out of scope: a masked host srbd_batch_step; the single context; compacting the due environments into a smaller
+ *   grid; graph capture; a device-side step counter (step_num is the simulator's; the mask is one comparison on it);
+ *   and every refusal the unmasked calls make stays (gait-adaptive sampling with the cost terms, gait-adaptive CEM,
+ *   shift_solution).  srbd_batch_set_gait_device itself takes no mask: inside the masked interface step the gait
+ *   setting is masked with the rest. */
+int srbd_batch_step_masked_device(srbd_batch* b, const srbd_batch_device_io* io, const int32_t* due, void* hip_stream);
+int srbd_batch_step_cem_masked_device(srbd_batch* b, const srbd_batch_device_io* io, const srbd_batch_cem_io* cem,
+                                      const int32_t* due, void* hip_stream);
+int srbd_batch_interface_step_masked_device(srbd_batch* b, const srbd_batch_interface_io* io, const int32_t* due,
+                                            void* hip_stream);
 int srbd_selftest_interface_keys(uint64_t* keys_io, int32_t n, int32_t rng, int32_t iterations, uint64_t* step_keys);
 
 /* ---- Restarting single environments of the batched loop, device-resident: the episode's end of the reference's

@@ -371,7 +371,9 @@ static int batch_gait_dev_check(srbd_batch* b, const srbd_batch_gait_io* io) {
     return batch_gait_refuse(b, io->n_freq, false);
 }
 
-extern "C" int srbd_batch_set_gait_device(srbd_batch* b, const srbd_batch_gait_io* io, void* hip_stream) {
+// due: NULL, or the due mask of srbd_batch_interface_step_masked_device -- the gait fields of d_in[e] and d_ga_freq's
+// slice of an environment that is not due keep what its last solve set
+static int batch_set_gait_dev(srbd_batch* b, const srbd_batch_gait_io* io, const int32_t* due, void* hip_stream) {
     int rc = batch_gait_dev_check(b, io);
     if (rc != SRBD_OK) return rc;
     ModelConst& mc = b->c.mc;
@@ -384,11 +386,15 @@ extern "C" int srbd_batch_set_gait_device(srbd_batch* b, const srbd_batch_gait_i
     j.random_sampling = mc.method == SRBD_RANDOM_SAMPLING;
     j.N = mc.n_local;
     j.ldn = mc.ldn;
-    launch_batch_set_gait(j, b->d_in, b->d_ga_freq, b->E, s);
+    launch_batch_set_gait(j, b->d_in, b->d_ga_freq, b->E, s, due);
     if ((rc = batch_dev_end(b, s)) != SRBD_OK) return rc;
     mc.ga = 1;
     b->ga_staging_stale = true;
     return SRBD_OK;
+}
+
+extern "C" int srbd_batch_set_gait_device(srbd_batch* b, const srbd_batch_gait_io* io, void* hip_stream) {
+    return batch_set_gait_dev(b, io, nullptr, hip_stream);
 }
 
 extern "C" int srbd_batch_clear_gait(srbd_batch* b) {
@@ -621,11 +627,17 @@ extern "C" int srbd_batch_step_cem(srbd_batch* b, const float* states, const flo
 // srbd_batch_step_device (cem NULL, is_cem false) and srbd_batch_step_cem_device: batch_pack_cem_kernel also writes
 // d_in[e].sigma (the caller's rows or the reset constant) and batch_unpack_cem_kernel also scatters d_out[e].sigma.
 // Its refusals, which srbd_batch_interface_step_device makes too before it enqueues anything
+// The entry point's name in the messages: the masked forms (srbd_batch_step_masked_device, _step_cem_masked_device) or
+// the unmasked ones
+static const char* batch_step_dev_name(bool is_cem, bool masked) {
+    if (masked) return is_cem ? "srbd_batch_step_cem_masked_device" : "srbd_batch_step_masked_device";
+    return is_cem ? "srbd_batch_step_cem_device" : "srbd_batch_step_device";
+}
 static int batch_step_dev_check(srbd_batch* b, const srbd_batch_device_io* io, const srbd_batch_cem_io* cem,
-                                bool is_cem) {
+                                bool is_cem, bool masked = false) {
     // the arguments first, so a bad io is named as such whatever b is (b == NULL: the calling thread's error text)
     srbd_ctx* c = b ? &b->c : nullptr;
-    const std::string fn = is_cem ? "srbd_batch_step_cem_device" : "srbd_batch_step_device";
+    const std::string fn = batch_step_dev_name(is_cem, masked);
     if (!io) return fail(c, SRBD_E_INVALID, fn + ": null io");
     if (is_cem) {
         if (!cem) return fail(c, SRBD_E_INVALID, fn + ": null cem");
@@ -644,7 +656,8 @@ static int batch_step_dev_check(srbd_batch* b, const srbd_batch_device_io* io, c
     if (!b) return fail(nullptr, SRBD_E_INVALID, fn + ": null batch");
     const ModelConst& mc = c->mc;
     if (!is_cem && mc.method == SRBD_CEM_MPPI)
-        return fail(c, SRBD_E_INVALID, "CEM: sigma is part of the step (srbd_batch_step_cem_device)");
+        return fail(c, SRBD_E_INVALID,
+                    std::string("CEM: sigma is part of the step (") + batch_step_dev_name(true, masked) + ")");
     if (is_cem && mc.method != SRBD_CEM_MPPI)
         return fail(c, SRBD_E_INVALID, fn + ": not a CEM batch (srbd_batch_create_cem)");
     if (io->contact_stride < mc.H)
@@ -652,9 +665,13 @@ static int batch_step_dev_check(srbd_batch* b, const srbd_batch_device_io* io, c
     return SRBD_OK;
 }
 
+// due: NULL (the unmasked entry points: the launches they always made, the kernels' mask argument NULL), or the due
+// mask of the masked ones, handed to every launch -- the same grids, and the blocks of an environment that is not due
+// return at once.  The merge blocks count themselves whatever the mask holds, so d_count is zero and `seq` stored
+// behind every call: the next step, host or device, masked or not, finds the counter and the word as it expects them.
 static int batch_step_dev(srbd_batch* b, const srbd_batch_device_io* io, const srbd_batch_cem_io* cem, bool is_cem,
-                          void* hip_stream) {
-    int rc = batch_step_dev_check(b, io, cem, is_cem);
+                          void* hip_stream, const int32_t* due = nullptr, bool masked = false) {
+    int rc = batch_step_dev_check(b, io, cem, is_cem, masked);
     if (rc != SRBD_OK) return rc;
     srbd_ctx* c = &b->c;
     const ModelConst& mc = c->mc;
@@ -662,20 +679,20 @@ static int batch_step_dev(srbd_batch* b, const srbd_batch_device_io* io, const s
     if ((rc = batch_dev_begin(b, hip_stream, &s)) != SRBD_OK) return rc;
     const int E = b->E;
     const EnvModel* envs = b->env_on ? b->d_env : nullptr;
-    launch_batch_pack(mc, c->cfg.q_diag + 12, *io, b->d_in, E, s, is_cem ? cem : nullptr, envs);
+    launch_batch_pack(mc, c->cfg.q_diag + 12, *io, b->d_in, E, s, is_cem ? cem : nullptr, envs, due);
     if (io->noise)
-        launch_batch_transpose(mc, io->noise, b->d_noise, E, s);
+        launch_batch_transpose(mc, io->noise, b->d_noise, E, s, due);
     else
-        launch_batch_rng(mc, b->d_in, b->d_noise, E, s);
+        launch_batch_rng(mc, b->d_in, b->d_noise, E, s, due);
     if (mc.ga)
         launch_batch_rollout_ga(mc, b->d_in, b->d_noise, b->d_costs, b->d_rec, c->wrec_stride, b->d_ga_freq, E, s,
-                                envs);
+                                envs, due);
     else
-        launch_batch_rollout(mc, b->d_in, b->d_noise, b->d_costs, b->d_rec, c->wrec_stride, E, s, envs);
+        launch_batch_rollout(mc, b->d_in, b->d_noise, b->d_costs, b->d_rec, c->wrec_stride, E, s, envs, due);
     const uint32_t seq = ++c->seq;
     launch_batch_merge(mc, b->d_in, b->d_rec, c->wrec_stride, b->d_noise, b->d_out, b->d_eflag, b->d_count, c->d_flag,
-                       seq, E, s, envs);
-    launch_batch_unpack(mc, *io, b->d_out, b->d_costs, E, s, is_cem ? cem->sigma : nullptr);
+                       seq, E, s, envs, due);
+    launch_batch_unpack(mc, *io, b->d_out, b->d_costs, E, s, is_cem ? cem->sigma : nullptr, due);
     if ((rc = batch_dev_end(b, s)) != SRBD_OK) return rc;
     b->stepped = true;
     return SRBD_OK;
@@ -690,6 +707,29 @@ extern "C" int srbd_batch_step_cem_device(srbd_batch* b, const srbd_batch_device
     return batch_step_dev(b, io, cem, true, hip_stream);
 }
 
+// The masked steps (SCI:134 of the reference's wrapper: the solve runs only on the steps that are due).  io and due
+// are looked at first, so either is named whatever b is; the rest is the unmasked step's.
+static int batch_step_masked(srbd_batch* b, const srbd_batch_device_io* io, const srbd_batch_cem_io* cem, bool is_cem,
+                             const int32_t* due, void* hip_stream) {
+    srbd_ctx* c = b ? &b->c : nullptr;
+    const std::string fn = batch_step_dev_name(is_cem, true);
+    if (!io) return fail(c, SRBD_E_INVALID, fn + ": null io");
+    if (!due)
+        return fail(c, SRBD_E_INVALID,
+                    fn + ": null due (to step every environment call " + batch_step_dev_name(is_cem, false) + ")");
+    return batch_step_dev(b, io, cem, is_cem, hip_stream, due, true);
+}
+
+extern "C" int srbd_batch_step_masked_device(srbd_batch* b, const srbd_batch_device_io* io, const int32_t* due,
+                                             void* hip_stream) {
+    return batch_step_masked(b, io, nullptr, false, due, hip_stream);
+}
+
+extern "C" int srbd_batch_step_cem_masked_device(srbd_batch* b, const srbd_batch_device_io* io,
+                                                 const srbd_batch_cem_io* cem, const int32_t* due, void* hip_stream) {
+    return batch_step_masked(b, io, cem, true, due, hip_stream);
+}
+
 // SRBDControllerInterface.compute_control's sampling branch (srbd_controller_interface.py:113-180, :225-229) for every
 // environment of a batch, enqueued on the caller's stream: srbd_interface_step (srbd_host.cpp) statement for statement.
 // The prologue launch is its prepare_state and its with_newkey of every iteration (the step keys go to d_iface_keys,
@@ -700,9 +740,12 @@ extern "C" int srbd_batch_step_cem_device(srbd_batch* b, const srbd_batch_device
 // event protocol of the steps already orders against a call on another stream; the prologue joins it here, and the
 // event is recorded once more behind the epilogue, so a call on another stream also follows the epilogue's store of
 // previous_contact, the one caller-owned array that is state between calls.
-extern "C" int srbd_batch_interface_step_device(srbd_batch* b, const srbd_batch_interface_io* io, void* hip_stream) {
+// due: NULL (srbd_batch_interface_step_device), or the due mask of srbd_batch_interface_step_masked_device, handed to
+// the prologue, the gait setter, every iteration's step and the epilogue.
+static int batch_iface_step(srbd_batch* b, const srbd_batch_interface_io* io, const int32_t* due, void* hip_stream) {
     srbd_ctx* c = b ? &b->c : nullptr;
-    const std::string fn = "srbd_batch_interface_step_device";
+    const bool masked = due != nullptr;
+    const std::string fn = masked ? "srbd_batch_interface_step_masked_device" : "srbd_batch_interface_step_device";
     if (!b) return fail(nullptr, SRBD_E_INVALID, fn + ": null batch");
     if (!io) return fail(c, SRBD_E_INVALID, fn + ": null io");
     const ModelConst& mc = c->mc;
@@ -744,24 +787,40 @@ extern "C" int srbd_batch_interface_step_device(srbd_batch* b, const srbd_batch_
     sio.grf = io->grf_raw, sio.predicted_state = io->predicted_state, sio.best_cost = io->best_cost;
     sio.best_index = io->best_index, sio.best_freq = io->best_freq, sio.status = io->status, sio.costs = io->costs;
     srbd_batch_cem_io cem = {io->sigma, io->sigma_reset, 0};
-    if ((rc = batch_step_dev_check(b, &sio, is_cem ? &cem : nullptr, is_cem)) != SRBD_OK) return rc;
+    if ((rc = batch_step_dev_check(b, &sio, is_cem ? &cem : nullptr, is_cem, masked)) != SRBD_OK) return rc;
     hipStream_t s;
     if ((rc = batch_dev_begin(b, hip_stream, &s)) != SRBD_OK) return rc;  // d_iface_keys
-    launch_iface_prologue(*io, mc.rng, mc.P, b->d_iface_keys, b->E, s);
+    launch_iface_prologue(*io, mc.rng, mc.P, b->d_iface_keys, b->E, s, due);
     HIP_TRY(c, hipGetLastError());  // the steps below record the event behind their launches
     // the explicit handle again for the calls below: NULL would mean the batch's own stream to them
     void* const hs = s ? (void*)s : (void*)hipStreamLegacy;
-    if (io->gait && (rc = srbd_batch_set_gait_device(b, io->gait, hs)) != SRBD_OK) return rc;
+    if (io->gait && (rc = batch_set_gait_dev(b, io->gait, due, hs)) != SRBD_OK) return rc;
     for (int it = 0; it < io->iterations; ++it) {
         sio.seeds = b->d_iface_keys + 2 * (size_t)it * b->E;
         sio.counters = sio.seeds + b->E;
         cem.sigma_reset = it == 0 ? io->sigma_reset : 0.0f;
-        if ((rc = batch_step_dev(b, &sio, is_cem ? &cem : nullptr, is_cem, hs)) != SRBD_OK) return rc;
+        if ((rc = batch_step_dev(b, &sio, is_cem ? &cem : nullptr, is_cem, hs, due, masked)) != SRBD_OK) return rc;
     }
-    launch_iface_epilogue(*io, b->E, s);
+    launch_iface_epilogue(*io, b->E, s, due);
     // the event again, behind the epilogue: previous_contact lives between calls, so a following call on another
     // stream, which waits on the event, must see the epilogue's store of it and not only the last step
     return batch_dev_end(b, s);
+}
+
+extern "C" int srbd_batch_interface_step_device(srbd_batch* b, const srbd_batch_interface_io* io, void* hip_stream) {
+    return batch_iface_step(b, io, nullptr, hip_stream);
+}
+
+// io and due are looked at first, so either is named whatever b is
+extern "C" int srbd_batch_interface_step_masked_device(srbd_batch* b, const srbd_batch_interface_io* io,
+                                                       const int32_t* due, void* hip_stream) {
+    srbd_ctx* c = b ? &b->c : nullptr;
+    const std::string fn = "srbd_batch_interface_step_masked_device";
+    if (!io) return fail(c, SRBD_E_INVALID, fn + ": null io");
+    if (!due)
+        return fail(c, SRBD_E_INVALID,
+                    fn + ": null due (to step every environment call srbd_batch_interface_step_device)");
+    return batch_iface_step(b, io, due, hip_stream);
 }
 
 // The full-horizon plan (srbd_plan.hip): one launch over the caller's device arrays on the caller's stream, inside the

@@ -22,6 +22,11 @@
 // The device form of srbd_batch_set_gait (srbd_batch_set_gait_device):
 //   batch_set_gait_kernel   the gait fields of in[e] from the caller's device arrays, as fill_gait (srbd_api.hip)
 //                           writes them on the host, and the injected frequency rows into the batch's array
+// The due mask (srbd_batch_step_masked_device and its CEM and interface forms): every kernel of the device step takes
+// a trailing `due`, E words of the caller's device memory or NULL.  The environment is block-uniform in all of them,
+// so a block of an environment with due[e] == 0 reads that one word and returns before any other global access
+// (not_due); batch_merge_kernel's block skips merge_body and still counts itself.  NULL -- every launch of the
+// unmasked entry points and of the host step -- is a uniform branch on a kernel argument: the same instantiations.
 #include <algorithm>
 
 #include "srbd_device.h"
@@ -30,6 +35,9 @@
 #include "srbd_quad.h"
 
 namespace srbd {
+
+// The due mask: this block's environment is skipped.  One scalar load of due[env], none when the launch has no mask.
+__device__ __forceinline__ bool not_due(const int32_t* __restrict__ due, int env) { return due && due[env] == 0; }
 
 __global__ void __launch_bounds__(256) batch_copy_kernel(const uint4* __restrict__ src, uint4* __restrict__ dst,
                                                          int nwords, int stride_words) {
@@ -119,19 +127,25 @@ __device__ __forceinline__ void batch_pack_body(const srbd_batch_device_io& io, 
     }
 }
 __global__ void __launch_bounds__(64) batch_pack_kernel(const srbd_batch_device_io io, const BatchPackConst pc, int vec,
-                                                        StepInput* __restrict__ in_arr) {
+                                                        StepInput* __restrict__ in_arr,
+                                                        const int32_t* __restrict__ due) {
+    if (not_due(due, blockIdx.x)) return;
     batch_pack_body<false, false>(io, pc.H, pc.P, pc, vec, in_arr, srbd_batch_cem_io{nullptr, 0.0f, 0}, 0);
 }
 __global__ void __launch_bounds__(64) batch_pack_cem_kernel(const srbd_batch_device_io io, const BatchPackConst pc,
                                                             int vec, StepInput* __restrict__ in_arr,
-                                                            const srbd_batch_cem_io cem, int svec) {
+                                                            const srbd_batch_cem_io cem, int svec,
+                                                            const int32_t* __restrict__ due) {
+    if (not_due(due, blockIdx.x)) return;
     batch_pack_body<true, false>(io, pc.H, pc.P, pc, vec, in_arr, cem, svec);
 }
 template <bool CEM>
 __global__ void __launch_bounds__(64) batch_pack_env_kernel(const srbd_batch_device_io io, int H, int P, int vec,
                                                             StepInput* __restrict__ in_arr,
                                                             const EnvModel* __restrict__ envs,
-                                                            const srbd_batch_cem_io cem, int svec) {
+                                                            const srbd_batch_cem_io cem, int svec,
+                                                            const int32_t* __restrict__ due) {
+    if (not_due(due, blockIdx.x)) return;
     batch_pack_body<CEM, true>(io, H, P, envs[(int)blockIdx.x], vec, in_arr, cem, svec);
 }
 
@@ -209,14 +223,16 @@ __device__ __forceinline__ void batch_unpack_body(const srbd_batch_device_io& io
 __global__ void __launch_bounds__(256) batch_unpack_kernel(const srbd_batch_device_io io,
                                                            const StepOutput* __restrict__ out_arr,
                                                            const float* __restrict__ costs_arr, int P, int N, int ldn,
-                                                           int vec) {
+                                                           int vec, const int32_t* __restrict__ due) {
+    if (not_due(due, blockIdx.x)) return;
     batch_unpack_body<false>(io, out_arr, costs_arr, P, N, ldn, vec, nullptr, 0);
 }
 __global__ void __launch_bounds__(256) batch_unpack_cem_kernel(const srbd_batch_device_io io,
                                                                const StepOutput* __restrict__ out_arr,
                                                                const float* __restrict__ costs_arr, int P, int N,
                                                                int ldn, int vec, float* __restrict__ sigma,
-                                                               int svec) {
+                                                               int svec, const int32_t* __restrict__ due) {
+    if (not_due(due, blockIdx.x)) return;
     batch_unpack_body<true>(io, out_arr, costs_arr, P, N, ldn, vec, sigma, svec);
 }
 
@@ -225,8 +241,10 @@ __global__ void __launch_bounds__(256) batch_unpack_cem_kernel(const srbd_batch_
 // are the host path's bytes; nothing else of in[e] is written.  With injected frequencies every thread copies rows
 // k = tid, tid + blockDim.x, ... < N of freq_rows[e] to ga_freq[e ldn + k]; the padding rows N .. ldn stay zero.
 __global__ void __launch_bounds__(256) batch_set_gait_kernel(const BatchGaitJob j, StepInput* __restrict__ in_arr,
-                                                             float* __restrict__ ga_freq) {
+                                                             float* __restrict__ ga_freq,
+                                                             const int32_t* __restrict__ due) {
     const int e = blockIdx.x, tid = threadIdx.x;
+    if (not_due(due, e)) return;
     if (tid == 0) {
         float timing[4], set[SRBD_MAX_FREQS];
 #pragma unroll
@@ -243,15 +261,19 @@ __global__ void __launch_bounds__(256) batch_set_gait_kernel(const BatchGaitJob 
 }
 
 __global__ void __launch_bounds__(256) batch_rng_kernel(const ModelConst mc, const StepInput* __restrict__ in,
-                                                        float* __restrict__ noise) {
+                                                        float* __restrict__ noise,
+                                                        const int32_t* __restrict__ due) {
     const int e = blockIdx.y;
+    if (not_due(due, e)) return;
     const RngJob job{noise + (size_t)e * mc.P * mc.ldn, 0, 0, 1, 0, nullptr};  // keyed by in[e] (dev_ctr)
     rng_items(mc, in + e, job, blockIdx.x * 256 + threadIdx.x, gridDim.x * 256);
 }
 
 // transpose_kernel with one matrix per environment on blockIdx.z
 __global__ void __launch_bounds__(256) batch_transpose_kernel(const float* __restrict__ src, int n, int P, int ldn,
-                                                              float* __restrict__ dst) {
+                                                              float* __restrict__ dst,
+                                                              const int32_t* __restrict__ due) {
+    if (not_due(due, blockIdx.z)) return;
     transpose_tile(src + (size_t)blockIdx.z * n * P, n, P, ldn, dst + (size_t)blockIdx.z * P * ldn, blockIdx.x * 32,
                    blockIdx.y * 32);
 }
@@ -279,8 +301,9 @@ template <int KIND, int HT, int ST, bool CEMT, bool EXT, bool ENVT>  // rollout_
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) batch_rollout_kernel(
     const ModelConst mc, const StepInput* __restrict__ in_arr, const float* __restrict__ noise_arr,
     float* __restrict__ costs_arr, float* __restrict__ recs_arr, int rec_stride,
-    const EnvModel* __restrict__ envs) {
+    const EnvModel* __restrict__ envs, const int32_t* __restrict__ due) {
     const int env = blockIdx.y;
+    if (not_due(due, env)) return;  // no draws read, no costs, no leaf record
     const auto kc = model_view<ENVT>(mc, envs, env);
     const StepInput* __restrict__ in = in_arr + env;
     const float* __restrict__ noise = noise_arr + (size_t)env * mc.P * mc.ldn;
@@ -584,8 +607,10 @@ __global__ void __launch_bounds__(512) batch_rollout_ga_kernel(const ModelConst 
                                                                float* __restrict__ costs_arr,
                                                                float* __restrict__ recs_arr, int rec_stride,
                                                                const float* __restrict__ ga_freq_arr,
-                                                               const EnvModel* __restrict__ envs) {
+                                                               const EnvModel* __restrict__ envs,
+                                                               const int32_t* __restrict__ due) {
     const int env = blockIdx.y;
+    if (not_due(due, env)) return;
     const auto kc = model_view<ENVT>(mc, envs, env);
     const StepInput* __restrict__ in = in_arr + env;
     const float* __restrict__ noise = noise_arr + (size_t)env * mc.P * mc.ldn;
@@ -705,19 +730,25 @@ __global__ void __launch_bounds__(512) batch_rollout_ga_kernel(const ModelConst 
 // (eflag[e], device memory, unread).  Then thread 0 counts its block; the last arriver resets the counter for the
 // next launch and stores `seq` into the host's word -- after every block's outputs, so one word publishes them all.
 // ENVT (srbd_batch_set_env_params): the tail lanes' final GRFs and predicted state use envs[e] (merge_body's ENVT).
+// The due mask: a block whose environment is not due skips merge_body -- in[e], its records, out[e] and eflag[e] are
+// neither written nor read -- and still takes part in the arrival count, so the count reaches gridDim.y, the counter
+// is zero again and `seq` is published whatever the mask holds, an all-zero one included.
 template <int NT, bool STAGE, bool ENVT = false>
 __global__ void __launch_bounds__(NT) batch_merge_kernel(const ModelConst mc, StepInput* __restrict__ in,
                                                          const float* __restrict__ recs, int rec_stride,
                                                          const float* __restrict__ noise,
                                                          StepOutput* __restrict__ out, uint32_t* __restrict__ eflag,
                                                          uint32_t* __restrict__ count, uint32_t* __restrict__ flag,
-                                                         uint32_t seq, const EnvModel* __restrict__ envs) {
+                                                         uint32_t seq, const EnvModel* __restrict__ envs,
+                                                         const int32_t* __restrict__ due) {
     const int e = blockIdx.y;
     __shared__ MergeShared<NT> sh;
     extern __shared__ __attribute__((aligned(16))) float dsm[];
-    merge_body<NT, STAGE, false, ENVT>(mc, in + e, recs + (size_t)e * mc.nleaf * rec_stride, mc.nleaf, rec_stride, 0,
-                                       noise + (size_t)e * mc.P * mc.ldn, nullptr, out + e, 0, 0, nullptr, eflag + e,
-                                       seq, 0, 1, sh, dsm, false, 0, nullptr, ENVT ? envs + e : nullptr);
+    if (!not_due(due, e))
+        merge_body<NT, STAGE, false, ENVT>(mc, in + e, recs + (size_t)e * mc.nleaf * rec_stride, mc.nleaf, rec_stride,
+                                           0, noise + (size_t)e * mc.P * mc.ldn, nullptr, out + e, 0, 0, nullptr,
+                                           eflag + e, seq, 0, 1, sh, dsm, false, 0, nullptr,
+                                           ENVT ? envs + e : nullptr);
     if (threadIdx.x == 0) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         const uint32_t old = __hip_atomic_fetch_add(count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -749,15 +780,15 @@ void launch_batch_copy(const StepInput* in_host, StepInput* in, int E, size_t by
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 void launch_batch_pack(const ModelConst& mc, const float* q_feet, const srbd_batch_device_io& io, StepInput* in, int E,
-                       hipStream_t s, const srbd_batch_cem_io* cem, const EnvModel* envs) {
+                       hipStream_t s, const srbd_batch_cem_io* cem, const EnvModel* envs, const int32_t* due) {
     if (envs) {
         const int v = aligned16(io.states) && aligned16(io.refs) && aligned16(io.best_params);
         if (cem)
             hipLaunchKernelGGL(batch_pack_env_kernel<true>, dim3(E), dim3(64), 0, s, io, mc.H, mc.P, v, in, envs, *cem,
-                               (int)aligned16(cem->sigma));
+                               (int)aligned16(cem->sigma), due);
         else
             hipLaunchKernelGGL(batch_pack_env_kernel<false>, dim3(E), dim3(64), 0, s, io, mc.H, mc.P, v, in, envs,
-                               srbd_batch_cem_io{nullptr, 0.0f, 0}, 0);
+                               srbd_batch_cem_io{nullptr, 0.0f, 0}, 0, due);
         return;
     }
     BatchPackConst pc;
@@ -768,20 +799,20 @@ void launch_batch_pack(const ModelConst& mc, const float* q_feet, const srbd_bat
     const int vec = aligned16(io.states) && aligned16(io.refs) && aligned16(io.best_params);
     if (cem)
         hipLaunchKernelGGL(batch_pack_cem_kernel, dim3(E), dim3(64), 0, s, io, pc, vec, in, *cem,
-                           (int)aligned16(cem->sigma));
+                           (int)aligned16(cem->sigma), due);
     else
-        hipLaunchKernelGGL(batch_pack_kernel, dim3(E), dim3(64), 0, s, io, pc, vec, in);
+        hipLaunchKernelGGL(batch_pack_kernel, dim3(E), dim3(64), 0, s, io, pc, vec, in, due);
 }
 
 void launch_batch_unpack(const ModelConst& mc, const srbd_batch_device_io& io, const StepOutput* out,
-                         const float* costs, int E, hipStream_t s, float* sigma) {
+                         const float* costs, int E, hipStream_t s, float* sigma, const int32_t* due) {
     const int vec = aligned16(io.best_params) && aligned16(io.grf) && aligned16(io.predicted_state);
     if (sigma)
         hipLaunchKernelGGL(batch_unpack_cem_kernel, dim3(E), dim3(256), 0, s, io, out, costs, mc.P, mc.n_local, mc.ldn,
-                           vec, sigma, (int)aligned16(sigma));
+                           vec, sigma, (int)aligned16(sigma), due);
     else
         hipLaunchKernelGGL(batch_unpack_kernel, dim3(E), dim3(256), 0, s, io, out, costs, mc.P, mc.n_local, mc.ldn,
-                           vec);
+                           vec, due);
 }
 
 void launch_batch_set_env_params(const srbd_env_params* params, const int32_t* mask, int32_t* rejected, int E,
@@ -790,24 +821,27 @@ void launch_batch_set_env_params(const srbd_env_params* params, const int32_t* m
                        envs);
 }
 
-void launch_batch_set_gait(const BatchGaitJob& j, StepInput* in, float* ga_freq, int E, hipStream_t s) {
+void launch_batch_set_gait(const BatchGaitJob& j, StepInput* in, float* ga_freq, int E, hipStream_t s,
+                           const int32_t* due) {
     // one wave per environment for the fields alone; four when N rows are copied besides
-    hipLaunchKernelGGL(batch_set_gait_kernel, dim3(E), dim3(j.io.freq_rows ? 256 : 64), 0, s, j, in, ga_freq);
+    hipLaunchKernelGGL(batch_set_gait_kernel, dim3(E), dim3(j.io.freq_rows ? 256 : 64), 0, s, j, in, ga_freq, due);
 }
 
-void launch_batch_rng(const ModelConst& mc, const StepInput* in, float* noise, int E, hipStream_t s) {
+void launch_batch_rng(const ModelConst& mc, const StepInput* in, float* noise, int E, hipStream_t s,
+                      const int32_t* due) {
     // the draws do not depend on the grid (rng_items strides over the items): about 32 768 blocks in all
     const int gx = std::max(1, std::min(rng_grid(mc), 32768 / E));
-    hipLaunchKernelGGL(batch_rng_kernel, dim3(gx, E), dim3(256), 0, s, mc, in, noise);
+    hipLaunchKernelGGL(batch_rng_kernel, dim3(gx, E), dim3(256), 0, s, mc, in, noise, due);
 }
 
-void launch_batch_transpose(const ModelConst& mc, const float* src, float* noise, int E, hipStream_t s) {
+void launch_batch_transpose(const ModelConst& mc, const float* src, float* noise, int E, hipStream_t s,
+                            const int32_t* due) {
     const dim3 grid((mc.n_local + 31) / 32, (mc.P + 31) / 32, E);
-    hipLaunchKernelGGL(batch_transpose_kernel, grid, dim3(256), 0, s, src, mc.n_local, mc.P, mc.ldn, noise);
+    hipLaunchKernelGGL(batch_transpose_kernel, grid, dim3(256), 0, s, src, mc.n_local, mc.P, mc.ldn, noise, due);
 }
 
 void launch_batch_rollout(const ModelConst& mc, const StepInput* in, const float* noise, float* costs, float* recs,
-                          int rec_stride, int E, hipStream_t s, const EnvModel* envs) {
+                          int rec_stride, int E, hipStream_t s, const EnvModel* envs, const int32_t* due) {
     const dim3 grid(mc.nleaf, E);
     const int H = mc.H, S = mc.S;
     // mc.cost_on (srbd_batch_set_cost_terms): the EXT instantiations, on the same compile-time shapes; CEM
@@ -818,16 +852,16 @@ void launch_batch_rollout(const ModelConst& mc, const StepInput* in, const float
     {                                                                                                             \
         if (cem && mc.cost_on)                                                                                    \
             hipLaunchKernelGGL((batch_rollout_kernel<K, HH, SS, true, true, ENVT>), grid, dim3(256), 0, s, mc,    \
-                               in, noise, costs, recs, rec_stride, EV);                                           \
+                               in, noise, costs, recs, rec_stride, EV, due);                                      \
         else if (cem)                                                                                             \
             hipLaunchKernelGGL((batch_rollout_kernel<K, HH, SS, true, false, ENVT>), grid, dim3(256), 0, s, mc,   \
-                               in, noise, costs, recs, rec_stride, EV);                                           \
+                               in, noise, costs, recs, rec_stride, EV, due);                                      \
         else if (mc.cost_on)                                                                                      \
             hipLaunchKernelGGL((batch_rollout_kernel<K, HH, SS, false, true, ENVT>), grid, dim3(256), 0, s, mc,   \
-                               in, noise, costs, recs, rec_stride, EV);                                           \
+                               in, noise, costs, recs, rec_stride, EV, due);                                      \
         else                                                                                                      \
             hipLaunchKernelGGL((batch_rollout_kernel<K, HH, SS, false, false, ENVT>), grid, dim3(256), 0, s, mc,  \
-                               in, noise, costs, recs, rec_stride, EV);                                           \
+                               in, noise, costs, recs, rec_stride, EV, due);                                      \
         return;                                                                                                   \
     }
 #define SRBD_BR(K, HH, SS) SRBD_BR_(K, HH, SS, false, none)
@@ -866,14 +900,15 @@ void launch_batch_rollout(const ModelConst& mc, const StepInput* in, const float
 }
 
 void launch_batch_rollout_ga(const ModelConst& mc, const StepInput* in, const float* noise, float* costs, float* recs,
-                             int rec_stride, const float* ga_freq, int E, hipStream_t s, const EnvModel* envs) {
+                             int rec_stride, const float* ga_freq, int E, hipStream_t s, const EnvModel* envs,
+                             const int32_t* due) {
     const dim3 grid(mc.nleaf, E);
     const int H = mc.H;
     const EnvModel* const none = nullptr;
 #define SRBD_BG_(K, HH, ENVT, EV)                                                                                 \
     {                                                                                                             \
         hipLaunchKernelGGL((batch_rollout_ga_kernel<K, HH, ENVT>), grid, dim3(256), 0, s, mc, in, noise, costs,   \
-                           recs, rec_stride, ga_freq, EV);                                                        \
+                           recs, rec_stride, ga_freq, EV, due);                                                   \
         return;                                                                                                   \
     }
 #define SRBD_BG(K, HH) SRBD_BG_(K, HH, false, none)
@@ -911,23 +946,23 @@ void launch_batch_rollout_ga(const ModelConst& mc, const StepInput* in, const fl
 
 void launch_batch_merge(const ModelConst& mc, StepInput* in, const float* recs, int rec_stride, const float* noise,
                         StepOutput* out, uint32_t* eflag, uint32_t* count, uint32_t* flag, uint32_t seq, int E,
-                        hipStream_t s, const EnvModel* envs) {
+                        hipStream_t s, const EnvModel* envs, const int32_t* due) {
     size_t smem = 0;
     const dim3 grid(1, E);
     const EnvModel* const none = nullptr;
     const bool stage = merge_stage_fits(mc.nleaf, rec_stride, mc.P, mc.K, &smem);
     if (stage && envs)
         hipLaunchKernelGGL((batch_merge_kernel<MERGE_STAGE_THREADS, true, true>), grid, dim3(MERGE_STAGE_THREADS), smem,
-                           s, mc, in, recs, rec_stride, noise, out, eflag, count, flag, seq, envs);
+                           s, mc, in, recs, rec_stride, noise, out, eflag, count, flag, seq, envs, due);
     else if (stage)
         hipLaunchKernelGGL((batch_merge_kernel<MERGE_STAGE_THREADS, true>), grid, dim3(MERGE_STAGE_THREADS), smem, s, mc,
-                           in, recs, rec_stride, noise, out, eflag, count, flag, seq, none);
+                           in, recs, rec_stride, noise, out, eflag, count, flag, seq, none, due);
     else if (envs)
         hipLaunchKernelGGL((batch_merge_kernel<MERGE_THREADS, false, true>), grid, dim3(MERGE_THREADS), smem, s, mc, in,
-                           recs, rec_stride, noise, out, eflag, count, flag, seq, envs);
+                           recs, rec_stride, noise, out, eflag, count, flag, seq, envs, due);
     else
         hipLaunchKernelGGL((batch_merge_kernel<MERGE_THREADS, false>), grid, dim3(MERGE_THREADS), smem, s, mc, in, recs,
-                           rec_stride, noise, out, eflag, count, flag, seq, none);
+                           rec_stride, noise, out, eflag, count, flag, seq, none, due);
 }
 
 }  // namespace srbd

@@ -162,6 +162,9 @@ void launch_arm_copy(const uint32_t* go, uint32_t seq, uint64_t deadline_ticks, 
 void launch_div_selftest(const float* a, const float* b, int n, float* o, hipStream_t s);
 void launch_log1p_selftest(const float* t, int n, float* o, hipStream_t s);
 
+// `due` (here and in every batch launcher of the device step below): NULL, or E words of device memory -- the due mask
+// of srbd_batch_step_masked_device: the blocks of an environment with due[e] == 0 return before any other global
+// access (launch_batch_merge's still count themselves); the grids do not depend on it.
 // Batched environments (srbd_batch.hip): E independent problems of one ModelConst (world 1; CEM through
 // srbd_batch_create_cem) per launch, environment e on blockIdx.y.  Device arrays: in[E]; noise E x P x ldn (SoA per environment); costs
 // E x ldn; recs E x nleaf leaf records; out[E] and `flag` host-mapped.  Every launch count is independent of E.
@@ -178,13 +181,15 @@ void launch_batch_copy(const StepInput* in_host, StepInput* in, int E, size_t by
 // out[e].sigma into the caller's sigma rows, in the same launches
 // envs != NULL (srbd_batch_set_env_params): fzref and cost_feet from environment e's record instead of mc.mg / q_feet
 void launch_batch_pack(const ModelConst& mc, const float* q_feet, const srbd_batch_device_io& io, StepInput* in, int E,
-                       hipStream_t s, const srbd_batch_cem_io* cem = nullptr, const EnvModel* envs = nullptr);
+                       hipStream_t s, const srbd_batch_cem_io* cem = nullptr, const EnvModel* envs = nullptr,
+                       const int32_t* due = nullptr);
 // srbd_batch_set_env_params_device: the caller's device arrays (E records; mask and rejected E words or NULL) into the
 // batch's raw fields raw[E] and derived records envs[E]; one thread per environment
 void launch_batch_set_env_params(const srbd_env_params* params, const int32_t* mask, int32_t* rejected, int E,
                                  srbd_env_params* raw, EnvModel* envs, hipStream_t s);
 void launch_batch_unpack(const ModelConst& mc, const srbd_batch_device_io& io, const StepOutput* out,
-                         const float* costs, int E, hipStream_t s, float* sigma = nullptr);
+                         const float* costs, int E, hipStream_t s, float* sigma = nullptr,
+                         const int32_t* due = nullptr);
 // srbd_batch_set_gait_device: the caller's io by value, the chunk boundaries ga_chunk_bounds formed on the host and the
 // shapes; in[e]'s gait fields, and with io.freq_rows environment e's N rows into ga_freq at stride ldn
 struct BatchGaitJob {
@@ -192,28 +197,32 @@ struct BatchGaitJob {
     int32_t cb[GA_MAXCB];
     int32_t random_sampling, N, ldn;
 };
-void launch_batch_set_gait(const BatchGaitJob& j, StepInput* in, float* ga_freq, int E, hipStream_t s);
+void launch_batch_set_gait(const BatchGaitJob& j, StepInput* in, float* ga_freq, int E, hipStream_t s,
+                           const int32_t* due = nullptr);
 // environment e's draws keyed by in[e]'s seed and counter (rng_items)
-void launch_batch_rng(const ModelConst& mc, const StepInput* in, float* noise, int E, hipStream_t s);
+void launch_batch_rng(const ModelConst& mc, const StepInput* in, float* noise, int E, hipStream_t s,
+                      const int32_t* due = nullptr);
 // injected noise, E x n_local x P row-major -> SoA per environment
-void launch_batch_transpose(const ModelConst& mc, const float* src, float* noise, int E, hipStream_t s);
+void launch_batch_transpose(const ModelConst& mc, const float* src, float* noise, int E, hipStream_t s,
+                            const int32_t* due = nullptr);
 // four-lane rollouts, one 64-sample leaf per block: costs and leaf records (no in-launch fold); mc.cost_on selects
 // the kernels with the opt-in cost terms
 // envs != NULL (srbd_batch_set_env_params, here and in the two launchers below): E per-environment records; the
 // kernels' ENVT forms read the robot's and the cost's constants from envs[e] instead of mc
 void launch_batch_rollout(const ModelConst& mc, const StepInput* in, const float* noise, float* costs, float* recs,
-                          int rec_stride, int E, hipStream_t s, const EnvModel* envs = nullptr);
+                          int rec_stride, int E, hipStream_t s, const EnvModel* envs = nullptr,
+                          const int32_t* due = nullptr);
 // the gait-adaptive four-lane rollouts, keyed by in[e]'s gait fields; ga_freq: E x ldn injected per-row frequencies
 // (read only when in[e].ga_explicit is set; padding rows zero), else may be NULL
 void launch_batch_rollout_ga(const ModelConst& mc, const StepInput* in, const float* noise, float* costs, float* recs,
                              int rec_stride, const float* ga_freq, int E, hipStream_t s,
-                             const EnvModel* envs = nullptr);
+                             const EnvModel* envs = nullptr, const int32_t* due = nullptr);
 // one block per environment folds its leaf records to the root (merge_body) and writes out[e]; the blocks count
 // themselves in *count (zero between launches: the last arriver resets it) and the last one stores `seq` in *flag.
 // eflag: E device words (each block's own publish word inside merge_body)
 void launch_batch_merge(const ModelConst& mc, StepInput* in, const float* recs, int rec_stride, const float* noise,
                         StepOutput* out, uint32_t* eflag, uint32_t* count, uint32_t* flag, uint32_t seq, int E,
-                        hipStream_t s, const EnvModel* envs = nullptr);
+                        hipStream_t s, const EnvModel* envs = nullptr, const int32_t* due = nullptr);
 
 // The full-horizon plan of one parameter row per environment (srbd_plan.hip; srbd_batch_plan_device, srbd_plan): one
 // thread per environment, PLAN_ENVS of them per block, the block's outputs staged in LDS, hc steps at a time
@@ -427,10 +436,11 @@ struct LoopResetJob {
 // the current contact from column 0 of io.contacts, and environment e's io.iterations step keys (rule `rng`,
 // srbd_iface.h) into step_keys -- IFACE_MAX_ITERS rows of 2 E words, row i = E seeds then E counters -- with the
 // advanced key back in io.keys.  Epilogue: io.grf = io.grf_raw x current contact (float64), io.footholds from
-// io.ref_in, io.previous_contact = current contact.
+// io.ref_in, io.previous_contact = current contact.  due: a lane of an environment that is not due returns before
+// any other access (its key does not advance, its previous contact stays that of its last solve).
 void launch_iface_prologue(const srbd_batch_interface_io& io, int rng, int num_params, uint64_t* step_keys, int E,
-                           hipStream_t s);
-void launch_iface_epilogue(const srbd_batch_interface_io& io, int E, hipStream_t s);
+                           hipStream_t s, const int32_t* due = nullptr);
+void launch_iface_epilogue(const srbd_batch_interface_io& io, int E, hipStream_t s, const int32_t* due = nullptr);
 // srbd_api.hip: the calling thread's error text (srbd_last_error(NULL)) for an entry point that has no handle.
 int fail_global(int code, const char* message);
 

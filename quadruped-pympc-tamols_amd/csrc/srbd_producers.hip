@@ -234,10 +234,14 @@ struct IfaceJob {
     uint64_t *keys, *step_keys;
     int32_t contact_stride, iterations, params_per_leg, num_params, rng;
 };
-__global__ void __launch_bounds__(PROD_BLOCK) iface_prologue_kernel(int E, const IfaceJob j) {
+// due (srbd_batch_interface_step_masked_device; NULL otherwise): the four lanes of an environment that is not due
+// return behind that one load -- nothing of it is prepared, its key stays where its last solve left it.
+__global__ void __launch_bounds__(PROD_BLOCK) iface_prologue_kernel(int E, const IfaceJob j,
+                                                                    const int32_t* __restrict__ due) {
     const int t = blockIdx.x * PROD_BLOCK + threadIdx.x;
     if (t >= 4 * E) return;
     const int e = t >> 2, l = t & 3;
+    if (due && due[e] == 0) return;
     prepare_state_leg(e, l, j.contacts + (size_t)t * j.contact_stride, j.previous_contact + t, j.state_in, j.ref_in,
                       j.params_per_leg, j.num_params, j.best_params, j.states, j.refs);
     if (l == 0) {
@@ -263,11 +267,13 @@ __global__ void __launch_bounds__(PROD_BLOCK) iface_epilogue_kernel(int E, const
                                                                     const double* __restrict__ ref_in,
                                                                     double* __restrict__ grf,
                                                                     double* __restrict__ footholds,
-                                                                    float* __restrict__ previous_contact) {
+                                                                    float* __restrict__ previous_contact,
+                                                                    const int32_t* __restrict__ due) {
 #pragma clang fp contract(off)
     const int t = blockIdx.x * PROD_BLOCK + threadIdx.x;
     if (t >= 4 * E) return;
     const int e = t >> 2, l = t & 3;
+    if (due && due[e] == 0) return;  // not due: previous_contact keeps the contact of its last solve
     const float cur = contacts[(size_t)t * contact_stride];
     const double cd = (double)cur;
 #pragma unroll
@@ -863,7 +869,7 @@ extern "C" int srbd_prepare_state_device(int32_t num_envs, const double* d_state
 
 // srbd_batch_interface_step_device (srbd_api_batch.hip, which owns the batch) enqueues its two launches through these.
 void srbd::launch_iface_prologue(const srbd_batch_interface_io& io, int rng, int num_params, uint64_t* step_keys, int E,
-                                 hipStream_t s) {
+                                 hipStream_t s, const int32_t* due) {
     IfaceJob j = {};
     j.state_in = io.state_in, j.ref_in = io.ref_in;
     j.contacts = io.contacts, j.previous_contact = io.previous_contact;
@@ -871,11 +877,11 @@ void srbd::launch_iface_prologue(const srbd_batch_interface_io& io, int rng, int
     j.keys = io.keys, j.step_keys = step_keys;
     j.contact_stride = io.contact_stride, j.iterations = io.iterations;
     j.params_per_leg = io.params_per_leg, j.num_params = num_params, j.rng = rng;
-    hipLaunchKernelGGL(iface_prologue_kernel, dim3(blocks_of(E)), dim3(PROD_BLOCK), 0, s, E, j);
+    hipLaunchKernelGGL(iface_prologue_kernel, dim3(blocks_of(E)), dim3(PROD_BLOCK), 0, s, E, j, due);
 }
-void srbd::launch_iface_epilogue(const srbd_batch_interface_io& io, int E, hipStream_t s) {
+void srbd::launch_iface_epilogue(const srbd_batch_interface_io& io, int E, hipStream_t s, const int32_t* due) {
     hipLaunchKernelGGL(iface_epilogue_kernel, dim3(blocks_of(E)), dim3(PROD_BLOCK), 0, s, E, io.grf_raw, io.contacts,
-                       io.contact_stride, io.ref_in, io.grf, io.footholds, io.previous_contact);
+                       io.contact_stride, io.ref_in, io.grf, io.footholds, io.previous_contact, due);
 }
 
 extern "C" int srbd_frg_step_device(srbd_frg* d_frg, int32_t num_envs, const srbd_frg_batch_io* io, void* hip_stream) {

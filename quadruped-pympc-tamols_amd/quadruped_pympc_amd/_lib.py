@@ -471,6 +471,10 @@ SIGNATURES.update({
     # the controller interface's step of a batch, and the host twin of its key schedule
     "srbd_batch_interface_step_device": (_I, [_P, C.POINTER(BatchInterfaceIO), _P]),
     "srbd_selftest_interface_keys": (_I, [_P, _I, _I, _I, _P]),
+    # the same three device steps for the environments a due mask names
+    "srbd_batch_step_masked_device": (_I, [_P, C.POINTER(BatchDeviceIO), _P, _P]),
+    "srbd_batch_step_cem_masked_device": (_I, [_P, C.POINTER(BatchDeviceIO), C.POINTER(BatchCemIO), _P, _P]),
+    "srbd_batch_interface_step_masked_device": (_I, [_P, C.POINTER(BatchInterfaceIO), _P, _P]),
     # start-and-stop (host and device) and update_state_and_reference in one launch
     "srbd_pgg_start_stop": (_I, [C.POINTER(SrbdPgg), _DP, _DP, _D, _DP, _DP, _DP, _DP, _DP, _DP, _DP]),
     "srbd_pgg_start_stop_device": (_I, [_P, _I, C.POINTER(SrbdStartStopBatchIo), _P]),
@@ -1336,22 +1340,66 @@ class BatchContext:
 
         return self._step_device(dev, enqueue, states, refs, contacts, best, seeds, counters, noise, want_costs, stream)
 
-    def _step_device(self, dev, enqueue, states, refs, contacts, best, seeds, counters, noise, want_costs, stream):
+    def check_due(self, due, dev=None):
+        """The argument checks of the masked steps' ``due`` (ValueError; nothing is enqueued): an (E,) int32 or bool
+        torch tensor, contiguous, on the context's device."""
+        import torch
+
+        dev = torch.device("cuda", self.cfg.device_id) if dev is None else dev
+        _device_tensors_shape([("due", due, (self.E,), (torch.int32, torch.bool))])
+        if due.device != dev:
+            raise ValueError(f"due must be on {dev}, got {due.device}")
+
+    @staticmethod
+    def _due_words(due, s):
+        """``due`` as the int32 words the library reads; a bool mask is converted on the stream (no host read)."""
+        import torch
+
+        if due.dtype == torch.int32:
+            return due
+        with torch.cuda.stream(s):
+            return due.to(torch.int32)
+
+    def step_masked_device(self, states, refs, contacts, best, seeds, counters, due, *, noise=None, want_costs=False,
+                           out=None, stream=None):
+        """srbd_batch_step_masked_device: ``step_device`` for the environments ``due`` names -- an (E,) int32 or bool
+        tensor of the context's device, non-zero / True: step this environment.  A due environment gets the bytes
+        ``step_device`` gives it; an environment that is not due is neither written nor read: its ``best`` row and
+        its rows of the outputs keep their bytes, and its draws and rollouts do not run.  out None: the output dict
+        is allocated as by ``step_device``, but zero-filled, so a row that was never due is defined; out a dict this
+        method returned: the due rows are written into it, the others hold their last solve."""
+        dev = self.check_step_device(states, refs, contacts, best, seeds, counters, noise)
+        self.check_due(due, dev)
+
+        def enqueue(io, handle, words):
+            self.check(lib.srbd_batch_step_masked_device(self.h, C.byref(io), words.data_ptr(), handle),
+                       "srbd_batch_step_masked_device")
+
+        return self._step_device(dev, enqueue, states, refs, contacts, best, seeds, counters, noise, want_costs, stream,
+                                 due=due, out=out)
+
+    def _step_device(self, dev, enqueue, states, refs, contacts, best, seeds, counters, noise, want_costs, stream,
+                     due=None, out=None):
         """The output tensors and the io struct of a device step (the arguments already checked); ``enqueue(io,
-        stream handle)`` makes the library call."""
+        stream handle)`` makes the library call -- ``enqueue(io, stream handle, due words)`` for a masked step, whose
+        outputs are ``out`` or zero-filled."""
         import torch
 
         E, N = self.E, self.N
         s = torch.cuda.current_stream(dev) if stream is None else stream
-        with torch.cuda.stream(s):  # the outputs belong to the stream that writes them
-            out = {"grf": torch.empty((E, 12), dtype=torch.float32, device=dev),
-                   "predicted_state": torch.empty((E, 24), dtype=torch.float32, device=dev),
-                   "best_cost": torch.empty(E, dtype=torch.float32, device=dev),
-                   "best_index": torch.empty(E, dtype=torch.int32, device=dev),
-                   "best_freq": torch.empty(E, dtype=torch.float32, device=dev),
-                   "status": torch.empty(E, dtype=torch.int32, device=dev)}
-            if want_costs:
-                out["costs"] = torch.empty((E, N), dtype=torch.float32, device=dev)
+        if out is None:
+            new = torch.empty if due is None else torch.zeros
+            with torch.cuda.stream(s):  # the outputs belong to the stream that writes them
+                out = {"grf": new((E, 12), dtype=torch.float32, device=dev),
+                       "predicted_state": new((E, 24), dtype=torch.float32, device=dev),
+                       "best_cost": new(E, dtype=torch.float32, device=dev),
+                       "best_index": new(E, dtype=torch.int32, device=dev),
+                       "best_freq": new(E, dtype=torch.float32, device=dev),
+                       "status": new(E, dtype=torch.int32, device=dev)}
+                if want_costs:
+                    out["costs"] = new((E, N), dtype=torch.float32, device=dev)
+        elif want_costs and "costs" not in out:
+            raise ValueError("out holds no costs: it was made without want_costs")
         io = BatchDeviceIO(states=states.data_ptr(), refs=refs.data_ptr(), contacts=contacts.data_ptr(),
                            noise=None if noise is None else noise.data_ptr(), seeds=seeds.data_ptr(),
                            counters=counters.data_ptr(), contact_stride=int(contacts.shape[2]), pad=0,
@@ -1362,7 +1410,10 @@ class BatchContext:
                            costs=out["costs"].data_ptr() if want_costs else None)
         # torch's default stream is the null stream, handle 0, which the C call reads as "the batch's own stream":
         # hand it on by its explicit handle (hipStreamLegacy)
-        enqueue(io, C.c_void_p(s.cuda_stream or 1))
+        if due is None:
+            enqueue(io, C.c_void_p(s.cuda_stream or 1))
+        else:
+            enqueue(io, C.c_void_p(s.cuda_stream or 1), self._due_words(due, s))
         return out
 
     def check_plan_device(self, states, refs, contacts, params, freqs=None):
@@ -1448,8 +1499,23 @@ class BatchContext:
                    "srbd_batch_plan")
         return out
 
+    def interface_step_masked_device(self, state_in, ref_in, contacts, keys, previous_contact, best, due, out=None,
+                                     **kw):
+        """srbd_batch_interface_step_masked_device: ``interface_step_device`` (its arguments and keywords) for the
+        environments ``due`` names -- an (E,) int32 or bool tensor of the context's device (a bool mask is converted on
+        the stream, no host read); ``mpc_due`` (interfaces/srbd_controller_interface_batched) forms it from the
+        simulator's step counters.  A due environment gets the bytes ``interface_step_device`` gives it.  An
+        environment that is not due is neither written nor read: keys, previous_contact, best and sigma keep its rows
+        (the key does not advance, the previous contact stays that of its last solve), and so do the outputs.
+        out None: the output dict is allocated as by ``interface_step_device``, but zero-filled, so a row that was
+        never due is defined; out the dict of the previous call: the due rows are written into it and the others hold
+        their last solve -- what the reference holds between solves."""
+        return self.interface_step_device(state_in, ref_in, contacts, keys, previous_contact, best, _due=due, _out=out,
+                                          **kw)
+
     def interface_step_device(self, state_in, ref_in, contacts, keys, previous_contact, best, *, iterations: int = 1,
-                              sigma=None, sigma_reset: float = 0.0, gait_io=None, want_costs=False, stream=None):
+                              sigma=None, sigma_reset: float = 0.0, gait_io=None, want_costs=False, stream=None,
+                              _due=None, _out=None):
         """srbd_batch_interface_step_device: ``SRBDControllerInterface.compute_control``'s sampling branch for every
         environment, enqueued on ``stream`` (None: ``torch.cuda.current_stream()``) without a host synchronisation:
         prepare_state, per sampling iteration the key schedule (and CEM's sigma reset at the first) and the device
@@ -1483,20 +1549,27 @@ class BatchContext:
                 raise ValueError(f"{name} must be on {dev}, got {t.device}")
         if not 1 <= int(iterations) <= MAX_IFACE_ITERS:
             raise ValueError(f"iterations must be in 1..{MAX_IFACE_ITERS}, got {iterations}")
+        if _due is not None:
+            self.check_due(_due, dev)
         s = torch.cuda.current_stream(dev) if stream is None else stream
-        with torch.cuda.stream(s):  # the outputs belong to the stream that writes them
-            out = {"states": torch.empty((E, 24), dtype=torch.float32, device=dev),
-                   "refs": torch.empty((E, 24), dtype=torch.float32, device=dev),
-                   "grf": torch.empty((E, 12), dtype=torch.float64, device=dev),
-                   "footholds": torch.empty((E, 12), dtype=torch.float64, device=dev),
-                   "grf_raw": torch.empty((E, 12), dtype=torch.float32, device=dev),
-                   "predicted_state": torch.empty((E, 24), dtype=torch.float32, device=dev),
-                   "best_cost": torch.empty(E, dtype=torch.float32, device=dev),
-                   "best_index": torch.empty(E, dtype=torch.int32, device=dev),
-                   "best_freq": torch.empty(E, dtype=torch.float32, device=dev),
-                   "status": torch.empty(E, dtype=torch.int32, device=dev)}
-            if want_costs:
-                out["costs"] = torch.empty((E, N), dtype=torch.float32, device=dev)
+        out = _out
+        if out is None:
+            new = torch.empty if _due is None else torch.zeros  # masked: a row that was never due is defined
+            with torch.cuda.stream(s):  # the outputs belong to the stream that writes them
+                out = {"states": new((E, 24), dtype=torch.float32, device=dev),
+                       "refs": new((E, 24), dtype=torch.float32, device=dev),
+                       "grf": new((E, 12), dtype=torch.float64, device=dev),
+                       "footholds": new((E, 12), dtype=torch.float64, device=dev),
+                       "grf_raw": new((E, 12), dtype=torch.float32, device=dev),
+                       "predicted_state": new((E, 24), dtype=torch.float32, device=dev),
+                       "best_cost": new(E, dtype=torch.float32, device=dev),
+                       "best_index": new(E, dtype=torch.int32, device=dev),
+                       "best_freq": new(E, dtype=torch.float32, device=dev),
+                       "status": new(E, dtype=torch.int32, device=dev)}
+                if want_costs:
+                    out["costs"] = new((E, N), dtype=torch.float32, device=dev)
+        elif want_costs and "costs" not in out:
+            raise ValueError("out holds no costs: it was made without want_costs")
         io = BatchInterfaceIO(
             state_in=state_in.data_ptr(), ref_in=ref_in.data_ptr(), contacts=contacts.data_ptr(),
             contact_stride=int(contacts.shape[2]), iterations=int(iterations), params_per_leg=P // 4, pad=0,
@@ -1509,8 +1582,14 @@ class BatchContext:
             best_index=out["best_index"].data_ptr(), best_freq=out["best_freq"].data_ptr(),
             status=out["status"].data_ptr(), costs=out["costs"].data_ptr() if want_costs else None)
         # the null stream by its explicit handle, as in step_device
-        self.check(lib.srbd_batch_interface_step_device(self.h, C.byref(io), C.c_void_p(s.cuda_stream or 1)),
-                   "srbd_batch_interface_step_device")
+        if _due is None:
+            self.check(lib.srbd_batch_interface_step_device(self.h, C.byref(io), C.c_void_p(s.cuda_stream or 1)),
+                       "srbd_batch_interface_step_device")
+        else:
+            words = self._due_words(_due, s)
+            self.check(lib.srbd_batch_interface_step_masked_device(self.h, C.byref(io), words.data_ptr(),
+                                                                   C.c_void_p(s.cuda_stream or 1)),
+                       "srbd_batch_interface_step_masked_device")
         if gait_io is not None:
             self._gait = True
         return out
@@ -1594,11 +1673,42 @@ class CemBatchContext(BatchContext):
 
         return self._step_device(dev, enqueue, states, refs, contacts, best, seeds, counters, noise, want_costs, stream)
 
+    def step_cem_masked_device(self, states, refs, contacts, best, sigma, seeds, counters, due, *,
+                               sigma_reset: float = 0.0, noise=None, want_costs=False, out=None, stream=None):
+        """srbd_batch_step_cem_masked_device: ``step_cem_device`` for the environments ``due`` names, with ``due`` and
+        ``out`` as ``BatchContext.step_masked_device`` takes them.  The sigma row of an environment that is not due
+        keeps its bytes: sigma_reset is not applied to it."""
+        dev = self.check_step_cem_device(states, refs, contacts, best, sigma, seeds, counters, noise, sigma_reset)
+        self.check_due(due, dev)
+        cem = BatchCemIO(sigma=sigma.data_ptr(), sigma_reset=float(sigma_reset), pad=0)
+
+        def enqueue(io, handle, words):
+            self.check(lib.srbd_batch_step_cem_masked_device(self.h, C.byref(io), C.byref(cem), words.data_ptr(),
+                                                             handle), "srbd_batch_step_cem_masked_device")
+
+        return self._step_device(dev, enqueue, states, refs, contacts, best, seeds, counters, noise, want_costs, stream,
+                                 due=due, out=out)
+
 
 # ---------------------------------------------------------------------- device producers (include/srbd_mpc.h)
 PGG_BYTES = C.sizeof(SrbdPgg)
 MAX_ENVS = 4096
 MAX_DTS = 32
+
+
+def _device_tensors_shape(specs):
+    """The host half of ``_device_tensors``: type, dtype, shape and contiguity of (name, tensor, shape, dtypes)."""
+    import torch
+
+    for name, t, shape, dtypes in specs:
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch tensor, got {type(t).__name__}")
+        if t.dtype not in dtypes:
+            raise ValueError(f"{name} must be {' or '.join(str(d) for d in dtypes)}, got {t.dtype}")
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
 
 
 def _device_tensors(specs):

@@ -151,7 +151,7 @@ class Batched_Sampling_MPC:
 
     def compute_control_device(self, states, references, contact_sequences, best_control_parameters, keys, *,
                                noise=None, stream=None, gait=None, timings=None, nominal_step_frequencies=None,
-                               optimize_swings=None, step_frequencies=None):
+                               optimize_swings=None, step_frequencies=None, due=None):
         """``compute_control`` on torch tensors of the context's device (``srbd_batch_step_device``): nothing crosses
         to the host and nothing waits for the device; the step is enqueued on ``stream`` (None: torch's current
         stream) and the returned tensors are ready in that stream's order.
@@ -169,7 +169,17 @@ class Batched_Sampling_MPC:
 
         The gait keywords (the gait-adaptive class only; see its ``_set_gait_device``): when any is given, the
         step's arguments are checked first and the gait setting is enqueued on ``stream`` ahead of the step
-        (``srbd_batch_set_gait_device``); without them the step runs with the last gait setting made."""
+        (``srbd_batch_set_gait_device``); without them the step runs with the last gait setting made.
+
+        due None: every environment is stepped.  due an (E,) int32 or bool tensor of the context's device
+        (``mpc_due``, interfaces/srbd_controller_interface_batched): only the environments it names are stepped
+        (``srbd_batch_step_masked_device``).  An environment that is not due is neither written nor read -- its row of
+        best_control_parameters keeps its bytes -- and the controller keeps one output dict for these calls, so the
+        returned tensors hold the last solve of the environments that are not due (zeros before the first) and are
+        overwritten in place by the next ``due=`` call; so do the ``costs`` rows.  The keys are the caller's: advance
+        only the due environments' keys.  The gait setter itself takes no mask (it is a setting, not a solve): with
+        the gait keywords every environment's gait fields are rewritten from its inputs, and an environment reads
+        them at its next due step; ``Batched_SRBDControllerInterface`` masks the gait setting with the rest."""
         import torch
 
         ctx = self.context
@@ -196,8 +206,14 @@ class Batched_Sampling_MPC:
         if with_gait:  # every refusal before anything is enqueued
             ctx.check_step_device(states, references, contact_sequences, best_control_parameters, seeds, counters, noise)
             self._set_gait_device(stream=stream, **gait_arguments)
-        out = ctx.step_device(states, references, contact_sequences, best_control_parameters, seeds, counters,
-                              noise=noise, stream=stream)
+        if due is None:
+            out = ctx.step_device(states, references, contact_sequences, best_control_parameters, seeds, counters,
+                                  noise=noise, stream=stream)
+        else:
+            out = self._held_result = ctx.step_masked_device(states, references, contact_sequences,
+                                                             best_control_parameters, seeds, counters, due,
+                                                             noise=noise, out=getattr(self, "_held_result", None),
+                                                             stream=stream)
         self._calls += 1
         with torch.cuda.stream(s):
             footholds = torch.zeros((E, 12), dtype=torch.int32, device=dev)

@@ -81,12 +81,15 @@ class Batched_CEM_Sampling_MPC(Batched_Sampling_MPC):
                 LazyBatchCosts(ctx, self._calls, self), sigma)
 
     def compute_control_device(self, states, references, contact_sequences, best_control_parameters, keys, sigma, *,
-                               sigma_reset=None, noise=None, stream=None):
+                               sigma_reset=None, noise=None, stream=None, due=None):
         """``compute_control`` on torch tensors of the context's device (``srbd_batch_step_cem_device``), enqueued on
         ``stream`` (None: torch's current stream) without a host synchronisation.  The tensors and ``keys`` are those
         of ``Batched_Sampling_MPC.compute_control_device``; sigma is an (E, P) float32 tensor updated in place.
         sigma_reset: None or 0 -- sigma is read; a positive constant -- every environment starts this call from it
         and sigma is only written (the first sampling iteration of a control step; see the module docstring).
+        due: None, or the (E,) int32 or bool mask of ``Batched_Sampling_MPC.compute_control_device``
+        (``srbd_batch_step_cem_masked_device``): an environment that is not due keeps its rows of best parameters and
+        sigma -- sigma_reset is not applied to it -- and the returned tensors hold its last solve.
         Returns the 8-tuple of ``compute_control`` as tensors, best parameters and sigma being the arguments."""
         import torch
 
@@ -107,9 +110,14 @@ class Batched_CEM_Sampling_MPC(Batched_Sampling_MPC):
             seeds = keys
             with torch.cuda.stream(s):
                 counters = torch.full((E,), self._calls + 1, dtype=torch.int64, device=dev)
-        out = ctx.step_cem_device(states, references, contact_sequences, best_control_parameters, sigma, seeds,
-                                  counters, sigma_reset=0.0 if sigma_reset is None else float(sigma_reset),
-                                  noise=noise, stream=stream)
+        reset = 0.0 if sigma_reset is None else float(sigma_reset)
+        if due is None:
+            out = ctx.step_cem_device(states, references, contact_sequences, best_control_parameters, sigma, seeds,
+                                      counters, sigma_reset=reset, noise=noise, stream=stream)
+        else:
+            out = self._held_result = ctx.step_cem_masked_device(
+                states, references, contact_sequences, best_control_parameters, sigma, seeds, counters, due,
+                sigma_reset=reset, noise=noise, out=getattr(self, "_held_result", None), stream=stream)
         self._calls += 1
         with torch.cuda.stream(s):
             footholds = torch.zeros((E, 12), dtype=torch.int32, device=dev)

@@ -23,6 +23,11 @@ after the first ``compute_control_device`` here, the controller's own ``compute_
 / ``with_newkey`` would continue from the stale host key.  Set ``iface.keys`` or ``iface.best_control_parameters`` (in
 place) to re-seed or re-start environments.
 
+The reference does not solve on every simulation step (quadruped_pympc_wrapper.py:134): ``due = mpc_due(step_num,
+simulation_dt, mpc_frequency)`` and ``compute_control_device(..., due=due)`` step only the environments whose own step
+counter says so (``srbd_batch_interface_step_masked_device``); the others are neither written nor read, and the
+returned tensors hold their last solve.
+
 ``shift_solution`` configurations raise ``NotImplementedError``, as ``prepare_state_and_reference_device`` does.  Graph
 capture, gait-adaptive CEM and more than ``_lib.MAX_IFACE_ITERS`` sampling iterations are not provided; only the last
 iteration's outputs are returned, as the reference keeps only the last.
@@ -33,6 +38,19 @@ import numpy as np
 
 from .. import _lib
 from ..controllers.sampling.centroidal_nmpc_hip_batched import LazyBatchCosts
+
+
+def mpc_due(step_num, simulation_dt: float, mpc_frequency: float):
+    """The reference's MPC gate for every environment (QuadrupedPyMPC_Wrapper.compute_actions,
+    quadruped_pympc_wrapper.py:134): ``step_num % round(1 / (mpc_frequency * simulation_dt)) == 0`` as an int32 tensor
+    of ``step_num``'s device and shape, torch ops on the current stream and no host read.  step_num: the simulator's
+    (E,) integer tensor of per-environment step counters, which restart with the episode.  The period is the
+    reference's expression, Python's ``round`` included (2.5 -> 2).  The result is the ``due`` of
+    ``compute_control_device`` and of ``BatchContext.interface_step_masked_device``."""
+    import torch
+
+    period = round(1 / (mpc_frequency * simulation_dt))
+    return (step_num % period == 0).to(torch.int32)
 
 
 class Batched_SRBDControllerInterface:
@@ -65,6 +83,7 @@ class Batched_SRBDControllerInterface:
         self.sigma_cem_mppi = (torch.full((E, P), self.sigma_reset_value, dtype=torch.float32, device=dev)
                                if self._cem else None)
         self.last_device_result = None
+        self._held_result = None  # the output dict the masked calls (due=) write their due rows into
 
     def _initial_keys(self) -> np.ndarray:
         """(E, 2) uint64: (seed, counter) on Philox; (packed JAX key, call count) on the JAX streams."""
@@ -76,7 +95,8 @@ class Batched_SRBDControllerInterface:
         return np.array([[k, c._calls] for k in packed], dtype=np.uint64)
 
     def compute_control_device(self, state_in, ref_in, contact_sequences, *, gait=None, optimize_swings=None,
-                               timings=None, nominal_step_frequencies=None, step_frequencies=None, stream=None):
+                               timings=None, nominal_step_frequencies=None, step_frequencies=None, due=None,
+                               stream=None):
         """One control step of every environment on torch tensors of the controller's device, enqueued on ``stream``
         (None: torch's current stream) without a host synchronisation.
 
@@ -88,6 +108,16 @@ class Batched_SRBDControllerInterface:
 
         ``num_sampling_iterations`` and ``sigma_cem_mppi`` are read from the configuration.  The interface's
         ``previous_contact_mpc``, ``keys``, ``best_control_parameters`` and ``sigma_cem_mppi`` are updated in place.
+
+        due None: every environment is stepped.  due an (E,) int32 or bool tensor of the controller's device
+        (``mpc_due``): only the environments it names are stepped (``srbd_batch_interface_step_masked_device``).  An
+        environment that is not due is neither written nor read -- its key does not advance, its warm start, sigma and
+        ``previous_contact_mpc`` row stay those of its last solve -- and the interface keeps one output dict for these
+        calls, so the returned tensors hold the last solve of the environments that are not due (zeros before an
+        environment's first solve) and are overwritten in place by the next ``due=`` call.  The ``costs`` rows of
+        environments that are not due are those of their last solve too.  The controller's ``_calls`` advances by
+        ``num_sampling_iterations`` per call whatever the mask holds -- it numbers the calls for the lazy costs; the
+        per-environment truth is ``keys``.
 
         Returns (GRFs (E, 12) float64, masked with the current contact; footholds (E, 12) float64; predicted states
         (E, 24) float32; best sample frequencies (E,); best costs (E,) float32; costs (E, N) lazy -- fetched to the
@@ -110,10 +140,15 @@ class Batched_SRBDControllerInterface:
             gait_io = ctx.make_gait_io(optimize_swings, c.step_freq_delta, c.dt, PGG_DUTY_FACTOR,
                                        pgg=getattr(gait, "state", gait), timings=timings,
                                        nominal_freqs=nominal_step_frequencies, freq_rows=step_frequencies)
-        out = ctx.interface_step_device(state_in, ref_in, contact_sequences, self.keys, self.previous_contact_mpc,
-                                        self.best_control_parameters, iterations=self.num_sampling_iterations,
-                                        sigma=self.sigma_cem_mppi, sigma_reset=self.sigma_reset_value,
-                                        gait_io=gait_io, stream=stream)
+        kw = dict(iterations=self.num_sampling_iterations, sigma=self.sigma_cem_mppi,
+                  sigma_reset=self.sigma_reset_value, gait_io=gait_io, stream=stream)
+        if due is None:
+            out = ctx.interface_step_device(state_in, ref_in, contact_sequences, self.keys, self.previous_contact_mpc,
+                                            self.best_control_parameters, **kw)
+        else:
+            out = self._held_result = ctx.interface_step_masked_device(
+                state_in, ref_in, contact_sequences, self.keys, self.previous_contact_mpc,
+                self.best_control_parameters, due, out=self._held_result, **kw)
         c._calls += self.num_sampling_iterations
         dev = self.keys.device
         s = torch.cuda.current_stream(dev) if stream is None else stream
@@ -131,7 +166,9 @@ class Batched_SRBDControllerInterface:
         """The full-horizon plan of the last ``compute_control_device`` call (``BatchContext.plan_device``): the
         updated best parameters rolled out from that call's prepared state and reference rows, with its contact rows
         and, gait-adaptive, its ``best_freq``.  The interface holds references to those tensors and copies nothing,
-        so call it before they are overwritten.  Enqueued on ``stream`` (None: torch's current stream).  Returns the
+        so call it before they are overwritten.  After a ``due=`` call the rows of an environment that was not due are
+        those of its last solve, and its plan is that solve's -- provided the caller's contact tensor still holds the
+        contact rows that solve saw.  Enqueued on ``stream`` (None: torch's current stream).  Returns the
         dict of ``plan_device``.  RuntimeError before the first step."""
         out = self.last_device_result
         if out is None:
