@@ -23,7 +23,7 @@
  *                                       write-back of WBInterface.compute_stance_and_swing_torque
  *                                       quadruped_pympc/helpers/swing_trajectory_controller.py:148-165
  *                                       quadruped_pympc/interfaces/wb_interface.py:354-358
- *   srbd_vfa_init / _mode / _commit / _reset
+ *   srbd_vfa_init / _mode / _commit / _reset / _height_search
  *                                    <- the apex gate of WBInterface.update_state_and_reference around the foothold
  *                                       search and VisualFootholdAdaptation's state
  *                                       quadruped_pympc/interfaces/wb_interface.py:230-246
@@ -327,7 +327,7 @@ int srbd_gait_apply_freq(srbd_pgg* pgg, srbd_frg* frg /* or NULL */, srbd_stc* s
  * Stale constraint: a search that finds no candidate for a leg leaves that leg's box as it was (the reference assigns
  * footholds_constraints only for a feasible leg, :209-228), so the box returned with valid 0 is the last feasible
  * search's, or NaN if there was none.  Neither the reset nor a pass-through touches boxes or valid.
- * Out of scope: the 'height' and 'vfa' strategies, the early-stance detector and inverse kinematics (start-and-stop
+ * Out of scope: the 'vfa' strategy, the early-stance detector and inverse kinematics (start-and-stop
  * is the gait generator's, srbd_pgg_start_stop above, and does not touch this state;
  * the per-environment masked reset of this and the loop's other state is srbd_loop_reset, below). */
 enum { SRBD_VFA_PASS = 0, SRBD_VFA_SEARCH = 1, SRBD_VFA_HOLD = 2 };
@@ -358,6 +358,16 @@ int srbd_vfa_mode(const srbd_vfa* g, const srbd_stc* stc, const double contact[4
 int srbd_vfa_commit(srbd_vfa* g, int32_t mode, const double seeds[12], const double searched_footholds[12],
                     const double searched_boxes[24], const int32_t searched_valid[4], double out_footholds[12],
                     double out_boxes[24], int32_t out_valid[4]);
+/* The 'height' strategy's search of one leg (visual_foothold_adaptation.py:145-151 with HeightMap.get_height): patch
+ * is the leg's rows x cols x 3 points (x, y, z), seed its reference foothold.  idx = the point with the smallest
+ * (x - seed[0]) * (x - seed[0]) + (y - seed[1]) * (y - seed[1]) (float64, unfused) under numpy.argmin's rule: the
+ * first minimum wins, and a NaN distance wins at its first occurrence.  foothold = (seed[0], seed[1], z[idx] + 0.02);
+ * *valid = 0 when that z is NaN (a ray that missed on a scene whose miss_z is NaN), else 1.  The strategy has no
+ * foothold constraints: the searched boxes handed to srbd_vfa_commit with this result are NaN.  csrc/srbd_vfa.h
+ * states the search once for this function and for the kernel of srbd_vfa_height_step_device (srbd_mpc.h).
+ * SRBD_E_INVALID (nothing written): a NULL pointer, rows or cols below 1, rows * cols above 320. */
+int srbd_vfa_height_search(const double* patch, int32_t rows, int32_t cols, const double seed[3], double foothold[3],
+                           int32_t* valid);
 
 /* ---- Velocity modulator, terrain estimator and the reference row's first twelve entries: what
  * WBInterface.update_state_and_reference builds every control step from the velocity command, before and after the

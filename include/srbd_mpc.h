@@ -865,7 +865,8 @@ int srbd_tamols_batch_device(srbd_terrain* terrain /* NULL: patch form */, const
  *   SRBD_E_INVALID (before any HIP call): everything srbd_tamols_batch_device refuses; a NULL d_vfa, d_stc or
  *   io->contact; an apex_interval that is not finite.  A failed launch: SRBD_E_HIP, or SRBD_E_NODEVICE where no device
  *   exists.
- *   Out of scope: the 'height' and 'vfa' strategies; the early-stance detector and inverse kinematics (start-and-stop
+ *   The 'height' strategy behind the same gate is srbd_vfa_height_step_device, below.
+ *   Out of scope: the 'vfa' strategy; the early-stance detector and inverse kinematics (start-and-stop
  *   is the gait generator's: srbd_pgg_start_stop_device and srbd_wb_update_device, below);
  *   compacting the searching environments into a smaller grid (their count would have to reach the host).  The
  *   per-environment masked reset of d_vfa and the loop's other device state is srbd_loop_reset_device, below. */
@@ -888,7 +889,12 @@ int srbd_vfa_step_device(struct srbd_vfa* d_vfa, const struct srbd_stc* d_stc, s
  *   pointing into those arrays.  The host arrays are not kept.  The set is immutable after creation.  No device:
  *   SRBD_E_NODEVICE; a failed allocation: SRBD_E_NOMEM; another failed HIP call: SRBD_E_HIP.
  *   srbd_terrain_set_last_error: the set's last message; NULL: the calling thread's last failed create, or its last
- *   call below refused for a NULL set.  srbd_terrain_set_num_scenes(NULL) is SRBD_E_INVALID,
+ *   call below refused for a NULL set.  Two conventions meet on this handle: the two searches here store an argument
+ *   refusal on the set, so they follow the handle to refuse; srbd_terrain_set_patches_device and
+ *   srbd_vfa_height_step_scenes_device (further below) refuse their arguments before they follow any handle and
+ *   store the message on the thread's slot, read with NULL -- after SRBD_E_INVALID from one of those two, the set's
+ *   own message is an older one (the shared-scene forms of those two do the same with srbd_terrain_last_error(NULL)).
+ *   srbd_terrain_set_num_scenes(NULL) is SRBD_E_INVALID,
  *   srbd_terrain_set_destroy(NULL) a no-op.
  *   srbd_tamols_batch_scenes_device is the terrain form of srbd_tamols_batch_device with environment e's rays cast
  *   against scene d_scene[e].  d_scene (num_envs int32) is the caller's device memory, read in stream order: a reset
@@ -938,6 +944,87 @@ int srbd_vfa_step_scenes_device(struct srbd_vfa* d_vfa, const struct srbd_stc* d
                                 const int32_t* d_scene /* E */, const srbd_tamols_params* params, int32_t num_envs,
                                 const srbd_tamols_batch_io* io, double apex_interval, int32_t* d_mode /* E, or NULL */,
                                 void* hip_stream);
+/* Device-resident height scans: the heightmap sensor of the batched loop.  K rows x cols patches per environment,
+ * raycast against the one scene all environments share (srbd_terrain_patches_device) or against scene d_scene[e] of a
+ * set (srbd_terrain_set_patches_device), device in and device out on the caller's stream -- what a policy trained or
+ * evaluated on the batched loop reads around the base or the feet, and what srbd_terrain_patches returns to the host.
+ *   Inputs: centers num_envs x K x 3 (z is not read), yaws num_envs (one per environment, as the sensor has), the
+ *   lattice (rows, cols, dist_x, dist_y) and ray_z shared by all patches.  Outputs, at least one of them: points
+ *   num_envs x K x rows x cols x 3 (x, y, z) and heights num_envs x K x rows x cols, which is points[..., 2].
+ *   Arithmetic: patch point (i, j), its coordinates and its ray are srbd_terrain_patches's (csrc/terrain_ray.h,
+ *   float64, unfused); the yaw's cos / sin are formed on the device, correctly rounded (csrc/yaw_sincos.h), as
+ *   srbd_tamols_batch_device forms them.
+ *   Equivalence: every output of environment e holds the bytes heightmaps_out of srbd_tamols_batch_scenes_device
+ *   (srbd_tamols_batch_device for the shared scene) holds for the same centres as seeds, the same yaw and lattice; for
+ *   a yaw whose libm cos / sin equal srbd_selftest_yaw_sincos's it also holds the bytes srbd_terrain_patches returns on
+ *   a srbd_terrain created from that scene.  "The bytes" as in the calls above: NaNs position for position (a NaN's
+ *   sign and payload are not part of the contract).  Environments are independent: a NaN centre or yaw in one changes
+ *   nothing in another.
+ *   d_scene is read in stream order; an index outside 0..num_scenes-1 runs on the empty scene (no ground,
+ *   no primitives, no height field, miss_z NaN) and nothing is read out of bounds.
+ *   Launch shape: grid (K, num_envs), one block per (patch, environment) of rows * cols threads rounded up to whole
+ *   waves (at most 320), one thread per ray; block (k, e) reads d_scene[e] once, bounds-checks it and copies the
+ *   scene's record into LDS; heights are written as consecutive 8-byte stores.
+ *   Enqueue contract (the producers' above): exactly one launch on hip_stream, no synchronising HIP call, no device
+ *   memory touched from the host; the stream handle is read as srbd_prepare_state_device reads it; every pointer is
+ *   memory of the current device, which must be the terrain's or the set's; they must outlive the launch.
+ *   SRBD_E_INVALID (before any HIP call, with a message naming the argument -- read it with
+ *   srbd_terrain_last_error(NULL) / srbd_terrain_set_last_error(NULL): the handle is not followed before the arguments
+ *   have passed): a NULL terrain, set, d_scene, io, centers or yaws; both outputs NULL; num_envs outside 1..4096;
+ *   patches_per_env outside 1..16; rows or cols below 1 or rows * cols above 320; a dist_x or dist_y that is not
+ *   positive and finite; a ray_z that is not finite; a d_scene that is not 4-byte aligned.  A failed launch:
+ *   SRBD_E_HIP, or SRBD_E_NODEVICE where no device exists.
+ *   Out of scope: per-environment lattices, float32 outputs, graph capture. */
+typedef struct srbd_patch_batch_io {
+    const double* centers;   /* E x K x 3, device */
+    const double* yaws;      /* E, device: one yaw per environment, as the sensor has */
+    int32_t patches_per_env; /* K, 1..16 */
+    int32_t rows, cols;      /* rows * cols 1..320, as srbd_tamols_batch_device */
+    double dist_x, dist_y, ray_z;
+    double* points;          /* E x K x rows x cols x 3 (x, y, z), or NULL */
+    double* heights;         /* E x K x rows x cols (z only), or NULL; at least one of the two */
+} srbd_patch_batch_io;
+int srbd_terrain_patches_device(srbd_terrain* terrain, int32_t num_envs, const srbd_patch_batch_io* io,
+                                void* hip_stream);
+int srbd_terrain_set_patches_device(srbd_terrain_set* set, const int32_t* d_scene /* E */, int32_t num_envs,
+                                    const srbd_patch_batch_io* io, void* hip_stream);
+/* The 'height' strategy behind the apex gate (VisualFootholdAdaptation.compute_adaptation, strategy 'height',
+ * visual_foothold_adaptation.py:145-151, inside wb_interface.py:230-246): srbd_vfa_step_device with another search --
+ * a searching leg's foothold is its seed with z = the height of the nearest point of the leg's raycast patch + 0.02
+ * (srbd_vfa_height_search of srbd_host.h is the host twin; csrc/srbd_vfa.h states it once for both).  The state is the
+ * same srbd_vfa, the gate the same, so srbd_loop_reset_device resets it as before and an environment may be stepped by
+ * either strategy.
+ *   io is srbd_tamols_batch_device's struct.  Read: seeds, contact (required), yaws, rows, cols, dist_x, dist_y, ray_z.
+ *   Written: footholds, boxes, valid, ref's entries 12..23 (what get_footholds_adapted returns), and for searching
+ *   environments only seed_heights (the foothold's z) and heightmaps_out (the leg's patch: the bytes
+ *   srbd_terrain_patches_device writes for the seed as centre).  hips, forward_vel, base_pos, feet and scores are
+ *   ignored and may be NULL.  There is no patch form: io->heightmaps is refused.
+ *   Boxes: the strategy has no foothold constraints, so the searched box is NaN, and the call inherits
+ *   srbd_vfa_commit's rule for it -- a leg whose ray hit (valid 1) stores the NaN box, a leg whose nearest point is a
+ *   miss on a scene with miss_z NaN (foothold z NaN, valid 0) keeps the box its state held (NaN after srbd_vfa_init;
+ *   an older TAMOLS box if the state came from that strategy).
+ *   Launch shape: grid (4 legs, num_envs), rows * cols threads rounded up to whole waves.  The gate, the read-once rule
+ *   for initialized[leg] and the HOLD / PASS early exit are srbd_vfa_step_device's; a SEARCH block casts one ray per
+ *   thread and reduces the argmin with wave shuffles and then LDS, the lowest index winning ties (numpy.argmin's rule:
+ *   the first minimum, a NaN distance at its first occurrence), without atomics.
+ *   Equivalence: environment e does what srbd_vfa_mode, then -- in SEARCH -- srbd_vfa_height_search on the four patches
+ *   srbd_terrain_patches_device returns for its seeds, then srbd_vfa_commit with NaN boxes do on a host srbd_vfa with
+ *   d_vfa[e]'s bytes: d_vfa[e], every output row and d_mode[e] hold the host's bytes (NaNs position for position).
+ *   Environments are independent,
+ *   and a non-searching environment reads neither its yaw, its scene index nor the scene.
+ *   Enqueue contract: srbd_vfa_step_device's.
+ *   SRBD_E_INVALID (before any HIP call, with a message as above): a NULL terrain, set, d_scene, d_vfa, d_stc, io,
+ *   io->contact, io->seeds, io->footholds, io->boxes, io->valid or io->yaws; an apex_interval that is not finite;
+ *   num_envs outside 1..4096; rows or cols below 1 or rows * cols above 320; a dist_x or dist_y that is not positive;
+ *   io->heightmaps given; a d_scene that is not 4-byte aligned.
+ *   Out of scope: a patch form; the 'vfa' strategy; compacting the searching environments into a smaller grid. */
+int srbd_vfa_height_step_device(struct srbd_vfa* d_vfa, const struct srbd_stc* d_stc, srbd_terrain* terrain,
+                                int32_t num_envs, const srbd_tamols_batch_io* io, double apex_interval,
+                                int32_t* d_mode /* E, or NULL */, void* hip_stream);
+int srbd_vfa_height_step_scenes_device(struct srbd_vfa* d_vfa, const struct srbd_stc* d_stc, srbd_terrain_set* set,
+                                       const int32_t* d_scene /* E */, int32_t num_envs,
+                                       const srbd_tamols_batch_io* io, double apex_interval,
+                                       int32_t* d_mode /* E, or NULL */, void* hip_stream);
 /* Self-test: out_cs[2 i], out_cs[2 i + 1] = the cos and sin srbd_tamols_batch_device's kernel forms of yaws[i],
  * evaluated on the host by the same function (plain float64 operations and fma: the same bits on both sides). */
 int srbd_selftest_yaw_sincos(const double* yaws, int32_t n, double* out_cs);

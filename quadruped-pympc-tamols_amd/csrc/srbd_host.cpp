@@ -364,6 +364,15 @@ extern "C" int srbd_vfa_commit(srbd_vfa* g, int32_t mode, const double seeds[12]
     return SRBD_OK;
 }
 
+extern "C" int srbd_vfa_height_search(const double* patch, int32_t rows, int32_t cols, const double seed[3],
+                                      double foothold[3], int32_t* valid) {  // VFA:145-151, PatchHeightMap.get_height
+    if (!patch || !seed || !foothold || !valid || rows < 1 || cols < 1 || (int64_t)rows * cols > 320)
+        return SRBD_E_INVALID;
+    const int i = srbd::vfa_height_nearest(patch, rows * cols, seed[0], seed[1]);
+    srbd::vfa_height_result(seed[0], seed[1], patch[3 * i + 2], foothold, valid);
+    return SRBD_OK;
+}
+
 // ------------------------------------------- per-environment reset of the loop's state (srbd_reset.h)
 extern "C" int srbd_loop_reset(int32_t level, const double initial_feet[12], srbd_pgg* pgg, srbd_frg* frg,
                                srbd_stc* stc, srbd_terrain_est* terrain_est, srbd_vfa* vfa,

@@ -409,6 +409,50 @@ struct TamolsBatchScenesJob : TamolsBatchJob {
 };
 void launch_tamols_batch_scenes(const TamolsBatchScenesJob& j, bool gated, hipStream_t s);
 
+// The error text of a call on a scene (t == NULL: what srbd_terrain_last_error(NULL) returns).
+int terrain_fail(srbd_terrain* t, int code, const std::string& message);
+
+// Device-resident height scans (srbd_terrain_patches_device / srbd_terrain_set_patches_device; terrain_kernel.hip
+// terrain_patch_batch_kernel): K patches per environment, one block per (patch, environment), one lane per ray.
+// table != NULL: environment e's rays go against table[scene[e]] (the empty scene for an index outside the set),
+// else against `t`.
+constexpr int PATCH_BATCH_MAX_RAYS = 320;  // TAMOLS_MAXCAND: the lattice limit of srbd_tamols_batch_device
+constexpr int PATCH_BATCH_MAX_K = 16;
+struct PatchBatchJob {
+    const double* centers;  // E x K x 3
+    const double* yaws;     // E
+    double* points;         // E x K x rows x cols x 3, or NULL
+    double* heights;        // E x K x rows x cols, or NULL
+    TerrainDev t;
+    const TerrainDev* table;
+    const int32_t* scene;
+    int32_t num_scenes;
+    int E, K, rows, cols;
+    double dist_x, dist_y, ray_z;
+};
+void launch_patch_batch(const PatchBatchJob& j, hipStream_t s);
+
+// The 'height' strategy behind the apex gate (srbd_vfa_height_step_device / _scenes_device; vfa_height_kernel.hip):
+// srbd_vfa_step_device's grid (4 legs x E) and gate; a SEARCH block casts its leg's rows x cols rays around the seed,
+// one lane each, and takes the nearest point's height (srbd_vfa.h vfa_height_*).  Scenes as in PatchBatchJob.
+struct VfaHeightJob {
+    const double *seeds, *yaws;
+    const float* contact;
+    double *footholds, *boxes, *seed_heights, *hm_out, *ref;
+    int32_t* valid;
+    TerrainDev t;
+    const TerrainDev* table;
+    const int32_t* scene;
+    int32_t num_scenes;
+    int E, rows, cols;
+    double dist_x, dist_y, ray_z;
+    srbd_vfa* vfa;
+    const srbd_stc* stc;
+    int32_t* mode;
+    double apex_interval;
+};
+void launch_vfa_height(const VfaHeightJob& j, hipStream_t s);
+
 // The per-environment reset of the loop's device state (srbd_loop_reset_device; srbd_producers.hip
 // loop_reset_kernel): the arrays of one call (include/srbd_mpc.h srbd_loop_reset_io), E entries each.  One wave per
 // environment, LOOP_RESET_WAVES of them per block.

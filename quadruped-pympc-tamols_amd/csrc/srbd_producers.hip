@@ -1224,6 +1224,169 @@ extern "C" int srbd_vfa_step_scenes_device(srbd_vfa* d_vfa, const srbd_stc* d_st
     return launch_status();
 }
 
+// ------------------------------------------------------------------ device-resident height scans, 'height' footholds
+namespace {
+
+// The lattice both calls share (rows, cols, dist_x, dist_y); NULL: accepted.  finite_dist: the scans ask for finite
+// spacings, the gated step for what srbd_vfa_step_device asks.
+const char* lattice_refused(int32_t rows, int32_t cols, double dist_x, double dist_y, bool finite_dist) {
+    if (rows < 1) return "rows must be at least 1";
+    if (cols < 1) return "cols must be at least 1";
+    if ((int64_t)rows * cols > PATCH_BATCH_MAX_RAYS) return "rows * cols must be at most 320";
+    if (!(dist_x > 0.0) || (finite_dist && !std::isfinite(dist_x)))
+        return finite_dist ? "dist_x must be positive and finite" : "dist_x must be positive";
+    if (!(dist_y > 0.0) || (finite_dist && !std::isfinite(dist_y)))
+        return finite_dist ? "dist_y must be positive and finite" : "dist_y must be positive";
+    return nullptr;
+}
+
+const char* patch_io_refused(int32_t num_envs, const srbd_patch_batch_io* io) {
+    if (!io) return "null io";
+    if (!io->centers) return "null io->centers";
+    if (!io->yaws) return "null io->yaws";
+    if (!io->points && !io->heights) return "io->points and io->heights are both null";
+    if (!envs_ok(num_envs)) return "num_envs must be 1..4096";
+    if (io->patches_per_env < 1 || io->patches_per_env > PATCH_BATCH_MAX_K) return "io->patches_per_env must be 1..16";
+    if (const char* why = lattice_refused(io->rows, io->cols, io->dist_x, io->dist_y, true)) return why;
+    if (!std::isfinite(io->ray_z)) return "ray_z must be finite";
+    return nullptr;
+}
+
+PatchBatchJob patch_job(int32_t num_envs, const srbd_patch_batch_io* io) {
+    PatchBatchJob j = {};
+    j.centers = io->centers;
+    j.yaws = io->yaws;
+    j.points = io->points;
+    j.heights = io->heights;
+    j.E = num_envs;
+    j.K = io->patches_per_env;
+    j.rows = io->rows;
+    j.cols = io->cols;
+    j.dist_x = io->dist_x;
+    j.dist_y = io->dist_y;
+    j.ray_z = io->ray_z;
+    return j;
+}
+
+bool on_current_device(int device) {
+    int cur = -1;
+    return hipGetDevice(&cur) != hipSuccess || cur == device;  // no device: the launch reports it
+}
+
+// What the two 'height' steps refuse of the arguments they share (NULL: nothing).
+const char* height_step_refused(const srbd_vfa* d_vfa, const srbd_stc* d_stc, int32_t num_envs,
+                                const srbd_tamols_batch_io* io, double apex_interval) {
+    if (!d_vfa) return "null d_vfa";
+    if (!d_stc) return "null d_stc";
+    if (!io) return "null io";
+    if (!io->contact) return "null io->contact";
+    if (!std::isfinite(apex_interval)) return "apex_interval must be finite";
+    if (!io->seeds) return "null io->seeds";
+    if (!io->footholds) return "null io->footholds";
+    if (!io->boxes) return "null io->boxes";
+    if (!io->valid) return "null io->valid";
+    if (!envs_ok(num_envs)) return "num_envs must be 1..4096";
+    if (io->heightmaps) return "io->heightmaps given: the 'height' step has no patch form";
+    if (!io->yaws) return "null io->yaws";
+    return lattice_refused(io->rows, io->cols, io->dist_x, io->dist_y, false);
+}
+
+VfaHeightJob height_job(srbd_vfa* d_vfa, const srbd_stc* d_stc, int32_t num_envs, const srbd_tamols_batch_io* io,
+                        double apex_interval, int32_t* d_mode) {
+    VfaHeightJob j = {};
+    j.seeds = io->seeds;
+    j.yaws = io->yaws;
+    j.contact = io->contact;
+    j.footholds = io->footholds;
+    j.boxes = io->boxes;
+    j.valid = io->valid;
+    j.seed_heights = io->seed_heights;
+    j.hm_out = io->heightmaps_out;
+    j.ref = io->ref;
+    j.E = num_envs;
+    j.rows = io->rows;
+    j.cols = io->cols;
+    j.dist_x = io->dist_x;
+    j.dist_y = io->dist_y;
+    j.ray_z = io->ray_z;
+    j.vfa = d_vfa;
+    j.stc = d_stc;
+    j.mode = d_mode;
+    j.apex_interval = apex_interval;
+    return j;
+}
+
+}  // namespace
+
+// An argument refusal leaves its message where srbd_terrain_last_error(NULL) / srbd_terrain_set_last_error(NULL) read it:
+// the handle is not followed before the arguments have passed.
+extern "C" int srbd_terrain_patches_device(srbd_terrain* terrain, int32_t num_envs, const srbd_patch_batch_io* io,
+                                           void* hip_stream) {
+    const std::string w = "srbd_terrain_patches_device: ";
+    if (!terrain) return terrain_fail(nullptr, SRBD_E_INVALID, w + "null terrain");
+    if (const char* why = patch_io_refused(num_envs, io)) return terrain_fail(nullptr, SRBD_E_INVALID, w + why);
+    if (!on_current_device(terrain->device))
+        return terrain_fail(terrain, SRBD_E_INVALID, w + "the terrain is not on the current device");
+    PatchBatchJob j = patch_job(num_envs, io);
+    j.t = terrain->dev;
+    launch_patch_batch(j, stream_of(hip_stream));
+    return launch_status();
+}
+
+extern "C" int srbd_terrain_set_patches_device(srbd_terrain_set* set, const int32_t* d_scene, int32_t num_envs,
+                                               const srbd_patch_batch_io* io, void* hip_stream) {
+    const std::string w = "srbd_terrain_set_patches_device: ";
+    if (!set) return terrain_set_fail(nullptr, SRBD_E_INVALID, w + "null set");
+    if (!d_scene) return terrain_set_fail(nullptr, SRBD_E_INVALID, w + "null d_scene");
+    if (reinterpret_cast<uintptr_t>(d_scene) % alignof(int32_t))
+        return terrain_set_fail(nullptr, SRBD_E_INVALID, w + "d_scene is not 4-byte aligned");
+    if (const char* why = patch_io_refused(num_envs, io)) return terrain_set_fail(nullptr, SRBD_E_INVALID, w + why);
+    if (!on_current_device(set->device))
+        return terrain_set_fail(set, SRBD_E_INVALID, w + "the set is not on the current device");
+    PatchBatchJob j = patch_job(num_envs, io);
+    j.table = set->d_table;
+    j.scene = d_scene;
+    j.num_scenes = set->num_scenes;
+    launch_patch_batch(j, stream_of(hip_stream));
+    return launch_status();
+}
+
+extern "C" int srbd_vfa_height_step_device(srbd_vfa* d_vfa, const srbd_stc* d_stc, srbd_terrain* terrain,
+                                           int32_t num_envs, const srbd_tamols_batch_io* io, double apex_interval,
+                                           int32_t* d_mode, void* hip_stream) {
+    const std::string w = "srbd_vfa_height_step_device: ";
+    if (!terrain) return terrain_fail(nullptr, SRBD_E_INVALID, w + "null terrain");
+    if (const char* why = height_step_refused(d_vfa, d_stc, num_envs, io, apex_interval))
+        return terrain_fail(nullptr, SRBD_E_INVALID, w + why);
+    if (!on_current_device(terrain->device))
+        return terrain_fail(terrain, SRBD_E_INVALID, w + "the terrain is not on the current device");
+    VfaHeightJob j = height_job(d_vfa, d_stc, num_envs, io, apex_interval, d_mode);
+    j.t = terrain->dev;
+    launch_vfa_height(j, stream_of(hip_stream));
+    return launch_status();
+}
+
+extern "C" int srbd_vfa_height_step_scenes_device(srbd_vfa* d_vfa, const srbd_stc* d_stc, srbd_terrain_set* set,
+                                                  const int32_t* d_scene, int32_t num_envs,
+                                                  const srbd_tamols_batch_io* io, double apex_interval,
+                                                  int32_t* d_mode, void* hip_stream) {
+    const std::string w = "srbd_vfa_height_step_scenes_device: ";
+    if (!set) return terrain_set_fail(nullptr, SRBD_E_INVALID, w + "null set");
+    if (!d_scene) return terrain_set_fail(nullptr, SRBD_E_INVALID, w + "null d_scene");
+    if (reinterpret_cast<uintptr_t>(d_scene) % alignof(int32_t))
+        return terrain_set_fail(nullptr, SRBD_E_INVALID, w + "d_scene is not 4-byte aligned");
+    if (const char* why = height_step_refused(d_vfa, d_stc, num_envs, io, apex_interval))
+        return terrain_set_fail(nullptr, SRBD_E_INVALID, w + why);
+    if (!on_current_device(set->device))
+        return terrain_set_fail(set, SRBD_E_INVALID, w + "the set is not on the current device");
+    VfaHeightJob j = height_job(d_vfa, d_stc, num_envs, io, apex_interval, d_mode);
+    j.table = set->d_table;
+    j.scene = d_scene;
+    j.num_scenes = set->num_scenes;
+    launch_vfa_height(j, stream_of(hip_stream));
+    return launch_status();
+}
+
 extern "C" int srbd_loop_reset_device(int32_t num_envs, const srbd_loop_reset_io* io, void* hip_stream) {
     if (!envs_ok(num_envs)) return fail_global(SRBD_E_INVALID, "srbd_loop_reset_device: num_envs must be 1..4096");
     if (!io) return fail_global(SRBD_E_INVALID, "srbd_loop_reset_device: null io");

@@ -21,7 +21,10 @@
 // Stale constraint: VFA:209-222 assigns footholds_constraints[leg] only for a leg with a feasible candidate, and
 // neither reset nor get_footholds_adapted touches it, so an infeasible leg keeps the box of its last feasible search
 // (NaN here where the reference still holds None) while its foothold is the seed at its terrain height (VFA:223-228).
-// Out of scope: the 'height' and 'vfa' strategies; the early-stance detector and inverse kinematics (start-and-stop is
+// The 'height' strategy's search (VFA:145-151: each seed's z becomes its patch's nearest-point height + 0.02) is stated
+// here too, vfa_height_*, for the host twin srbd_vfa_height_search and the kernel of srbd_vfa_height_step_device
+// (vfa_height_kernel.hip): the gate and the commit around it are the ones above.
+// Out of scope: the 'vfa' strategy; the early-stance detector and inverse kinematics (start-and-stop is
 // the gait generator's, srbd_start_stop.h);
 // compacting the searching environments into a smaller grid (the count would have to reach the host).  The
 // per-environment reset of this state is srbd_reset.h's.
@@ -92,6 +95,48 @@ YAW_HD inline bool vfa_mode_ok(int32_t mode) {
 YAW_HD inline bool vfa_struct_ok(const srbd_vfa* g) {
     return g->initialized[0] == g->initialized[1] && g->initialized[0] == g->initialized[2] &&
            g->initialized[0] == g->initialized[3];
+}
+
+// ---- the 'height' strategy: the seed at the height of its patch's nearest point (PatchHeightMap.get_height)
+// Squared xy distance of patch point (x, y) from the seed (sx, sy): float64, unfused, the one expression both sides
+// evaluate.
+YAW_HD inline double vfa_height_d2(double x, double y, double sx, double sy) {
+#pragma clang fp contract(off)
+    const double dx = x - sx, dy = y - sy;
+    return dx * dx + dy * dy;
+}
+
+// numpy.argmin's order on (distance, index) pairs: does (da, ia) come before (db, ib)?  A NaN distance comes before
+// every number, and among equals (two NaNs, two equal numbers) the lower index: a total order, so the minimum may be
+// folded in any grouping -- the host's serial scan and the kernel's wave shuffles find the same point.
+YAW_HD inline bool vfa_height_before(double da, int ia, double db, int ib) {
+    const bool na = da != da, nb = db != db;
+    if (na != nb) return na;
+    if (na) return ia < ib;
+    return da < db || (da == db && ia < ib);
+}
+
+// The index of the nearest of a patch's n points (x, y, z triples) to the seed, serially.
+YAW_HD inline int vfa_height_nearest(const double* patch, int n, double sx, double sy) {
+    int bi = 0;
+    double bd = vfa_height_d2(patch[0], patch[1], sx, sy);
+    for (int i = 1; i < n; ++i) {
+        const double d = vfa_height_d2(patch[3 * i], patch[3 * i + 1], sx, sy);
+        if (vfa_height_before(d, i, bd, bi)) {
+            bd = d;
+            bi = i;
+        }
+    }
+    return bi;
+}
+
+// The leg's foothold from its nearest point's height z: the seed's x and y, z + 0.02; a ray that missed on a scene
+// whose miss_z is NaN gives a NaN height and valid 0.
+YAW_HD inline void vfa_height_result(double sx, double sy, double z, double* foothold, int32_t* valid) {
+    foothold[0] = sx;
+    foothold[1] = sy;
+    foothold[2] = z + 0.02;
+    *valid = z != z ? 0 : 1;
 }
 
 }  // namespace srbd

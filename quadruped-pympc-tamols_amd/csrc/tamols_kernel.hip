@@ -759,10 +759,7 @@ static_assert(sizeof(srbd_tamols_params) % sizeof(double) == 0 && offsetof(Tamol
 // set's concatenated arrays, so the cull, the field walk and the walk of the whole scene index from zero as before.
 // Behind the gate, so a HOLD or PASS block reads neither its index nor the set.  The two instantiations without
 // SCENES compile to the code they had.
-constexpr int TERRAIN_DEV_WORDS = (int)(sizeof(TerrainDev) / 8);
-static_assert(sizeof(TerrainDev) % 8 == 0 && offsetof(TerrainDev, miss_z) % 8 == 0 && TERRAIN_DEV_WORDS <= 64,
-              "the scene's record is copied as 8-byte words, one per lane of wave 3");
-typedef uint64_t __attribute__((may_alias)) record_word;
+// (the copy itself: terrain_ray.h scene_record_load, shared with the height scans and the 'height' step)
 // The body is a device function the kernels below wrap, inlined into each: written as the kernel template itself, the
 // gated SCENES instantiation crashes the compiler's optimizer (ROCm 7.2, infer-address-spaces inside the inliner's
 // call-graph walk), and the wrapped form compiles the two shared-scene kernels to the registers, scratch and LDS
@@ -867,14 +864,8 @@ __device__ __forceinline__ void tamols_batch_body(const TamolsBatchArg<SCENES>& 
         j.lattice = 0;
     }
     if constexpr (SCENES) {
-        if (tid >= 192 && tid < 192 + TERRAIN_DEV_WORDS) {
-            const int k = tid - 192;
-            const int32_t sid = __builtin_amdgcn_readfirstlane(bj.scene[e]);  // block-uniform; tells the compiler so
-            // an index outside the set: no ground, no primitives, no height field (all words zero), miss_z NaN
-            record_word w = k == (int)(offsetof(TerrainDev, miss_z) / 8) ? 0x7ff8000000000000ull : 0ull;
-            if ((uint32_t)sid < (uint32_t)bj.num_scenes) w = reinterpret_cast<const record_word*>(bj.table + sid)[k];
-            reinterpret_cast<record_word*>(&j.t)[k] = w;
-        }
+        if (tid >= 192 && tid < 192 + SCENE_RECORD_WORDS)
+            scene_record_load(bj.table, bj.scene, bj.num_scenes, e, tid - 192, &j.t);
     }
     __syncthreads();
 

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "terrain_ray.h"
+#include "yaw_sincos.h"
 
 namespace srbd {
 
@@ -30,13 +31,68 @@ void launch_terrain_patches(const TerrainDev& t, const PatchJob& j, hipStream_t 
     hipLaunchKernelGGL(terrain_patch_kernel, dim3((n + 255) / 256), dim3(256), 0, s, t, j);
 }
 
+// ------------------------------------------------------------------ device-resident height scans
+// srbd_terrain_patches_device / srbd_terrain_set_patches_device: grid (K patches, E environments), one lane per ray.
+// Wave 0 prepares what the block's rays share -- the yaw's cos / sin (yaw_sincos.h, one lane: the bits
+// srbd_tamols_batch_device's kernel forms) and, SCENES, the environment's scene: scene[e] read once, bounds-checked,
+// the record's 8-byte words copied into LDS or the empty scene's formed there (terrain_ray.h scene_record_load) -- and
+// every lane then casts terrain_ray_point's ray, so a point holds the bytes terrain_patch_kernel and the TAMOLS
+// launches write for the same centre, yaw and lattice.  Every ray walks the whole scene: the primitive loads are block-uniform.
+static_assert(PATCH_BATCH_MAX_RAYS == TAMOLS_MAXCAND, "one lattice limit for the scans and the searches");
+
+template <bool SCENES>
+__global__ void __launch_bounds__(PATCH_BATCH_MAX_RAYS) terrain_patch_batch_kernel(const PatchBatchJob j) {
+    __shared__ TerrainDev lt;
+    __shared__ double cs[2];
+    const int k = blockIdx.x, e = blockIdx.y, tid = threadIdx.x;
+    if (SCENES && tid < SCENE_RECORD_WORDS) {
+        scene_record_load(j.table, j.scene, j.num_scenes, e, tid, &lt);
+    } else if (tid == SCENE_RECORD_WORDS) {  // the next lane of wave 0
+        yaw_sincos(j.yaws[e], cs[0], cs[1]);
+    }
+    __syncthreads();
+    const int nc = j.rows * j.cols;
+    if (tid >= nc) return;
+    TerrainDev trec;
+    const TerrainDev* scene_rec = &j.t;
+    if constexpr (SCENES) {  // out of LDS into registers
+        trec = lt;
+        scene_rec = &trec;
+    }
+    const double* c = j.centers + 3 * ((size_t)e * j.K + k);
+    const size_t at = ((size_t)e * j.K + k) * nc + tid;
+    if (j.points && !j.heights) {  // straight to the caller's array, as terrain_patch_kernel
+        terrain_ray_point(*scene_rec, c[0], c[1], cs[0], cs[1], j.rows, j.cols, tid / j.cols, tid % j.cols, j.dist_x,
+                          j.dist_y, j.ray_z, j.points + 3 * at);
+        return;
+    }
+    double o[3];
+    terrain_ray_point(*scene_rec, c[0], c[1], cs[0], cs[1], j.rows, j.cols, tid / j.cols, tid % j.cols, j.dist_x,
+                      j.dist_y, j.ray_z, o);
+    if (j.points) {
+        double* p = j.points + 3 * at;
+        p[0] = o[0];
+        p[1] = o[1];
+        p[2] = o[2];
+    }
+    j.heights[at] = o[2];  // consecutive lanes, consecutive doubles
+}
+
+void launch_patch_batch(const PatchBatchJob& j, hipStream_t s) {
+    const int threads = (j.rows * j.cols + 63) / 64 * 64;  // whole waves, at most PATCH_BATCH_MAX_RAYS
+    if (j.table)
+        hipLaunchKernelGGL(terrain_patch_batch_kernel<true>, dim3(j.K, j.E), dim3(threads), 0, s, j);
+    else
+        hipLaunchKernelGGL(terrain_patch_batch_kernel<false>, dim3(j.K, j.E), dim3(threads), 0, s, j);
+}
+
 }  // namespace srbd
 
 using namespace srbd;
 
 static std::string g_terrain_error;
 
-static int terrain_fail(srbd_terrain* t, int code, const std::string& m) {
+int srbd::terrain_fail(srbd_terrain* t, int code, const std::string& m) {
     (t ? t->err : g_terrain_error) = m;
     return code;
 }

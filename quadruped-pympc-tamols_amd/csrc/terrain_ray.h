@@ -110,4 +110,21 @@ __device__ __forceinline__ void terrain_ray_point(const TerrainDev& t, double cx
     o[2] = hit ? best : t.miss_z;
 }
 
+// One scene per environment: environment e's record out of a set's table into `dst` (LDS), one 8-byte word per lane.
+// The SCENE_RECORD_WORDS lanes that call it (lane = 0 .. SCENE_RECORD_WORDS - 1, in one wave) read scene[e] -- one
+// load, block-uniform --, bounds-check it and copy table[scene[e]]'s words; an index outside 0..num_scenes-1 gives the
+// empty scene instead: no ground, no primitives, no height field (all words zero), miss_z NaN.  Nothing is read out of
+// bounds.  The caller's barrier publishes `dst`.
+constexpr int SCENE_RECORD_WORDS = (int)(sizeof(TerrainDev) / 8);
+static_assert(sizeof(TerrainDev) % 8 == 0 && offsetof(TerrainDev, miss_z) % 8 == 0 && SCENE_RECORD_WORDS < 64,
+              "the scene's record is copied as 8-byte words, one per lane of one wave");
+typedef uint64_t __attribute__((may_alias)) scene_record_word;
+__device__ __forceinline__ void scene_record_load(const TerrainDev* table, const int32_t* scene, int32_t num_scenes,
+                                                  int e, int lane, TerrainDev* dst) {
+    const int32_t sid = __builtin_amdgcn_readfirstlane(scene[e]);  // block-uniform; tells the compiler so
+    scene_record_word w = lane == (int)(offsetof(TerrainDev, miss_z) / 8) ? 0x7ff8000000000000ull : 0ull;
+    if ((uint32_t)sid < (uint32_t)num_scenes) w = reinterpret_cast<const scene_record_word*>(table + sid)[lane];
+    reinterpret_cast<scene_record_word*>(dst)[lane] = w;
+}
+
 }  // namespace srbd

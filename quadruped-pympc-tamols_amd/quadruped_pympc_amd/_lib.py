@@ -172,6 +172,14 @@ class TamolsBatchIO(C.Structure):
     ]
 
 
+class PatchBatchIO(C.Structure):
+    """srbd_patch_batch_io (include/srbd_mpc.h): the device arrays of one srbd_terrain_patches_device call."""
+    _fields_ = [
+        ("centers", _P), ("yaws", _P), ("patches_per_env", _I), ("rows", _I), ("cols", _I), ("dist_x", _D),
+        ("dist_y", _D), ("ray_z", _D), ("points", _P), ("heights", _P),
+    ]
+
+
 SIGNATURES = {
     "srbd_num_params": (_I, [C.POINTER(SrbdConfig)]),
     "srbd_device_count": (_I, [_IP]),
@@ -463,6 +471,12 @@ SIGNATURES.update({
     "srbd_tamols_batch_scenes_device": (_I, [_P, _P, C.POINTER(TamolsParams), _I, C.POINTER(TamolsBatchIO), _P]),
     "srbd_vfa_step_scenes_device": (_I, [_P, _P, _P, _P, C.POINTER(TamolsParams), _I, C.POINTER(TamolsBatchIO), _D,
                                          _P, _P]),
+    # device-resident height scans and the 'height' strategy behind the gate (and its host twin)
+    "srbd_terrain_patches_device": (_I, [_P, _I, C.POINTER(PatchBatchIO), _P]),
+    "srbd_terrain_set_patches_device": (_I, [_P, _P, _I, C.POINTER(PatchBatchIO), _P]),
+    "srbd_vfa_height_step_device": (_I, [_P, _P, _P, _I, C.POINTER(TamolsBatchIO), _D, _P, _P]),
+    "srbd_vfa_height_step_scenes_device": (_I, [_P, _P, _P, _P, _I, C.POINTER(TamolsBatchIO), _D, _P, _P]),
+    "srbd_vfa_height_search": (_I, [_DP, _I, _I, _DP, _DP, _IP]),
     # the per-environment reset of the loop's state: the host call and its device form
     "srbd_loop_reset": (_I, [_I, _DP, C.POINTER(SrbdPgg), C.POINTER(SrbdFrg), C.POINTER(SrbdStc),
                              C.POINTER(SrbdTerrainEst), C.POINTER(SrbdVfa), C.POINTER(SrbdPgg), C.POINTER(SrbdFrg),
@@ -1854,19 +1868,20 @@ def _tamols_batch_enqueue(native, what, seeds, hips, params, *, terrain=None, ya
                           cols=7, dist_x=0.04, dist_y=0.04, ray_z=10.0, forward_vel=None, base_pos=None, contact=None,
                           feet=None, ref=None, out=None, want_seed_heights=False, want_scores=False,
                           want_heightmaps=False, stream=None, extra_inputs=lambda E: (), extra_outputs=lambda E: (),
-                          scene_ids=None):
+                          scene_ids=None, search_inputs=True):
     """What ``tamols_batch_device`` and ``vfa_step_device`` share: the checks of the search's tensors, its outputs and
     its srbd_tamols_batch_io.  ``native(terrain_handle, params, E, io, outputs, stream)`` makes the C call ``what``
     (when ``terrain`` is a GpuTerrainSet, ``native`` gets the ``scene_ids`` pointer as a seventh argument and makes the
     scenes call);
     ``extra_inputs(E)`` yields further (name, tensor, shape, dtypes) to check, ``extra_outputs(E)`` further
-    (name, shape, dtypes) outputs, always allocated when not given in ``out``."""
+    (name, shape, dtypes) outputs, always allocated when not given in ``out``.  ``search_inputs`` False (the 'height'
+    step, which reads neither): ``params`` is not checked and ``hips`` may be None."""
     import torch
 
     E = int(seeds.shape[0]) if isinstance(seeds, torch.Tensor) and seeds.dim() == 3 else 0
     if not 1 <= E <= MAX_ENVS:
         raise ValueError(f"seeds must be a torch tensor of shape (1..{MAX_ENVS}, 4, 3)")
-    if not isinstance(params, TamolsParams):
+    if search_inputs and not isinstance(params, TamolsParams):
         raise ValueError("params must be a TamolsParams")
     if (terrain is None) == (heightmaps is None):
         raise ValueError("give either terrain (with yaws) or heightmaps")
@@ -1877,7 +1892,9 @@ def _tamols_batch_enqueue(native, what, seeds, hips, params, *, terrain=None, ya
         raise ValueError("scene_ids belong to a terrain set (GpuTerrainSet), not to " +
                          ("heightmaps: the patch form has no scenes" if terrain is None else "a single GpuTerrain"))
     f64, f32, i32 = (torch.float64,), (torch.float32,), (torch.int32,)
-    specs = [("seeds", seeds, (E, 4, 3), f64), ("hips", hips, (E, 4, 3), f64)]
+    specs = [("seeds", seeds, (E, 4, 3), f64)]
+    if search_inputs or hips is not None:
+        specs.append(("hips", hips, (E, 4, 3), f64))
     if is_set:
         specs.append(("scene_ids", scene_ids, (E,), i32))
     if terrain is None:
@@ -1938,9 +1955,10 @@ def _tamols_batch_enqueue(native, what, seeds, hips, params, *, terrain=None, ya
                            footholds=ptr(o["footholds"]), boxes=ptr(o["boxes"]), valid=ptr(o["valid"]),
                            seed_heights=ptr(o.get("seed_heights")), scores=ptr(o.get("scores")),
                            heightmaps_out=ptr(o.get("heightmaps")), ref=ptr(ref))
+        p = C.byref(params) if search_inputs else None
         if is_set:
-            return native(terrain.h, C.byref(params), E, C.byref(io), o, s, scene_ids.data_ptr())
-        return native(None if terrain is None else terrain.h, C.byref(params), E, C.byref(io), o, s)
+            return native(terrain.h, p, E, C.byref(io), o, s, scene_ids.data_ptr())
+        return native(None if terrain is None else terrain.h, p, E, C.byref(io), o, s)
 
     return _enqueue(dev, stream, alloc, call, what.replace("_device", "_scenes_device") if is_set else what)
 
@@ -2012,6 +2030,111 @@ def vfa_step_device(vfa, stc, seeds, hips, params, contact, *, apex_interval: fl
         native, "srbd_vfa_step_device", seeds, hips, params, contact=contact,
         extra_inputs=lambda E: (("vfa", vfa, (E, VFA_BYTES), u8), ("stc", stc, (E, STC_BYTES), u8)),
         extra_outputs=lambda E: (("mode", (E,), i32),), **kw)
+
+
+def vfa_height_step_device(vfa, stc, seeds, contact, *, terrain, yaws, hips=None, apex_interval: float = 0.01,
+                           heightmaps=None, want_scores=False, **kw):
+    """srbd_vfa_height_step_device: the 'height' strategy behind the apex gate, one launch enqueued on ``stream``
+    without a host synchronisation.  vfa / stc / seeds / contact as in ``vfa_step_device``; ``terrain`` a GpuTerrain,
+    or a GpuTerrainSet with ``scene_ids``; ``yaws`` (E,) float64; rows, cols, dist_x, dist_y, ray_z, ref, out,
+    want_seed_heights, want_heightmaps, stream as there.  A searching environment's footholds are its seeds at the
+    height of the nearest point of the leg's raycast patch + 0.02 (NaN and valid 0 where that ray missed on a scene
+    whose miss_z is NaN); its searched boxes are NaN.  ``hips``, forward_vel, base_pos and feet are ignored (checked
+    when given); there is no patch form and there are no scores.  Returns ``vfa_step_device``'s dict."""
+    import math
+
+    import torch
+
+    if heightmaps is not None:
+        raise ValueError("the 'height' step has no patch form: give terrain and yaws, not heightmaps")
+    if want_scores or "scores" in (kw.get("out") or {}):
+        raise ValueError("the 'height' step has no scores")
+    if terrain is None:
+        raise ValueError("the 'height' step needs a terrain (a GpuTerrain, or a GpuTerrainSet with scene_ids)")
+    if contact is None:
+        raise ValueError("the gate needs the contact flags")
+    interval = float(apex_interval)
+    if not math.isfinite(interval):
+        raise ValueError(f"apex_interval must be finite, got {apex_interval}")
+    u8, i32 = (torch.uint8,), (torch.int32,)
+
+    def native(th, p, E, io, o, s, ids=None):
+        if ids is not None:
+            return lib.srbd_vfa_height_step_scenes_device(vfa.data_ptr(), stc.data_ptr(), th, ids, E, io, interval,
+                                                          o["mode"].data_ptr(), s)
+        return lib.srbd_vfa_height_step_device(vfa.data_ptr(), stc.data_ptr(), th, E, io, interval,
+                                               o["mode"].data_ptr(), s)
+
+    return _tamols_batch_enqueue(
+        native, "srbd_vfa_height_step_device", seeds, hips, None, contact=contact, terrain=terrain, yaws=yaws,
+        extra_inputs=lambda E: (("vfa", vfa, (E, VFA_BYTES), u8), ("stc", stc, (E, STC_BYTES), u8)),
+        extra_outputs=lambda E: (("mode", (E,), i32),), search_inputs=False, **kw)
+
+
+MAX_PATCHES_PER_ENV = 16
+
+
+def terrain_patches_device(terrain, centers, yaws, rows=13, cols=7, dist_x=0.04, dist_y=0.04, ray_z=10.0, points=True,
+                           heights=False, stream=None, scene_ids=None, out=None):
+    """srbd_terrain_patches_device / srbd_terrain_set_patches_device: K height scans per environment, one launch
+    enqueued on ``stream`` (None: torch's current stream) without a host synchronisation.  centers (E, K, 3) and yaws
+    (E,) float64 cuda tensors; ``terrain`` a GpuTerrain, or a GpuTerrainSet with ``scene_ids`` (E,) int32 (read in
+    stream order; an index outside the set: the empty scene).  Returns ``points`` (E, K, rows, cols, 3), ``heights``
+    (E, K, rows, cols) or, with both flags, the pair; ``out``: a dict of preallocated ``points`` / ``heights``."""
+    import math
+
+    import torch
+
+    if not isinstance(centers, torch.Tensor) or centers.dim() != 3:
+        raise ValueError(f"centers must be a torch tensor of shape (1..{MAX_ENVS}, 1..{MAX_PATCHES_PER_ENV}, 3)")
+    E, K = int(centers.shape[0]), int(centers.shape[1])
+    if not 1 <= E <= MAX_ENVS or not 1 <= K <= MAX_PATCHES_PER_ENV:
+        raise ValueError(f"centers must be (1..{MAX_ENVS}, 1..{MAX_PATCHES_PER_ENV}, 3), got {tuple(centers.shape)}")
+    is_set = hasattr(terrain, "num_scenes")
+    if is_set and scene_ids is None:
+        raise ValueError("a terrain set needs scene_ids, the (E,) int32 scene index of every environment")
+    if scene_ids is not None and not is_set:
+        raise ValueError("scene_ids belong to a terrain set (GpuTerrainSet), not to a single GpuTerrain")
+    rows, cols = int(rows), int(cols)
+    if rows < 1 or cols < 1 or rows * cols > MAX_CAND:
+        raise ValueError(f"the patch must have 1..{MAX_CAND} points, got {rows} x {cols}")
+    dist_x, dist_y, ray_z = float(dist_x), float(dist_y), float(ray_z)
+    if not (dist_x > 0.0 and dist_y > 0.0 and math.isfinite(dist_x) and math.isfinite(dist_y)):
+        raise ValueError(f"dist_x and dist_y must be positive and finite, got {dist_x}, {dist_y}")
+    if not math.isfinite(ray_z):
+        raise ValueError(f"ray_z must be finite, got {ray_z}")
+    given = dict(out or {})
+    want = [n for n, w in (("points", points), ("heights", heights)) if w or n in given]
+    if not want:
+        raise ValueError("ask for points, heights or both")
+    f64 = (torch.float64,)
+    shapes = {"points": (E, K, rows, cols, 3), "heights": (E, K, rows, cols)}
+    specs = [("centers", centers, (E, K, 3), f64), ("yaws", yaws, (E,), f64)]
+    if is_set:
+        specs.append(("scene_ids", scene_ids, (E,), (torch.int32,)))
+    for name, t in given.items():
+        if name not in shapes:
+            raise ValueError(f"unknown output {name!r}")
+        specs.append((f"out[{name!r}]", t, shapes[name], f64))
+    dev = _device_tensors(specs)
+    if is_set and dev.index != terrain.device_id:
+        raise ValueError(f"scene_ids must be on the set's device cuda:{terrain.device_id}, got {dev}")
+
+    def alloc():
+        return {n: given[n] if n in given else torch.empty(shapes[n], dtype=torch.float64, device=dev) for n in want}
+
+    def call(o, s):
+        io = PatchBatchIO(centers=centers.data_ptr(), yaws=yaws.data_ptr(), patches_per_env=K, rows=rows, cols=cols,
+                          dist_x=dist_x, dist_y=dist_y, ray_z=ray_z,
+                          points=o["points"].data_ptr() if "points" in o else None,
+                          heights=o["heights"].data_ptr() if "heights" in o else None)
+        if is_set:
+            return lib.srbd_terrain_set_patches_device(terrain.h, scene_ids.data_ptr(), E, C.byref(io), s)
+        return lib.srbd_terrain_patches_device(terrain.h, E, C.byref(io), s)
+
+    o = _enqueue(dev, stream, alloc, call,
+                 "srbd_terrain_set_patches_device" if is_set else "srbd_terrain_patches_device")
+    return (o["points"], o["heights"]) if len(want) == 2 else o[want[0]]
 
 
 FRG_BYTES = C.sizeof(SrbdFrg)

@@ -145,6 +145,16 @@ class GpuTerrain:
             raise RuntimeError(f"srbd_terrain_patches failed ({rc}): {msg.decode() if msg else ''}")
         return out
 
+    def patches_device(self, centers, yaws, rows=13, cols=7, dist_x=0.04, dist_y=0.04, ray_z=10.0, points=True,
+                       heights=False, stream=None, out=None):
+        """The height scan of a batch on the device (``srbd_terrain_patches_device``): centers (E, K, 3) and yaws (E,)
+        float64 cuda tensors, K patches per environment at the environment's yaw, one launch enqueued on ``stream``
+        (None: torch's current stream), nothing synchronised.  Returns ``points`` (E, K, rows, cols, 3), ``heights``
+        (E, K, rows, cols) -- the points' z --, or with both flags the pair; the bytes ``patches`` returns wherever
+        numpy's cos / sin of the yaw are the correctly rounded ones.  CPU tensors are refused, not copied."""
+        return _lib.terrain_patches_device(self, centers, yaws, rows, cols, dist_x, dist_y, ray_z, points, heights,
+                                           stream, out=out)
+
     def close(self):
         if getattr(self, "h", None):
             _lib.lib.srbd_terrain_destroy(self.h)
@@ -161,7 +171,7 @@ class GpuTerrainSet:
     """A device-resident, immutable set of scenes (``srbd_terrain_set``) for the batched searches with one scene per
     environment: ``tamols_batch_device`` / ``vfa_step_device`` (and ``BatchedVisualFootholdAdaptation``) take it as
     ``terrain`` together with ``scene_ids``, the (E,) int32 device tensor of every environment's scene index.
-    ``scenes``: a sequence of the keyword dicts ``GpuTerrain`` takes (prims, has_ground, ground_z, hfield, miss_z)."""
+    ``patches_device`` is the height scan on them.  ``scenes``: a sequence of the keyword dicts ``GpuTerrain`` takes (prims, has_ground, ground_z, hfield, miss_z)."""
 
     def __init__(self, scenes, device_id=0):
         scenes = [dict(s) for s in scenes]
@@ -185,6 +195,14 @@ class GpuTerrainSet:
         self.h = h
         self.device_id = int(device_id)
         self.num_scenes = len(scenes)
+
+    def patches_device(self, centers, yaws, rows=13, cols=7, dist_x=0.04, dist_y=0.04, ray_z=10.0, points=True,
+                       heights=False, stream=None, *, scene_ids, out=None):
+        """``GpuTerrain.patches_device`` with environment e's rays cast against scene ``scene_ids[e]``
+        (``srbd_terrain_set_patches_device``): scene_ids an (E,) int32 tensor on the set's device, read in stream
+        order; an index outside the set scans the empty scene (every height NaN)."""
+        return _lib.terrain_patches_device(self, centers, yaws, rows, cols, dist_x, dist_y, ray_z, points, heights,
+                                           stream, scene_ids=scene_ids, out=out)
 
     def close(self):
         if getattr(self, "h", None):

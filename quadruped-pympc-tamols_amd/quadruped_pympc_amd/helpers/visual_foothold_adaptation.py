@@ -332,17 +332,23 @@ class VisualFootholdAdaptation:
 
 
 class BatchedVisualFootholdAdaptation:
-    """TAMOLS foothold adaptation of ``num_envs`` environments on the device (``srbd_tamols_batch_device``): the
-    batched, device-resident counterpart of ``VisualFootholdAdaptation.compute_adaptation`` with the strategy
-    ``'tamols'``, for the loop ``gait.run -> compute_adaptation_device -> prepare_state_and_reference_device ->
+    """Foothold adaptation of ``num_envs`` environments on the device: the batched, device-resident counterpart of
+    ``VisualFootholdAdaptation.compute_adaptation`` with the strategy ``'tamols'`` (``srbd_tamols_batch_device``; the
+    default) or ``'height'`` (``step_device`` only: ``srbd_vfa_height_step_device``, each searching leg's seed at the
+    height of its raycast patch's nearest point + 0.02, no foothold constraints), for the loop ``gait.run -> compute_adaptation_device -> prepare_state_and_reference_device ->
     compute_control_device``.  Every environment gets what the single-environment call computes for its inputs; the
     parameters (``tamols_params`` and the robot's reach limits, through ``tamols_params_struct``) are shared.  The
     constructor touches no device."""
 
-    def __init__(self, num_envs: int, config_module=None):
+    def __init__(self, num_envs: int, config_module=None, adaptation_strategy="tamols"):
         num_envs = int(num_envs)
         if not 1 <= num_envs <= _lib.MAX_ENVS:
             raise ValueError(f"num_envs must be 1..{_lib.MAX_ENVS}, got {num_envs}")
+        if adaptation_strategy == "vfa":
+            raise ImportError("VFA strategy requested but VFA module could not be imported.")
+        if adaptation_strategy not in ("tamols", "height"):
+            raise ValueError(f"adaptation_strategy must be 'tamols' or 'height', got {adaptation_strategy!r}")
+        self.adaptation_strategy = adaptation_strategy
         cfg = active_config(config_module)
         self.num_envs = num_envs
         self.tamols_params = cfg.simulation_params.get("tamols_params", {})
@@ -418,12 +424,24 @@ class BatchedVisualFootholdAdaptation:
         (E, 4, 3), boxes (E, 4, 2, 3), valid (E, 4) int32, mode (E,) int32 of ``_lib.VFA_SEARCH`` / ``VFA_HOLD`` /
         ``VFA_PASS``); a leg whose last search found no candidate returns valid 0 with the box of its last feasible
         search (NaN if none).  ``ref``'s feet receive the footholds.  ``mode`` is allocated once and rewritten by
-        every call.  ``terrain`` a GpuTerrainSet with ``scene_ids``: a searching environment searches on its own scene."""
+        every call.  ``terrain`` a GpuTerrainSet with ``scene_ids``: a searching environment searches on its own scene.
+        With the strategy ``'height'`` the search is the nearest-point height of the leg's raycast patch
+        (``srbd_vfa_height_step_device``): ``terrain`` is required, ``heightmaps`` raises ValueError, the hips, velocity,
+        base position and feet are not read, and a searching leg's box is NaN."""
         if getattr(seeds, "shape", (0,))[0] != self.num_envs:
             raise ValueError(f"seeds must hold {self.num_envs} environments, got {tuple(getattr(seeds, 'shape', ()))}")
         given = dict(patch.pop("out", None) or {})
         if "mode" not in given and self._mode is not None:
             given["mode"] = self._mode
+        if self.adaptation_strategy == "height":
+            if heightmaps is not None:
+                raise ValueError("the 'height' strategy has no patch form: give terrain and yaws, not heightmaps")
+            out = _lib.vfa_height_step_device(self.state, getattr(stc, "state", stc), seeds, current_contact,
+                                              terrain=terrain, yaws=yaws, hips=hips, apex_interval=apex_interval,
+                                              forward_vel=forward_vel, base_pos=base_position, feet=current_feet_pos,
+                                              ref=ref, stream=stream, out=given, scene_ids=scene_ids, **patch)
+            self._mode = out["mode"]
+            return out["footholds"], out["boxes"], out["valid"], out["mode"]
         out = _lib.vfa_step_device(self.state, getattr(stc, "state", stc), seeds, hips, self._params(), current_contact,
                                    apex_interval=apex_interval, terrain=terrain, yaws=yaws, heightmaps=heightmaps,
                                    forward_vel=forward_vel, base_pos=base_position, feet=current_feet_pos, ref=ref,
@@ -445,6 +463,9 @@ class BatchedVisualFootholdAdaptation:
         whose feet (entries 12..23) receive the footholds.  Returns (footholds (E, 4, 3), boxes (E, 4, 2, 3) -- NaN
         for a leg without a feasible candidate, whose foothold is the seed at its terrain height --, valid (E, 4)
         int32)."""
+        if self.adaptation_strategy != "tamols":
+            raise ValueError(f"compute_adaptation_device is the 'tamols' search; the strategy "
+                             f"{self.adaptation_strategy!r} runs through step_device")
         if getattr(seeds, "shape", (0,))[0] != self.num_envs:
             raise ValueError(f"seeds must hold {self.num_envs} environments, got {tuple(getattr(seeds, 'shape', ()))}")
         out = _lib.tamols_batch_device(seeds, hips, self._params(), terrain=terrain, yaws=yaws, heightmaps=heightmaps,
