@@ -18,6 +18,11 @@
  *                                       WBInterface.compute_stance_and_swing_torque
  *                                       quadruped_pympc/helpers/swing_trajectory_controller.py:5-146
  *                                       quadruped_pympc/interfaces/wb_interface.py:369-415, :435-465
+ *   srbd_reflex_init / _detect / _reference / _step
+ *                                    <- EarlyStanceDetector and the 'scipy' SwingTrajectoryGenerator, the swing reflex
+ *                                       quadruped_pympc/helpers/early_stance_detector.py:7-128
+ *                                       quadruped_pympc/helpers/swing_generators/scipy_swing_trajectory_generator.py:8-122
+ *                                       quadruped_pympc/interfaces/wb_interface.py:362-365
  *   srbd_stc_touch_down / srbd_gait_apply_freq
  *                                    <- SwingTrajectoryController.check_touch_down_condition and the step-frequency
  *                                       write-back of WBInterface.compute_stance_and_swing_torque
@@ -200,9 +205,9 @@ int srbd_frg_mean(const srbd_frg* g, double mean_out[2]);
  * cofactors over the determinant.  For a well-conditioned Jacobian the two agree to rounding.  For a singular one they
  * do not: when the determinant is zero or not finite Jinv is the zero matrix, so every output stays finite and the
  * feedback-linearisation term reduces to the bias force.
- * Out of scope: the early-stance detector (neither generator reads its hit moment or hit point, and
- * reflex_next_steps_height_enhancement is off by default: it changes no output of this path), inverse kinematics and
- * des_joints_pos, the kinodynamic branch and the 'scipy' generator.  The re-timing from optimize_swing /
+ * Not in these calls: the early-stance detector and the 'scipy' generator, the one generator that reads the detector's
+ * hit moment and hit point, have entry points of their own, below (srbd_reflex_*).  Out of scope: inverse kinematics and
+ * des_joints_pos, and the kinodynamic branch.  The re-timing from optimize_swing /
  * best_sample_freq (wb_interface.py:354-358) is not part of srbd_stc_step: srbd_stc_touch_down and srbd_gait_apply_freq
  * below are its trigger and its write-back (srbd_stc_set_timing is the call it would make for the swing period). */
 enum { SRBD_SWING_BEZIER_REF = 0, SRBD_SWING_EXPLICIT = 1 };
@@ -267,6 +272,87 @@ int srbd_stc_step(srbd_stc* g, const srbd_stc_io* io, double dt);
 int srbd_stc_apex(const srbd_stc* g, const double contact[4], double interval);
 /* 1 if no contact equals 0, else 0; negative: NULL. */
 int srbd_stc_full_stance(const double contact[4]);
+
+/* ---- Swing reflexes: the early-stance detector and the 'scipy' swing generator, the reflex path of the leg controller
+ * (csrc/srbd_reflex.h, which the device form srbd_reflex_step_device of srbd_mpc.h compiles too).
+ *   srbd_reflex_init      <- EarlyStanceDetector.__init__          quadruped_pympc/helpers/early_stance_detector.py:7-33
+ *                            and the reflex fields of the scipy SwingTrajectoryGenerator.__init__
+ *                            quadruped_pympc/helpers/swing_generators/scipy_swing_trajectory_generator.py:8-23
+ *   srbd_reflex_detect    <- EarlyStanceDetector.update_detection  early_stance_detector.py:36-128
+ *   srbd_reflex_reference <- SwingTrajectoryGenerator.createCurve / compute_trajectory_references
+ *                            scipy_swing_trajectory_generator.py:25-122
+ *   srbd_reflex_step      <- wb_interface.py:362-415 and :435-465 with SwingTrajectoryController(generator="scipy")
+ * State: one srbd_reflex per environment (plain data, sizeof 320, doubles first, no byte of padding), next to that
+ * environment's srbd_stc, which is reused unchanged for the gains, step height, swing period, switches and clocks; its
+ * `generator` field is not read by these calls.  Legs FL FR RL RR.
+ * The detector, statement for statement (trigger_mode SRBD_REFLEX_TRACKING, the reference's configuration; with
+ * SRBD_REFLEX_OFF every leg is cleared each tick).  Leg by leg: a stance leg (contact == 1) only clears early_stance --
+ * its hit moment and hit point stay until its next swing tick; a leg that has not triggered and whose clock is inside
+ * the last early_stance_time_threshold (0.07 s) of the swing is skipped; a leg that has triggered keeps its hit for the
+ * rest of the swing; otherwise local = last_des_foot_pos - foot, disp = touch_down - lift_off and the leg triggers when
+ * norm(local) / norm(disp) > 0.3 and norm(local) > 0.1 (IEEE: a zero disp gives inf or NaN, compared as NumPy compares
+ * them; norm = sqrt((x x + y y) + z z)): hitpoint = foot, hitmoment = the clock, early_stance = 1, the gait-cycle
+ * counter = 0, and the tick ends there -- the legs after the first that triggers are not touched at all.  A leg that
+ * does not trigger is cleared (hitmoment -1, no hitpoint).  Then, only with the enhancement switched on: at most one
+ * touch-down edge (contact == 1 and previous_contact == 0) increments the counter, and only while it is >= 0; the flag
+ * height_enhancement is 0 <= gait_cycles < max_gait_cycles (6), otherwise the counter returns to -1.
+ * The generator: five knots per axis and scipy's CubicSpline(bc_type=["clamped", "clamped"]) through them, solved as
+ * the 3 x 3 tridiagonal system of the interior knot derivatives by elimination in the fixed order csrc/srbd_reflex.h
+ * writes out.  The contract is agreement with scipy to rounding, not to the bit; as an observation, on the recorded
+ * fixture (scipy 1.15.3) the spline's values did come out equal bit for bit, because LAPACK's tridiagonal solve makes
+ * no row exchange on these systems and then performs the same elimination.  Without a hit the knots are lift_off, the three
+ * step_height / 1.5 way-points and touch_down over t = 0, T/4, T/2, 3T/4, T (reflex_max_step_height in step_height's
+ * place while height_enhancement is set); with a hit the curve starts at the hit point, is pushed back by 0.01 (xf - x0),
+ * rises to reflex_max_step_height, ends x and y at its fourth knot and z at touch_down's (plus
+ * reflex_max_step_height / 2 when blind), over the hit moment to T in quarters.  Intervals are half-open, the last one
+ * closed, and the end intervals extrapolate.
+ * Deviation: with a hit recorded and swing_period - hitmoment not positive (only after a re-timing shortened the
+ * swing) the knots are not increasing and scipy raises; here that leg takes the no-hit curve from lift_off for that
+ * tick and its detector state is left alone.  The Jacobian inverse is srbd_stc_step's.
+ * Out of scope: the 'geom_contact' trigger (SRBD_REFLEX_GEOM_CONTACT is refused: it reads MuJoCo contact lists),
+ * inverse kinematics and des_joints_pos, the kinodynamic branch. */
+enum { SRBD_REFLEX_OFF = 0, SRBD_REFLEX_TRACKING = 1, SRBD_REFLEX_GEOM_CONTACT = 2 /* refused */ };
+typedef struct srbd_reflex {
+    double reflex_max_step_height;
+    double early_stance_time_threshold;           /* 0.07 after init */
+    double relative_tracking_error_threshold;     /* 0.3 */
+    double absolute_min_distance_error_threshold; /* 0.1 */
+    double hitmoments[4];                         /* the clock at the hit, or -1 */
+    double hitpoints[4][3];                       /* the foot at the hit; zeros while has_hitpoint is 0 */
+    double last_des_foot_pos[4][3];               /* the desired foot positions the previous step wrote; zeros at init */
+    int32_t has_hitpoint[4];                      /* 0: the reference's None */
+    int32_t early_stance[4];
+    int32_t trigger_mode;                         /* SRBD_REFLEX_OFF, SRBD_REFLEX_TRACKING */
+    int32_t blind;                                /* visual_foothold_adaptation == 'blind' */
+    int32_t use_height_enhancement;               /* reflex_next_steps_height_enhancement, the switch */
+    int32_t height_enhancement;                   /* the generator's flag as the last detection left it */
+    int32_t gait_cycles;                          /* gait cycles since the last reflex, -1 at init */
+    int32_t max_gait_cycles;                      /* 6 after init */
+    int32_t reserved[2];                          /* 0: so that no padding is left to chance */
+} srbd_reflex;
+
+/* The reference's values: the thresholds 0.07, 0.3 and 0.1, six cycles, no hit, counter -1, flag 0, last_des_foot_pos
+ * zero.  SRBD_E_INVALID (nothing written): a NULL r, a reflex_max_step_height that is not finite, a trigger_mode other
+ * than SRBD_REFLEX_OFF and SRBD_REFLEX_TRACKING. */
+int srbd_reflex_init(srbd_reflex* r, double reflex_max_step_height, int32_t blind, int32_t trigger_mode,
+                     int32_t use_height_enhancement);
+/* update_detection alone.  swing_time are the clocks the previous step left (4), feet the feet now, lift_off and
+ * touch_down 4 x 3, contact and previous_contact 4; the desired foot positions are r->last_des_foot_pos.
+ * SRBD_E_INVALID (nothing written): a NULL pointer, a struct srbd_reflex_init would refuse. */
+int srbd_reflex_detect(srbd_reflex* r, const double* feet, const double* lift_off, const double* touch_down,
+                       const double swing_time[4], double swing_period, const double contact[4],
+                       const double previous_contact[4]);
+/* The generator alone for one leg at that leg's clock g->swing_time[leg], with the leg's hit and the flag as r holds
+ * them.  SRBD_E_INVALID: NULL, leg outside 0..3, structs srbd_reflex_step would refuse. */
+int srbd_reflex_reference(const srbd_stc* g, const srbd_reflex* r, int32_t leg, const double lift_off[3],
+                          const double touch_down[3], double pos[3], double vel[3], double acc[3]);
+/* One environment's whole step, in this order: the detector (on the clocks and r->last_des_foot_pos the previous step
+ * left, io->foot_pos, io->lift_off, io->touch_down, io->contact and previous_contact); the clock update; srbd_stc_step's
+ * leg law with the spline generator in the place of the Bezier ones; io->des_foot_pos into r->last_des_foot_pos; apex
+ * and full stance.  SRBD_E_INVALID (nothing written): what srbd_stc_step refuses (the generator code of g excepted: it
+ * is not read), a NULL r or previous_contact, an unknown or refused trigger mode, a reflex_max_step_height that is not
+ * finite. */
+int srbd_reflex_step(srbd_stc* g, srbd_reflex* r, const srbd_stc_io* io, const double previous_contact[4], double dt);
 
 /* ---- Gait adaptation (mpc_params['optimize_step_freq']): when to optimise the step frequency, and what the sampler's
  * best frequency re-times (csrc/srbd_gait_adapt.h, which the device forms srbd_stc_touch_down_device and

@@ -1134,6 +1134,52 @@ typedef struct srbd_stc_batch_io {
 int srbd_stc_step_device(struct srbd_stc* d_stc, int32_t num_envs, double dt, const srbd_stc_batch_io* io,
                          void* hip_stream);
 
+/* The swing reflex path of the device-resident loop: the early-stance detector, the swing clocks and the stance and
+ * swing torques with the 'scipy' spline generator, the one generator that re-plans a swing from the point where the
+ * foot hit something (WBInterface.compute_stance_and_swing_torque, wb_interface.py:362-415 and :435-465, with
+ * EarlyStanceDetector.update_detection, early_stance_detector.py:36-128, in 'tracking' mode and
+ * SwingTrajectoryController(generator="scipy"), swing_generators/scipy_swing_trajectory_generator.py:25-122), for
+ * num_envs environments in one launch.  It takes srbd_stc_step_device's place in the loop for a caller that wants the
+ * reference's reflexes; srbd_stc_step_device itself is unchanged.
+ *   State: d_stc as for srbd_stc_step_device -- the same structs, so srbd_gait_apply_freq_device, srbd_loop_reset_device
+ *   and srbd_vfa_step_device work on them unchanged; the `generator` field is not read here -- and d_reflex, an array
+ *   of num_envs srbd_reflex structs (srbd_host.h, plain data) in device memory, initialised on the host with
+ *   srbd_reflex_init and uploaded: thresholds, reflex_max_step_height, trigger mode, blind flag and the enhancement
+ *   switch are per environment.  srbd_loop_reset_device does not know d_reflex: a caller that restarts an environment
+ *   copies that environment's struct as srbd_reflex_init left it over d_reflex[e] on the same stream.
+ *   Inputs are srbd_stc_step_device's (io->stc) plus previous_contact, E x 4 float32: the contact flags of the previous
+ *   control step (WBInterface.previous_contact), read by the detector's touch-down edge.
+ *   Order within an environment, as srbd_reflex_step (srbd_host.h): the detector -- on the clocks and
+ *   last_des_foot_pos the previous call left, foot_pos, lift_off, touch_down, contact, previous_contact; the clock
+ *   update; the leg law with the spline generator; des_foot_pos into d_reflex[e].last_des_foot_pos; apex and full
+ *   stance.
+ *   Equivalence: for environment e the call does what the host call srbd_reflex_step (srbd_host.h) does on host structs
+ *   with the same bytes and the same inputs, the contacts widened to double.  Afterwards d_stc[e] and d_reflex[e] hold
+ *   exactly the host structs' bytes and every output row the host's values, bit for bit, NaNs position for position.
+ *   Both sides compile the same per-leg functions (csrc/srbd_reflex.h, csrc/srbd_stc.h).  Environments are
+ *   independent: a NaN in one changes nothing in another.  An environment whose structs the host call refuses
+ *   (swing_period not positive and finite, a trigger mode other than SRBD_REFLEX_OFF and SRBD_REFLEX_TRACKING --
+ *   'geom_contact' among them --, a reflex_max_step_height that is not finite) is left as found and its output rows
+ *   are not written.  The deviations from the reference are the host function's: Jinv as in srbd_stc_step_device
+ *   (np.linalg.pinv there, the cofactor inverse and the zero matrix for a singular Jacobian here), the spline solved by
+ *   elimination in a fixed order where scipy calls LAPACK, and the no-hit curve for a leg whose hit moment is not
+ *   below swing_period, where scipy raises.
+ *   Enqueue contract (the producers' above, srbd_prepare_state_device's): exactly one launch on hip_stream, no
+ *   synchronising HIP call, no device memory touched from the host; the stream handle is read as
+ *   srbd_prepare_state_device reads it (NULL and hipStreamLegacy both select the legacy null stream); every pointer is
+ *   memory of the current device; no event and no ordering rule.  Arrays must not overlap.
+ *   SRBD_E_INVALID (before any HIP call): a NULL d_stc, d_reflex, io, io->previous_contact or required pointer of
+ *   io->stc (every pointer except lift_off, frg, des_joint_vel, apex and full_stance); both or neither of lift_off
+ *   and frg; num_envs outside 1..4096; a dt or apex_interval that is not finite.  A failed launch: SRBD_E_HIP, or
+ *   SRBD_E_NODEVICE where no device exists. */
+struct srbd_reflex;
+typedef struct srbd_reflex_batch_io {
+    srbd_stc_batch_io stc;            /* the arrays of srbd_stc_step_device, read and written as there */
+    const float* previous_contact;    /* E x 4 float32: the previous control step's contact flags */
+} srbd_reflex_batch_io;
+int srbd_reflex_step_device(struct srbd_stc* d_stc, struct srbd_reflex* d_reflex, int32_t num_envs, double dt,
+                            const srbd_reflex_batch_io* io, void* hip_stream);
+
 /* The velocity modulator and the terrain estimate with the reference row of the device-resident loop: what
  * WBInterface.update_state_and_reference builds from the velocity command before and after the foothold reference
  * generator (wb_interface.py:168-172 with velocity_modulator.py:19-46; wb_interface.py:250-291 with

@@ -8,6 +8,8 @@
 //   WBI  = quadruped_pympc/interfaces/wb_interface.py
 //   VM   = quadruped_pympc/helpers/velocity_modulator.py
 //   TE   = quadruped_pympc/helpers/terrain_estimator.py
+//   ESD  = quadruped_pympc/helpers/early_stance_detector.py
+//   SCI  = quadruped_pympc/helpers/swing_generators/scipy_swing_trajectory_generator.py
 // Built with -ffp-contract=off: every float64 operation rounds as NumPy's does.
 #include <math.h>
 #include <string.h>
@@ -18,6 +20,7 @@
 #include "srbd_gait_adapt.h"
 #include "srbd_iface.h"
 #include "srbd_jaxrng.h"
+#include "srbd_reflex.h"
 #include "srbd_reset.h"
 #include "srbd_start_stop.h"
 #include "srbd_stc.h"
@@ -309,6 +312,101 @@ extern "C" int srbd_stc_apex(const srbd_stc* g, const double contact[4], double 
 extern "C" int srbd_stc_full_stance(const double contact[4]) {  // STC:140-146
     if (!contact) return SRBD_E_INVALID;
     return srbd::stc_full_stance(contact);
+}
+
+// ------------------------------------------- swing reflexes: early-stance detector and spline generator (srbd_reflex.h)
+extern "C" int srbd_reflex_init(srbd_reflex* r, double reflex_max_step_height, int32_t blind, int32_t trigger_mode,
+                                int32_t use_height_enhancement) {  // ESD:7-33, SCI:8-23
+    if (!r || !std::isfinite(reflex_max_step_height)) return SRBD_E_INVALID;
+    if (trigger_mode != SRBD_REFLEX_OFF && trigger_mode != SRBD_REFLEX_TRACKING) return SRBD_E_INVALID;
+    memset(r, 0, sizeof(*r));
+    r->reflex_max_step_height = reflex_max_step_height;
+    r->early_stance_time_threshold = 0.07;
+    r->relative_tracking_error_threshold = 0.3;
+    r->absolute_min_distance_error_threshold = 0.1;
+    for (int l = 0; l < 4; ++l) r->hitmoments[l] = -1.0;
+    r->trigger_mode = trigger_mode;
+    r->blind = blind != 0;
+    r->use_height_enhancement = use_height_enhancement != 0;
+    r->gait_cycles = -1;
+    r->max_gait_cycles = 6;
+    return SRBD_OK;
+}
+
+namespace {
+
+bool reflex_struct_ok(const srbd_reflex* r) {
+    return (r->trigger_mode == SRBD_REFLEX_OFF || r->trigger_mode == SRBD_REFLEX_TRACKING) &&
+           std::isfinite(r->reflex_max_step_height);
+}
+
+// ESD:36-128: the legs in order, ending at the first that triggers; then the cycle counter and the flag.
+void reflex_detect(srbd_reflex* r, const double* feet, const double* lift_off, const double* touch_down,
+                   const double* swing_time, double swing_period, const double* contact, const double* previous) {
+    bool triggered = false;
+    for (int l = 0; l < 4 && !triggered; ++l) {
+        srbd::ReflexLeg s;
+        srbd::reflex_leg_load(r, l, s);
+        triggered = srbd::reflex_leg_detect(r, s, swing_time[l], swing_period, contact[l], feet + 3 * l,
+                                            r->last_des_foot_pos[l], lift_off + 3 * l, touch_down + 3 * l);
+        srbd::reflex_leg_store(r, l, s);
+    }
+    srbd::reflex_cycles(r, triggered, contact, previous, r->gait_cycles, r->height_enhancement);
+}
+
+}  // namespace
+
+extern "C" int srbd_reflex_detect(srbd_reflex* r, const double* feet, const double* lift_off, const double* touch_down,
+                                  const double swing_time[4], double swing_period, const double contact[4],
+                                  const double previous_contact[4]) {
+    if (!r || !feet || !lift_off || !touch_down || !swing_time || !contact || !previous_contact || !reflex_struct_ok(r))
+        return SRBD_E_INVALID;
+    reflex_detect(r, feet, lift_off, touch_down, swing_time, swing_period, contact, previous_contact);
+    return SRBD_OK;
+}
+
+extern "C" int srbd_reflex_reference(const srbd_stc* g, const srbd_reflex* r, int32_t leg, const double lift_off[3],
+                                     const double touch_down[3], double pos[3], double vel[3], double acc[3]) {
+    if (!g || !r || !lift_off || !touch_down || !pos || !vel || !acc || leg < 0 || leg > 3 ||
+        !srbd::reflex_structs_ok(g, r))
+        return SRBD_E_INVALID;
+    srbd::ReflexLeg s;
+    srbd::reflex_leg_load(r, leg, s);
+    srbd::reflex_reference(g, r, s, r->height_enhancement, g->swing_time[leg], lift_off, touch_down, pos, vel, acc);
+    return SRBD_OK;
+}
+
+// WBI:362-415, :435-465: the detector on what the previous step left, then srbd_stc_step's stages with the spline
+// generator, and the desired foot positions kept for the next step's detector (WBI:408).
+extern "C" int srbd_reflex_step(srbd_stc* g, srbd_reflex* r, const srbd_stc_io* io, const double previous_contact[4],
+                                double dt) {
+    if (!g || !r || !io || !previous_contact || !std::isfinite(dt) || !std::isfinite(io->apex_interval) ||
+        !srbd::reflex_structs_ok(g, r))
+        return SRBD_E_INVALID;
+    if (!io->jac || !io->jac_dot || !io->mass_matrix || !io->q_dot || !io->foot_pos || !io->foot_vel ||
+        !io->qfrc_passive || !io->qfrc_bias || !io->grfs || !io->lift_off || !io->touch_down || !io->contact ||
+        !io->tau || !io->des_foot_pos || !io->des_foot_vel)
+        return SRBD_E_INVALID;
+    reflex_detect(r, io->foot_pos, io->lift_off, io->touch_down, g->swing_time, g->swing_period, io->contact,
+                  previous_contact);
+    for (int l = 0; l < 4; ++l)
+        g->swing_time[l] = srbd::stc_clock(g->swing_time[l], g->swing_period, io->contact[l], dt);
+    for (int l = 0; l < 4; ++l) {
+        const srbd::StcLeg x = {io->jac + 9 * l,         io->jac_dot + 9 * l,      io->mass_matrix + 9 * l,
+                                io->q_dot + 3 * l,       io->foot_pos + 3 * l,     io->foot_vel + 3 * l,
+                                io->qfrc_passive + 3 * l, io->qfrc_bias + 3 * l,   io->grfs + 3 * l,
+                                io->lift_off + 3 * l,    io->touch_down + 3 * l,   io->tau + 3 * l,
+                                io->des_foot_pos + 3 * l, io->des_foot_vel + 3 * l,
+                                io->des_joint_vel ? io->des_joint_vel + 3 * l : nullptr};
+        srbd::ReflexSplineGen gen = {g, r, {}, r->height_enhancement, g->swing_time[l], x.lift_off, x.touch_down};
+        srbd::reflex_leg_load(r, l, gen.s);
+        srbd::stc_leg_with(g, io->contact[l], x, gen);
+    }
+    for (int l = 0; l < 4; ++l)
+        for (int k = 0; k < 3; ++k) r->last_des_foot_pos[l][k] = io->des_foot_pos[3 * l + k];
+    if (io->apex) *io->apex = srbd::stc_apex(g->swing_time, g->swing_period, io->contact, io->apex_interval);
+    if (io->full_stance) *io->full_stance = srbd::stc_full_stance(io->contact);
+    return SRBD_OK;
 }
 
 // ------------------------------------------- gait adaptation: trigger and frequency write-back (srbd_gait_adapt.h)

@@ -57,6 +57,7 @@
 
 #include "../../include/srbd_host.h"
 #include "../../include/srbd_mpc.h"
+#include "srbd_enqueue.h"
 #include "srbd_frg.h"
 #include "srbd_gait_adapt.h"
 #include "srbd_iface.h"
@@ -69,8 +70,6 @@
 
 namespace srbd {
 
-constexpr int PROD_BLOCK = 256;
-constexpr int PROD_MAX_ENVS = 4096;  // srbd_batch_create's range
 constexpr int PROD_MAX_DTS = 32;
 
 // Python's float `x % 1.0` (srbd_host.cpp pymod1; the float64 fmod is exact on both sides).
@@ -793,23 +792,6 @@ __global__ void __launch_bounds__(64 * LOOP_RESET_WAVES) loop_reset_kernel(int E
 using namespace srbd;
 
 namespace {
-
-// NULL and hipStreamLegacy both name the legacy null stream: there is no batch here to own one.
-hipStream_t stream_of(void* hip_stream) {
-    hipStream_t s = (hipStream_t)hip_stream;
-    return s == hipStreamLegacy ? nullptr : s;
-}
-
-int launch_status() {
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return SRBD_OK;
-    int ndev = 0;
-    return (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) ? SRBD_E_NODEVICE : SRBD_E_HIP;
-}
-
-unsigned blocks_of(int E) { return (unsigned)((4 * E + PROD_BLOCK - 1) / PROD_BLOCK); }
-
-bool envs_ok(int32_t E) { return E >= 1 && E <= PROD_MAX_ENVS; }
 
 // The sequence call's own checks (srbd_pgg_contact_sequence_device), and its constants.
 bool pgg_seq_const(int32_t horizon, int32_t min_horizon, const double* dts, const int32_t* lens, int32_t n_dts,

@@ -16,10 +16,10 @@
 // the determinant.  For a well-conditioned J the two agree to rounding; for a singular J they do not: the
 // pseudo-inverse is the least-squares inverse, this one is the zero matrix whenever det is zero or not finite, so
 // outputs stay finite and the feedback-linearisation term reduces to the bias force h.
-// Out of scope: the early-stance detector (neither generator here reads its hit moment or hit point, and
-// reflex_next_steps_height_enhancement is off by default, so it changes no output of this path); inverse kinematics
-// and des_joints_pos; the kinodynamic branch; the scipy generator.  The re-timing from optimize_swing /
-// best_sample_freq (WBI:354-358) lives in srbd_gait_adapt.h.
+// Not in this file: the early-stance detector and the scipy generator, which reads its hit moment and hit point, have
+// a file of their own (srbd_reflex.h, srbd_reflex_step); it runs stc_leg_with below with its spline in the generator's
+// place.  Out of scope: inverse kinematics and des_joints_pos; the kinodynamic branch.  The re-timing from
+// optimize_swing / best_sample_freq (WBI:354-358) lives in srbd_gait_adapt.h.
 #pragma once
 
 #include <math.h>
@@ -192,13 +192,15 @@ struct StcLeg {
 //     linearisation tau += ((M @ Jinv) @ ((des_acc + fb) - J_dot @ q_dot)) + h
 //   friction compensation, either kind of leg: tau -= passive
 //   des_joint_vel = q_dot + clip(Jinv @ des_foot_vel - q_dot, -10, 10)
-YAW_HD inline void stc_leg(const srbd_stc* g, double t, double contact, const StcLeg& x) {
+// gen(pos, vel, acc) is the swing generator at the leg's clock, called for a swing leg only.
+template <class Gen>
+YAW_HD inline void stc_leg_with(const srbd_stc* g, double contact, const StcLeg& x, const Gen& gen) {
 #pragma clang fp contract(off)
     double tau[3], dpos[3], dvel[3], jinv[9];
     stc_inverse(x.jac, jinv);
     if (contact == 0.0) {
         double dacc[3], fb[3], w[3], jq[3], mj[9], lin[3];
-        stc_reference(g, t, x.lift_off, x.touch_down, dpos, dvel, dacc);
+        gen(dpos, dvel, dacc);
         for (int k = 0; k < 3; ++k) {
             const double ep = dpos[k] - x.foot_pos[k], ev = dvel[k] - x.foot_vel[k];
             fb[k] = g->position_gain_fb * ep + g->velocity_gain_fb * ev;
@@ -232,6 +234,20 @@ YAW_HD inline void stc_leg(const srbd_stc* g, double t, double contact, const St
         x.des_foot_vel[k] = dvel[k];
         if (x.des_joint_vel) x.des_joint_vel[k] = x.q_dot[k] + stc_clip(jv[k] - x.q_dot[k], -10.0, 10.0);
     }
+}
+
+// The generator g selects at clock t, as stc_leg_with's hook.
+struct StcBezierGen {
+    const srbd_stc* g;
+    double t;
+    const double *lift_off, *touch_down;
+    YAW_HD void operator()(double* pos, double* vel, double* acc) const {
+        stc_reference(g, t, lift_off, touch_down, pos, vel, acc);
+    }
+};
+
+YAW_HD inline void stc_leg(const srbd_stc* g, double t, double contact, const StcLeg& x) {
+    stc_leg_with(g, contact, x, StcBezierGen{g, t, x.lift_off, x.touch_down});
 }
 
 // STC:129-138 from the four clocks: 1 if a swing leg's clock lies strictly inside swing_period / 2 +- interval.

@@ -293,6 +293,26 @@ class SrbdStcBatchIo(C.Structure):
     ]
 
 
+REFLEX_OFF, REFLEX_TRACKING, REFLEX_GEOM_CONTACT = 0, 1, 2
+# config.simulation_params['reflex_trigger_mode'] -> srbd_reflex.trigger_mode ('geom_contact' is refused)
+REFLEX_CODES = {False: REFLEX_OFF, "tracking": REFLEX_TRACKING}
+
+
+class SrbdReflex(C.Structure):
+    """srbd_reflex (include/srbd_host.h): the early-stance detector's state and the spline generator's reflex fields."""
+    _fields_ = [("reflex_max_step_height", _D), ("early_stance_time_threshold", _D),
+                ("relative_tracking_error_threshold", _D), ("absolute_min_distance_error_threshold", _D),
+                ("hitmoments", _D * 4), ("hitpoints", (_D * 3) * 4), ("last_des_foot_pos", (_D * 3) * 4),
+                ("has_hitpoint", _I * 4), ("early_stance", _I * 4), ("trigger_mode", _I), ("blind", _I),
+                ("use_height_enhancement", _I), ("height_enhancement", _I), ("gait_cycles", _I),
+                ("max_gait_cycles", _I), ("reserved", _I * 2)]
+
+
+class SrbdReflexBatchIo(C.Structure):
+    """srbd_reflex_batch_io (include/srbd_mpc.h): the device arrays of one srbd_reflex_step_device call."""
+    _fields_ = [("stc", SrbdStcBatchIo), ("previous_contact", _P)]
+
+
 VFA_PASS, VFA_SEARCH, VFA_HOLD = 0, 1, 2
 
 
@@ -394,6 +414,10 @@ SIGNATURES.update({
     "srbd_stc_step": (_I, [C.POINTER(SrbdStc), C.POINTER(SrbdStcIo), _D]),
     "srbd_stc_apex": (_I, [C.POINTER(SrbdStc), _DP, _D]),
     "srbd_stc_full_stance": (_I, [_DP]),
+    "srbd_reflex_init": (_I, [C.POINTER(SrbdReflex), _D, _I, _I, _I]),
+    "srbd_reflex_detect": (_I, [C.POINTER(SrbdReflex), _DP, _DP, _DP, _DP, _D, _DP, _DP]),
+    "srbd_reflex_reference": (_I, [C.POINTER(SrbdStc), C.POINTER(SrbdReflex), _I, _DP, _DP, _DP, _DP, _DP]),
+    "srbd_reflex_step": (_I, [C.POINTER(SrbdStc), C.POINTER(SrbdReflex), C.POINTER(SrbdStcIo), _DP, _D]),
     "srbd_stc_touch_down": (_I, [_IP, _DP, _DP, _DP, _I, _I, _I]),
     "srbd_gait_apply_freq": (_I, [C.POINTER(SrbdPgg), C.POINTER(SrbdFrg), C.POINTER(SrbdStc), _I, _F]),
     "srbd_vfa_init": (_I, [C.POINTER(SrbdVfa)]),
@@ -455,6 +479,7 @@ SIGNATURES.update({
     "srbd_selftest_yaw_sincos": (_I, [_P, _I, _P]),
     "srbd_frg_step_device": (_I, [_P, _I, C.POINTER(SrbdFrgBatchIo), _P]),
     "srbd_stc_step_device": (_I, [_P, _I, _D, C.POINTER(SrbdStcBatchIo), _P]),
+    "srbd_reflex_step_device": (_I, [_P, _P, _I, _D, C.POINTER(SrbdReflexBatchIo), _P]),
     "srbd_vm_modulate_device": (_I, [_I, C.POINTER(SrbdVmBatchIo), _P]),
     "srbd_terrain_ref_step_device": (_I, [_P, _I, C.POINTER(SrbdTerrainRefBatchIo), _P]),
     # the gait adaptation loop: trigger, device form of srbd_batch_set_gait, frequency write-back
@@ -2259,18 +2284,12 @@ STC_OUTPUTS = {"tau": ((4, 3), "float64"), "des_foot_pos": ((4, 3), "float64"), 
                "des_joint_vel": ((4, 3), "float64"), "apex": ((), "int32"), "full_stance": ((), "int32")}
 
 
-def stc_step_device(stc, dt: float, jac, jac_dot, q_dot, foot_pos, foot_vel, qfrc_passive, qfrc_bias, mass_matrix,
-                    grfs, touch_down, contact, *, lift_off=None, frg=None, apex_interval: float = 0.01, out=None,
-                    want_joint_vel=True, want_flags=True, stream=None):
-    """srbd_stc_step_device: the swing clocks and the stance and swing torques of every environment, one launch
-    enqueued on ``stream`` (None: torch's current stream) without a host synchronisation.
-    stc (E, STC_BYTES) uint8: the srbd_stc structs, advanced in place.  jac / jac_dot / mass_matrix (E, 4, 3, 3), q_dot /
-    foot_pos / foot_vel / qfrc_passive / qfrc_bias / grfs / touch_down (E, 4, 3) float64; contact (E, 4) float32.
-    Exactly one of lift_off (E, 4, 3) float64 and frg (E, FRG_BYTES) uint8, the foothold reference generator's state.
-    ``out``: a dict of preallocated outputs (any of tau, des_foot_pos, des_foot_vel, des_joint_vel (E, 4, 3) float64,
-    apex, full_stance (E,) int32); absent tau / des_foot_pos / des_foot_vel are allocated, des_joint_vel and the two
-    flags only when asked for by ``want_joint_vel`` / ``want_flags`` (else they are NULL in the call).  Returns the
-    dict of the tensors written."""
+def _leg_step_device(what, native, stc, extra, dt, jac, jac_dot, q_dot, foot_pos, foot_vel, qfrc_passive, qfrc_bias,
+                     mass_matrix, grfs, touch_down, contact, lift_off, frg, apex_interval, out, want_joint_vel,
+                     want_flags, stream):
+    """The checks, the output allocation and the enqueue ``stc_step_device`` and ``reflex_step_device`` share.
+    ``extra``: further (name, tensor, tail shape, dtypes) inputs; ``native(E, dt, io)`` makes the C call with the filled
+    ``SrbdStcBatchIo``."""
     import math
 
     import torch
@@ -2285,12 +2304,13 @@ def stc_step_device(stc, dt: float, jac, jac_dot, q_dot, foot_pos, foot_vel, qfr
     if (lift_off is None) == (frg is None):
         raise ValueError("give exactly one of lift_off and frg")
     f64, f32, u8 = (torch.float64,), (torch.float32,), (torch.uint8,)
-    specs = [("stc", stc, (E, STC_BYTES), u8), ("jac", jac, (E, 4, 3, 3), f64), ("jac_dot", jac_dot, (E, 4, 3, 3), f64),
-             ("q_dot", q_dot, (E, 4, 3), f64), ("foot_pos", foot_pos, (E, 4, 3), f64),
-             ("foot_vel", foot_vel, (E, 4, 3), f64), ("qfrc_passive", qfrc_passive, (E, 4, 3), f64),
-             ("qfrc_bias", qfrc_bias, (E, 4, 3), f64), ("mass_matrix", mass_matrix, (E, 4, 3, 3), f64),
-             ("grfs", grfs, (E, 4, 3), f64), ("touch_down", touch_down, (E, 4, 3), f64),
-             ("contact", contact, (E, 4), f32)]
+    specs = [("stc", stc, (E, STC_BYTES), u8)] + [(n, t, (E,) + tail, d) for n, t, tail, d in extra]
+    specs += [("jac", jac, (E, 4, 3, 3), f64), ("jac_dot", jac_dot, (E, 4, 3, 3), f64),
+              ("q_dot", q_dot, (E, 4, 3), f64), ("foot_pos", foot_pos, (E, 4, 3), f64),
+              ("foot_vel", foot_vel, (E, 4, 3), f64), ("qfrc_passive", qfrc_passive, (E, 4, 3), f64),
+              ("qfrc_bias", qfrc_bias, (E, 4, 3), f64), ("mass_matrix", mass_matrix, (E, 4, 3, 3), f64),
+              ("grfs", grfs, (E, 4, 3), f64), ("touch_down", touch_down, (E, 4, 3), f64),
+              ("contact", contact, (E, 4), f32)]
     if lift_off is not None:
         specs.append(("lift_off", lift_off, (E, 4, 3), f64))
     else:
@@ -2324,9 +2344,51 @@ def stc_step_device(stc, dt: float, jac, jac_dot, q_dot, foot_pos, foot_vel, qfr
                             tau=ptr(o["tau"]), des_foot_pos=ptr(o["des_foot_pos"]),
                             des_foot_vel=ptr(o["des_foot_vel"]), des_joint_vel=ptr(o.get("des_joint_vel")),
                             apex=ptr(o.get("apex")), full_stance=ptr(o.get("full_stance")))
-        return lib.srbd_stc_step_device(stc.data_ptr(), E, dt, C.byref(io), s)
+        return native(E, dt, io, s)
 
-    return _enqueue(dev, stream, alloc, call, "srbd_stc_step_device")
+    return _enqueue(dev, stream, alloc, call, what)
+
+
+def stc_step_device(stc, dt: float, jac, jac_dot, q_dot, foot_pos, foot_vel, qfrc_passive, qfrc_bias, mass_matrix,
+                    grfs, touch_down, contact, *, lift_off=None, frg=None, apex_interval: float = 0.01, out=None,
+                    want_joint_vel=True, want_flags=True, stream=None):
+    """srbd_stc_step_device: the swing clocks and the stance and swing torques of every environment, one launch
+    enqueued on ``stream`` (None: torch's current stream) without a host synchronisation.
+    stc (E, STC_BYTES) uint8: the srbd_stc structs, advanced in place.  jac / jac_dot / mass_matrix (E, 4, 3, 3), q_dot /
+    foot_pos / foot_vel / qfrc_passive / qfrc_bias / grfs / touch_down (E, 4, 3) float64; contact (E, 4) float32.
+    Exactly one of lift_off (E, 4, 3) float64 and frg (E, FRG_BYTES) uint8, the foothold reference generator's state.
+    ``out``: a dict of preallocated outputs (any of tau, des_foot_pos, des_foot_vel, des_joint_vel (E, 4, 3) float64,
+    apex, full_stance (E,) int32); absent tau / des_foot_pos / des_foot_vel are allocated, des_joint_vel and the two
+    flags only when asked for by ``want_joint_vel`` / ``want_flags`` (else they are NULL in the call).  Returns the
+    dict of the tensors written."""
+    return _leg_step_device(
+        "srbd_stc_step_device", lambda E, dt, io, s: lib.srbd_stc_step_device(stc.data_ptr(), E, dt, C.byref(io), s),
+        stc, [], dt, jac, jac_dot, q_dot, foot_pos, foot_vel, qfrc_passive, qfrc_bias, mass_matrix, grfs, touch_down,
+        contact, lift_off, frg, apex_interval, out, want_joint_vel, want_flags, stream)
+
+
+REFLEX_BYTES = C.sizeof(SrbdReflex)
+
+
+def reflex_step_device(stc, reflex, dt: float, jac, jac_dot, q_dot, foot_pos, foot_vel, qfrc_passive, qfrc_bias,
+                       mass_matrix, grfs, touch_down, contact, previous_contact, *, lift_off=None, frg=None,
+                       apex_interval: float = 0.01, out=None, want_joint_vel=True, want_flags=True, stream=None):
+    """srbd_reflex_step_device: the early-stance detector, the swing clocks and the stance and swing torques with the
+    'scipy' spline generator of every environment, one launch enqueued on ``stream`` (None: torch's current stream)
+    without a host synchronisation.  stc (E, STC_BYTES) and reflex (E, REFLEX_BYTES) uint8: the srbd_stc and
+    srbd_reflex structs, advanced in place; previous_contact (E, 4) float32, the previous control step's contact
+    flags; everything else as ``stc_step_device``.  Returns the dict of the tensors written."""
+    def native(E, dt, io, s):
+        rio = SrbdReflexBatchIo(stc=io, previous_contact=previous_contact.data_ptr())
+        return lib.srbd_reflex_step_device(stc.data_ptr(), reflex.data_ptr(), E, dt, C.byref(rio), s)
+
+    import torch
+
+    extra = [("reflex", reflex, (REFLEX_BYTES,), (torch.uint8,)),
+             ("previous_contact", previous_contact, (4,), (torch.float32,))]
+    return _leg_step_device("srbd_reflex_step_device", native, stc, extra, dt, jac, jac_dot, q_dot, foot_pos, foot_vel,
+                            qfrc_passive, qfrc_bias, mass_matrix, grfs, touch_down, contact, lift_off, frg,
+                            apex_interval, out, want_joint_vel, want_flags, stream)
 
 
 def vm_modulate_device(lin, ang, feet, hips, max_distance: float = 0.2, *, out=None, stream=None):

@@ -93,7 +93,7 @@ mpc_params = {
 
 simulation_params = {
     # config.py:196-198
-    "swing_generator": "bezier_ref",  # 'explicit', 'bezier_ref' ('scipy' is not available)
+    "swing_generator": "bezier_ref",  # 'explicit', 'bezier_ref' ('scipy': ReflexSwingTrajectoryController)
     "swing_position_gain_fb": 500,
     "swing_velocity_gain_fb": 10,
     "step_height": 0.3 * hip_height,
@@ -135,6 +135,10 @@ simulation_params = {
         "bound": {"step_freq": 1.8, "duty_factor": 0.65, "type": 2},
         "full_stance": {"step_freq": 2, "duty_factor": 0.65, "type": 7},
     },
+    # config.py:256-259: the swing reflexes (helpers/early_stance_detector.py, ReflexSwingTrajectoryController)
+    "reflex_trigger_mode": "tracking",  # 'tracking', False ('geom_contact' is not available)
+    "reflex_max_step_height": 0.5 * hip_height,
+    "reflex_next_steps_height_enhancement": False,
     "velocity_modulator": True,  # config.py:260
     "ref_z": hip_height,
     "mpc_frequency": 100,
@@ -154,5 +158,6 @@ def set_robot(name: str) -> None:
     hip_height = HIP_HEIGHTS[name]
     mpc_params["grf_max"] = mass * gravity_constant
     simulation_params["step_height"] = 0.3 * hip_height
+    simulation_params["reflex_max_step_height"] = 0.5 * hip_height
     simulation_params["ref_z"] = hip_height
     simulation_params["tamols_params"]["h_des"] = hip_height

@@ -12,8 +12,10 @@ all of them in one launch (``srbd_stc_step_device``, ``include/srbd_mpc.h``).
 
 Differences from the reference, all stated in the header: the leg Jacobian is inverted by cofactors over the
 determinant where the reference calls ``np.linalg.pinv`` (the zero matrix for a singular Jacobian), the gains are
-scalars, the 'scipy' generator is not available, and the early-stance arguments are accepted and ignored (neither
-generator here reads them).
+scalars, and the early-stance arguments of these two classes are accepted and ignored (neither generator here reads
+them).  The 'scipy' generator, which does read them, is ``ReflexSwingTrajectoryController`` and
+``BatchedReflexSwingTrajectoryController`` below, with the early-stance detector ahead of it (``srbd_reflex_step``,
+``srbd_reflex_step_device``).
 """
 from __future__ import annotations
 
@@ -32,7 +34,9 @@ def _check(rc, what):
 
 def _generator_code(generator):
     if generator == "scipy":
-        raise NotImplementedError("the 'scipy' swing generator is not available: use 'bezier_ref' or 'explicit'")
+        raise NotImplementedError("the 'scipy' swing generator is not available in this class: use 'bezier_ref' or "
+                                  "'explicit', or ReflexSwingTrajectoryController / "
+                                  "BatchedReflexSwingTrajectoryController for the spline generator with its reflexes")
     # the reference's constructor takes any other name as 'explicit'
     return _lib.SWING_CODES.get(generator, _lib.SWING_EXPLICIT)
 
@@ -313,6 +317,166 @@ class BatchedSwingTrajectoryController:
         out = _lib.stc_step_device(self.state, dt, jac, jac_dot, q_dot, foot_pos, foot_vel, qfrc_passive, qfrc_bias,
                                    mass_matrix, grfs, touch_down, contact, lift_off=lift_off,
                                    frg=getattr(frg, "state", frg), apex_interval=apex_interval, out=self._out)
+        self._out = out
+        return (out["tau"], out["des_foot_pos"], out["des_foot_vel"], out["des_joint_vel"], out["apex"],
+                out["full_stance"])
+
+
+def _reflex_struct(reflex_max_step_height, blind, reflex_trigger_mode, next_steps_height_enhancement):
+    from .early_stance_detector import trigger_code
+
+    r = _lib.SrbdReflex()
+    height = float(reflex_max_step_height)
+    if _lib.lib.srbd_reflex_init(C.byref(r), height, int(bool(blind)), trigger_code(reflex_trigger_mode),
+                                 int(bool(next_steps_height_enhancement))) != _lib.OK:
+        raise ValueError(f"reflex_max_step_height must be finite, got {height}")
+    return r
+
+
+class ReflexSwingTrajectoryController(SwingTrajectoryController):
+    """The reference's ``SwingTrajectoryController(generator="scipy")`` together with the ``EarlyStanceDetector`` that
+    feeds it, as ``WBInterface.compute_stance_and_swing_torque`` composes them (wb_interface.py:362-415): ``esd`` is the
+    detector, on the same ``srbd_reflex`` struct the spline generator reads, and ``step`` is one whole tick
+    (``srbd_reflex_step``): the detector on what the previous tick left, the clock update, the leg law with the spline,
+    the desired foot positions kept for the next tick's detector.  ``reflex_max_step_height`` and ``blind`` are what the
+    reference's generator reads from its config (``reflex_max_step_height``, ``visual_foothold_adaptation == 'blind'``),
+    ``reflex_trigger_mode`` and ``next_steps_height_enhancement`` what its detector reads."""
+
+    def __init__(self, step_height, swing_period, position_gain_fb, velocity_gain_fb, generator="scipy", *,
+                 reflex_max_step_height, blind=False, reflex_trigger_mode="tracking",
+                 next_steps_height_enhancement=False):
+        if generator != "scipy":
+            raise ValueError(f"ReflexSwingTrajectoryController runs the 'scipy' generator, got {generator!r}")
+        from .early_stance_detector import EarlyStanceDetector
+
+        super().__init__(step_height, swing_period, position_gain_fb, velocity_gain_fb, "bezier_ref")
+        self.generator = "scipy"  # the struct's generator code is not read by srbd_reflex_*
+        self._r = _reflex_struct(reflex_max_step_height, blind, reflex_trigger_mode, next_steps_height_enhancement)
+        self.esd = EarlyStanceDetector(reflex=self._r)
+
+    reflex_max_step_height = property(lambda s: s._r.reflex_max_step_height)
+    blind_locomotion = property(lambda s: bool(s._r.blind))
+    reflex_next_steps_height_enhancement = property(lambda s: bool(s._r.height_enhancement),
+                                                    lambda s, v: setattr(s._r, "height_enhancement", int(bool(v))))
+
+    def compute_trajectory_references(self, leg_id, lift_off, touch_down):
+        """The spline generator alone at the leg's current clock, with the leg's hit as the detector holds it."""
+        pos, vel, acc = np.zeros(3), np.zeros(3), np.zeros(3)
+        _check(_lib.lib.srbd_reflex_reference(self._gp, C.byref(self._r), int(leg_id),
+                                              _lib.dptr(_arr(lift_off, (3,), "lift_off")),
+                                              _lib.dptr(_arr(touch_down, (3,), "touch_down")), _lib.dptr(pos),
+                                              _lib.dptr(vel), _lib.dptr(acc)), "compute_trajectory_references")
+        return pos, vel, acc
+
+    def compute_swing_control_cartesian_space(self, *args, **kwargs):
+        raise NotImplementedError("ReflexSwingTrajectoryController has no one-leg form: step() runs the whole tick, "
+                                  "the detector included")
+
+    def step(self, dt, jac, jac_dot, q_dot, foot_pos, foot_vel, qfrc_passive, qfrc_bias, mass_matrix, grfs, lift_off,
+             touch_down, contact, previous_contact, apex_interval=0.01):
+        """One whole control step (``srbd_reflex_step``).  The parent's arguments plus ``previous_contact`` (4), the
+        previous step's contact flags.  Returns the parent's tuple."""
+        out = {k: np.zeros((4, 3)) for k in ("tau", "des_foot_pos", "des_foot_vel", "des_joint_vel")}
+        apex, full = C.c_int32(0), C.c_int32(0)
+        m, v = (4, 3, 3), (4, 3)
+        arrays = dict(jac=_arr(jac, m, "jac"), jac_dot=_arr(jac_dot, m, "jac_dot"),
+                      mass_matrix=_arr(mass_matrix, m, "mass_matrix"), q_dot=_arr(q_dot, v, "q_dot"),
+                      foot_pos=_arr(foot_pos, v, "foot_pos"), foot_vel=_arr(foot_vel, v, "foot_vel"),
+                      qfrc_passive=_arr(qfrc_passive, v, "qfrc_passive"), qfrc_bias=_arr(qfrc_bias, v, "qfrc_bias"),
+                      grfs=_arr(grfs, v, "grfs"), lift_off=_arr(lift_off, v, "lift_off"),
+                      touch_down=_arr(touch_down, v, "touch_down"), contact=_arr(contact, (4,), "contact"), **out)
+        io = _lib.SrbdStcIo(apex_interval=float(apex_interval), apex=C.pointer(apex), full_stance=C.pointer(full),
+                            **{k: _lib.dptr(a) for k, a in arrays.items()})
+        _check(_lib.lib.srbd_reflex_step(self._gp, C.byref(self._r), C.byref(io),
+                                         _lib.dptr(_arr(previous_contact, (4,), "previous_contact")), float(dt)),
+               "srbd_reflex_step")
+        return (out["tau"], out["des_foot_pos"], out["des_foot_vel"], out["des_joint_vel"], int(apex.value),
+                int(full.value))
+
+
+class BatchedReflexSwingTrajectoryController(BatchedSwingTrajectoryController):
+    """``num_envs`` reflex leg controllers whose state lives on the device (``srbd_reflex_step_device``,
+    include/srbd_mpc.h): ``BatchedSwingTrajectoryController`` with the early-stance detector ahead of the torques and
+    the 'scipy' spline generator in the Bezier generators' place.  Environment ``e`` behaves as a host
+    ``ReflexSwingTrajectoryController`` whose ``step`` is called each control step: both structs keep the host structs'
+    bytes and the outputs are the host's, bit for bit.
+
+    ``state`` stays the (E, sizeof(srbd_stc)) tensor of the parent, so ``apply_step_frequency``, ``BatchedLoopReset``,
+    ``vfa.step_device(stc=)`` and ``rising_edge`` work on it unchanged; ``reflex_state`` is the
+    (E, sizeof(srbd_reflex)) uint8 tensor beside it.  ``reflex_max_step_height`` and ``blind`` are scalars or length-E
+    sequences; the trigger mode and the enhancement switch are shared.  ``BatchedLoopReset`` does not know
+    ``reflex_state``: a caller that restarts environments calls ``reset(mask)`` here as well, on the same stream."""
+
+    def __init__(self, num_envs, step_height, swing_period, position_gain_fb, velocity_gain_fb, *,
+                 reflex_max_step_height, blind=False, reflex_trigger_mode="tracking",
+                 next_steps_height_enhancement=False, device=None):
+        E = int(num_envs)
+        if not 1 <= E <= _lib.MAX_ENVS:
+            raise ValueError(f"num_envs must be 1..{_lib.MAX_ENVS}, got {num_envs}")
+        heights = np.asarray(reflex_max_step_height, dtype=np.float64)
+        blinds = np.asarray(blind)
+        for name, a in (("reflex_max_step_height", heights), ("blind", blinds)):
+            if a.ndim != 0 and a.shape != (E,):
+                raise ValueError(f"{name} must be a scalar or have {E} entries, got shape {a.shape}")
+        heights, blinds = np.broadcast_to(heights, (E,)), np.broadcast_to(blinds, (E,))
+        host = (_lib.SrbdReflex * E)()
+        for e in range(E):
+            host[e] = _reflex_struct(heights[e], blinds[e], reflex_trigger_mode, next_steps_height_enhancement)
+        super().__init__(E, step_height, swing_period, position_gain_fb, velocity_gain_fb, "bezier_ref", device=device)
+        import torch
+
+        raw = np.frombuffer(bytes(host), dtype=np.uint8).reshape(E, _lib.REFLEX_BYTES).copy()
+        with torch.cuda.stream(torch.cuda.current_stream(self.device)):
+            self._reflex_initial = torch.from_numpy(raw).to(self.device)
+            self.reflex_state = self._reflex_initial.clone()
+
+    def state_dict(self):
+        """``{"stc": (SrbdStc * E) array, "reflex": (SrbdReflex * E) array}`` (waits for the device): the parent's
+        structs, with ``rising_edge`` riding along as there, and the reflex structs, for checkpoints and tests."""
+        reflex = (_lib.SrbdReflex * self.num_envs).from_buffer_copy(self.reflex_state.cpu().numpy().tobytes())
+        return {"stc": super().state_dict(), "reflex": reflex}
+
+    def load_state_dict(self, state):
+        """What ``state_dict`` returns: both entries are required (each a ctypes array or its bytes), so a checkpoint
+        cannot resume with one half of the controller stale.  The parent's form alone -- a ``(SrbdStc * E)`` array or a
+        byte string -- is refused with a ValueError naming the missing half."""
+        import torch
+
+        if not hasattr(self, "reflex_state"):  # the parent's constructor uploading its own structs
+            return super().load_state_dict(state)
+        if not isinstance(state, dict) or set(state) != {"stc", "reflex"}:
+            raise ValueError("load_state_dict takes the dict state_dict returns, {'stc': ..., 'reflex': ...}: the "
+                             "srbd_stc structs alone would leave the hits, counters and last_des_foot_pos stale")
+        raw = np.frombuffer(bytes(state["reflex"]), dtype=np.uint8)
+        if raw.size != self.num_envs * _lib.REFLEX_BYTES:
+            raise ValueError(f"{self.num_envs} srbd_reflex structs expected "
+                             f"({self.num_envs * _lib.REFLEX_BYTES} bytes), got {raw.size} bytes")
+        super().load_state_dict(state["stc"])
+        with torch.cuda.stream(torch.cuda.current_stream(self.device)):
+            self.reflex_state.copy_(torch.from_numpy(raw.reshape(self.num_envs, _lib.REFLEX_BYTES).copy()))
+
+    def reset(self, mask, stream=None):
+        """The masked environments' reflex structs back to their constructor bytes: no hit, counter -1, flag off,
+        ``last_des_foot_pos`` zero.  mask (E,) bool, int32 or int64 cuda tensor; a torch copy on ``stream`` (None: the
+        current stream), no host wait.  The ``srbd_stc`` structs are ``BatchedLoopReset``'s to restore."""
+        import torch
+
+        from .loop_reset import mask_words
+
+        words = mask_words(mask, self.num_envs, stream)
+        with torch.cuda.stream(torch.cuda.current_stream(self.device) if stream is None else stream):
+            self.reflex_state.copy_(torch.where(words.to(self.device)[:, None] != 0, self._reflex_initial,
+                                                self.reflex_state))
+
+    def step(self, dt, jac, jac_dot, q_dot, foot_pos, foot_vel, qfrc_passive, qfrc_bias, mass_matrix, grfs, touch_down,
+             contact, previous_contact, lift_off=None, frg=None, apex_interval=0.01):
+        """One control step of every environment on torch's current stream (``srbd_reflex_step_device``): the
+        parent's arguments plus ``previous_contact`` (E, 4) float32, the previous control step's contact flags (the
+        row ``BatchedWBInterface`` owns).  Returns the parent's tuple."""
+        out = _lib.reflex_step_device(self.state, self.reflex_state, dt, jac, jac_dot, q_dot, foot_pos, foot_vel,
+                                      qfrc_passive, qfrc_bias, mass_matrix, grfs, touch_down, contact, previous_contact,
+                                      lift_off=lift_off, frg=getattr(frg, "state", frg), apex_interval=apex_interval,
+                                      out=self._out)
         self._out = out
         return (out["tau"], out["des_foot_pos"], out["des_foot_vel"], out["des_joint_vel"], out["apex"],
                 out["full_stance"])
